@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — particle-steps/sec of the 2D DFSPH dam-break (BASELINE.json metric) on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--particles P]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--particles P] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, step statistics).  Everything else the
+benchmark measures rides on `--full`: the dominant kernel's live roofline record and the per-kernel pass behind it, the further
+windows of `also` (one GPU, default workload) and the CPU baseline.  `--dump-outputs DIR` writes what the timed path computed in its
+last step as DIR/<name>.npy (see dump_outputs()).
 
 `--gpus N` with N > 1 started WITHOUT a launcher (no RANK in the environment) starts the N ranks itself: before anything touches
 the GPU this process runs `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py
@@ -165,6 +170,26 @@ def cpu_baseline(scale, budget_s=8.0, max_steps=20):
     }
 
 
+DUMP_SAMPLE = 1 << 20  # particles --dump-outputs writes at most (20 B each as float32 + 8 B of index: 28 MiB)
+STEP_STAT_FIELDS = ("density_iterations", "divergence_iterations", "warmstart_density", "warmstart_divergence", "avg_density_error",
+                    "avg_divergence", "dt_prev", "dt", "vmax", "flags", "remote_entries", "neighbor_entries")
+
+
+def dump_outputs(out_dir, pos, vel, density, last_stats, timer):
+    """--dump-outputs: what a caller of the timed path holds after its last step — the world's positions, velocities and densities
+    (a fixed sample, seed 0, of DUMP_SAMPLE particles in array order when there are more; sample_index holds their indices), that
+    step's statistics (STEP_STAT_FIELDS, float64) and the TimeManager's clock (next step ns, total simulated ns, steps)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(pos)
+    idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False)) if n > DUMP_SAMPLE else np.arange(n)
+    arrays = {"positions": np.asarray(pos, np.float32)[idx], "velocities": np.asarray(vel, np.float32)[idx],
+              "densities": np.asarray(density, np.float32)[idx], "sample_index": idx.astype(np.float64),
+              "last_step_stats": np.array([float(last_stats[k]) for k in STEP_STAT_FIELDS], np.float64),
+              "timer": np.array([timer.simulation_step_ns(), timer.total_simulated_ns, timer.num_steps], np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def dry_workload(per_gpu, world):
     """The workload string of a run without building the scene (add_fluid_rect, fluidparticleworld.rs:140-166: 90 particles per metre)."""
     sc = float(np.sqrt(per_gpu * world / 4050.0))
@@ -253,6 +278,12 @@ def main():
                     "that runs the K steps (sphx_solver_simulation_steps: the caller's frame loop, main.rs:348-350, inside the library)")
     ap.add_argument("--abi-calls", action="store_true", help="drive the two-phase C ABI from Python (one ctypes call per phase) instead of "
                                                              "the host mirror's one call per step (A/B runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the dominant kernel's roofline record (event brackets in the timed "
+                         "region, a per-kernel pass after it), the `also` windows and the CPU baseline (each still off with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed in the last one as DIR/<name>.npy (float32 / float64): positions, "
+                         "velocities, densities of a fixed seeded sample of at most 2^20 particles (sample_index), last_step_stats, timer")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--dry-run-scene", action="store_true",
@@ -264,11 +295,16 @@ def main():
 
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
+    if args.dump_outputs and args.gpus > 1:
+        sys.exit("bench.py: --dump-outputs writes the outputs of a one-process run (--gpus 1)")
     default_workload = args.particles is None
     if args.particles is None:
         args.particles = 16_000_000
-    # the further windows ride on the plain `python bench.py [--steps K --warmup W]` run only (what the driver starts)
-    args.also = (default_workload and not args.no_also and args.gpus == 1 and args.solver == "dfsph" and not args.skip_steps
+    args.roofline = args.full and not args.no_roofline
+    # the further windows ride on the `python bench.py --full [--steps K --warmup W]` run of the default workload only
+    args.also = (args.full and default_workload and not args.no_also and args.gpus == 1 and args.solver == "dfsph" and not args.skip_steps
                  and not any(args.fixed_iterations) and args.tolerance_scale == 1.0 and not args.force_tiles and not args.lists_32bit
                  and not args.no_roofline and not args.dry_run)
     launched = "RANK" in os.environ
@@ -467,9 +503,10 @@ def main():
                 pass
         return rec
 
-    def measure(one_step, k_steps, ctx, barrier, steps, warmup, skip_steps, want_roofline, n, reduce_max=None):
+    def measure(one_step, k_steps, ctx, barrier, steps, warmup, skip_steps, want_roofline, n, reduce_max=None, after_timed=None):
         """--skip-steps + --warmup untimed steps, then EXACTLY `steps` timed ones between two barriers.  Returns the timing, the step
-        statistics and the live roofline record of the dominant kernel."""
+        statistics and the live roofline record of the dominant kernel.  after_timed(stats) runs right behind the timed region, before
+        the roofline's extra pass steps on."""
         # Warm-up: every launch bracketed by hipEvents on the context's stream -> which kernel dominates a step.  (All ranks take the
         # same decision: the kernel mix is the same on every tile.)
         dominant, wprof = None, None
@@ -520,6 +557,8 @@ def main():
                 live, live_from = wprof[dominant], "warm-up steps (the timed region was too short to bracket a launch)"
         if reduce_max is not None:
             elapsed = reduce_max(elapsed)
+        if after_timed is not None:
+            after_timed(stats)
         roof = None
         if live is not None and live["launches"]:
             ev_ms = ctx.profile_event_overhead()  # what an EMPTY hipEvent bracket measures on this stream, same process
@@ -639,8 +678,9 @@ def main():
                 "note": "at 1 M particles the working set (~170 MB) sits inside the 256 MB Infinity Cache: the HBM roofline is "
                         "a soft bound there; 16 M (the default) is the size where it binds"}
 
-    def single_window(particles, skip_steps, steps, warmup, want_roofline=True):
-        """One measurement on ONE context: the dam-break scaled to `particles`, `skip_steps` untimed steps, warm-up, timed steps."""
+    def single_window(particles, skip_steps, steps, warmup, want_roofline=True, dump_dir=None):
+        """One measurement on ONE context: the dam-break scaled to `particles`, `skip_steps` untimed steps, warm-up, timed steps
+        (dump_dir: --dump-outputs of the timed steps)."""
         scale, w = scene_of(particles)
         pos, boundary = w.positions, w.boundary_particles
         n = len(pos)
@@ -681,7 +721,16 @@ def main():
             torch.cuda.synchronize()
             ctx.synchronize()
 
-        elapsed, stats, roof = measure(one_step, k_steps, ctx, barrier, steps, warmup, skip_steps, want_roofline, n)
+        def dump(stats):
+            if solver is not None:
+                solver.sync_world(w)  # what the caller's world holds after the step (the timed steps ran with sync_world = 0)
+                d = dict(pos=w.positions, vel=w.velocities, density=w.densities)
+            else:
+                d = ctx.download(ids=False)
+            dump_outputs(dump_dir, d["pos"], d["vel"], d["density"], stats[-1], timer)
+
+        elapsed, stats, roof = measure(one_step, k_steps, ctx, barrier, steps, warmup, skip_steps, want_roofline, n,
+                                       after_timed=dump if dump_dir else None)
         it = iteration_stats(stats)
         kbar = float(np.mean([s["neighbor_entries"] for s in stats])) / n
         rbar = float(np.mean([s.get("remote_entries", 0) for s in stats])) / n
@@ -707,7 +756,7 @@ def main():
                    8: "BASELINE configs[4] (128 M, 8 strips)"}
     multi = None
     if world == 1 and not args.force_tiles:
-        head = single_window(args.particles, args.skip_steps, args.steps, args.warmup, want_roofline=not args.no_roofline)
+        head = single_window(args.particles, args.skip_steps, args.steps, args.warmup, want_roofline=args.roofline, dump_dir=args.dump_outputs)
         also = []
         if args.also:
             # the windows the headline (configs[2], 16 M: the largest single-GPU config) does not show: configs[1] — 1 M particles, resident
@@ -763,7 +812,7 @@ def main():
             out["roofline"] = head["roof"]
         if also:
             out["also"] = also
-        if not args.no_cpu_baseline and args.solver == "dfsph":
+        if args.full and not args.no_cpu_baseline and args.solver == "dfsph":
             # a bounded sample of the headline's OWN workload: the same scene at the same size, one warm-up step and two
             # timed ones per variant (~6 s per step of the reference-faithful variant at 16 M on the GPU box's host); beside it the 1 M
             # sample of rounds 1-4, so that the line shows what the size does to the restatement's cost per particle-step
@@ -872,8 +921,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
+    def dump(stats):
+        d = multi.download()  # (one process holds every tile: --gpus 1 --force-tiles)
+        dump_outputs(args.dump_outputs, d["pos"], d["vel"], d["density"], stats[-1], timer)
+
     try:
-        elapsed, stats, roof = measure(one_step, k_steps, ctx, barrier, args.steps, args.warmup, args.skip_steps, not args.no_roofline, n, reduce_max)
+        elapsed, stats, roof = measure(one_step, k_steps, ctx, barrier, args.steps, args.warmup, args.skip_steps, args.roofline, n, reduce_max,
+                                       after_timed=dump if args.dump_outputs else None)
     except Exception:
         diag("the step loop")
         raise

@@ -133,3 +133,57 @@ def test_four_ranks_on_2x2_tiles_share_the_gpu_over_gloo():
     packed = int(c["parallelism"].split(" exchanges (")[1].split(" ")[0])
     total = int(c["parallelism"].split(" exchanges (")[0].split(" ")[-1])
     assert total >= 14 and packed >= total - 4, c["parallelism"]
+
+
+def test_bench_refuses_zero_steps_and_multi_rank_dumps():
+    rc, out, err = run(["--steps", "0", "--dry-run"])
+    assert rc != 0 and out.strip() == "" and "--steps" in err
+    rc, out, err = run(["--gpus", "2", "--dry-run", "--dump-outputs", "unused"])
+    assert rc != 0 and out.strip() == "" and "--dump-outputs" in err
+
+
+def test_full_flag_is_accepted():
+    rc, out, err = run(["--dry-run", "--full", "--steps", "4"])
+    assert rc == 0, err
+    d = json.loads([ln for ln in out.splitlines() if ln.strip()][-1])
+    assert d["steps"] == 4
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_same_outputs_every_time(tmp_path):
+    """A plain run times exactly --steps steps and carries none of --full's extras; --dump-outputs writes the last timed step's arrays,
+    identical from run to run with the same arguments."""
+    lines = []
+    for k in range(2):
+        rc, out, err = run(["--particles", "20000", "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path / f"run{k}")])
+        assert rc == 0, err[-2000:]
+        ls = [ln for ln in out.splitlines() if ln.strip()]
+        assert len(ls) == 1
+        lines.append(json.loads(ls[0]))
+    for d in lines:
+        assert d["steps"] == 7 and d["warmup"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert abs(d["value"] - d["config"]["particles_total"] * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+        assert "roofline" not in d and "also" not in d and "cpu_baseline" not in d
+    import numpy as np
+
+    names = sorted(os.listdir(tmp_path / "run0"))
+    assert names == ["densities.npy", "last_step_stats.npy", "positions.npy", "sample_index.npy", "timer.npy", "velocities.npy"]
+    assert sorted(os.listdir(tmp_path / "run1")) == names
+    n = lines[0]["config"]["particles_total"]
+    for name in names:
+        a, b = np.load(tmp_path / "run0" / name), np.load(tmp_path / "run1" / name)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all()
+        assert np.array_equal(a, b), name
+    assert np.load(tmp_path / "run0" / "positions.npy").shape == (n, 2)  # fewer than 2^20 particles: all of them, in array order
+    assert np.array_equal(np.load(tmp_path / "run0" / "sample_index.npy"), np.arange(n))
+    assert np.load(tmp_path / "run0" / "last_step_stats.npy").shape == (12,)
+
+
+@pytest.mark.gpu
+def test_full_run_adds_the_roofline_record():
+    rc, out, err = run(["--full", "--particles", "20000", "--steps", "8", "--warmup", "2", "--no-cpu-baseline"])
+    assert rc == 0, err[-2000:]
+    ls = [ln for ln in out.splitlines() if ln.strip()]
+    assert len(ls) == 1
+    d = json.loads(ls[0])
+    assert d["steps"] == 8 and d["value"] > 0 and d["roofline"]["kernel"] and d["roofline"]["per_kernel"]

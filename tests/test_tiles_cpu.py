@@ -313,7 +313,10 @@ stats = [t.step(timer) for _ in range(int(os.environ["STEPS"]))]
 d = t.download_owned()
 np.savez(os.path.join(os.environ["OUT_DIR"], f"rank{dist.get_rank()}.npz"), pos=d["pos"], vel=d["vel"], ids=d["ids"], density=d["density"],
          dt_ns=np.array([s["dt_ns"] for s in stats]), Id=np.array([s["density_iterations"] for s in stats]))
-dist.barrier(); dist.destroy_process_group()
+dist.barrier()
+if os.environ["COMM"] == "shm":
+    comm.close()  # (rank 0 unlinks the segment)
+dist.destroy_process_group()
 '''
 
 
@@ -321,14 +324,18 @@ dist.barrier(); dist.destroy_process_group()
 def test_tiles_gloo_world_size_2(tmp_path, comm):
     """The N > 1 launch path of bench.py: one process per rank, torch.distributed (gloo here, RCCL on the GPUs); scalars over
     torch.distributed or over the shared-memory all-reduce (bench.py's default)."""
+    import socket
     import subprocess
 
+    with socket.socket() as sk:  # a free port: it also names the shared-memory segment, which must not be one another run holds
+        sk.bind(("127.0.0.1", 0))
+        port = sk.getsockname()[1]
     steps = 40
     script = tmp_path / "worker.py"
     script.write_text(GLOO_WORKER)
     env = dict(os.environ, REPO_ROOT=os.path.dirname(HERE), OUT_DIR=str(tmp_path), STEPS=str(steps), OMP_NUM_THREADS="1", COMM=comm)
     subprocess.check_call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-                           "--master-port", "29531", str(script)], env=env, timeout=600)
+                           "--master-port", str(port), str(script)], env=env, timeout=600)
     pos, boundary = dam_break(1.0)
     ref, rstats, timer_ns = single_domain(pos, boundary, steps)
     parts = [np.load(tmp_path / f"rank{r}.npz") for r in range(2)]

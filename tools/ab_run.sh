@@ -4,7 +4,7 @@ out=$1; shift
 mkdir -p $out
 for v in base "$@"; do
   if [ $v = base ]; then unset SPHX_LIB; else export SPHX_LIB=$PWD/yasph2d_amd/variants/libsphx_$v.so; fi
-  timeout 300 python bench.py --steps 100 --no-cpu-baseline > $out/bench_$v.json 2> $out/bench_$v.err
+  timeout 300 python bench.py --full --steps 100 --no-cpu-baseline > $out/bench_$v.json 2> $out/bench_$v.err
   python3 - $out/bench_$v.json $v <<'PY'
 import json,sys
 for l in open(sys.argv[1]):

@@ -55,7 +55,7 @@ python3 tools/make_valu_json.py $out/sq_16M.txt 15995168 $out/valu_16M.json "$VS
 fi
 if [ "$MODE" = prof ]; then find $out -name "*.csv" -delete; find $out -type d -empty -delete; exit 0; fi
 # bench lines (with roofline + cpu_baseline) of the same build
-b() { name=$1; shift; timeout 900 python3 bench.py "$@" > $out/bench_$name.json 2> $out/bench_$name.err; echo "bench $name rc=$?"; }
+b() { name=$1; shift; timeout 900 python3 bench.py --full "$@" > $out/bench_$name.json 2> $out/bench_$name.err; echo "bench $name rc=$?"; }
 b default --steps 20 --warmup 5
 b 1M --steps 100 --particles 1000000 --no-cpu-baseline --no-also
 b 1M_fixed32 --steps 100 --particles 1000000 --fixed-iterations 3 2 --no-cpu-baseline --no-also
