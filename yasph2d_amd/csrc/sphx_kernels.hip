@@ -7,6 +7,7 @@
 // residual sums (f64 accumulation, fixed tree) and max|v|^2 (exact).
 #include "sphx_internal.hpp"
 #include "sphx_sqrt.hpp"
+#include "sphx_xcd.hpp"
 
 namespace sphx {
 
@@ -182,15 +183,8 @@ __device__ __forceinline__ size_t ell_index(uint32_t i, uint32_t k) { return ((s
 // predecessor stopped.  A speed hint like the mapping itself; no result depends on it.
 // shift = log2 of the chunk length in blocks (Consts::xcd_shift; 0: one contiguous eighth per XCD, the round 1-5 form; the host sets 7:
 // 128 blocks = 32 768 particles).
-__device__ __forceinline__ uint32_t xcd_bid(uint32_t rev = 0u, uint32_t shift = 0u) {
-    const uint32_t per = gridDim.x >> 3, q0 = blockIdx.x >> 3, x = blockIdx.x & 7u;
-    const uint32_t q = rev ? per - 1u - q0 : q0;
-    if (shift == 0u) return x * per + q;
-    const uint32_t full = per >> shift, g = q >> shift;
-    if (g < full) return (g << (shift + 3u)) + (x << shift) + (q - (g << shift));
-    const uint32_t r = per - (full << shift);  // the last, shorter group of chunks
-    return (full << (shift + 3u)) + x * r + (q - (full << shift));
-}
+// (the arithmetic: sphx_xcd.hpp, shared with the host and its exhaustive test)
+__device__ __forceinline__ uint32_t xcd_bid(uint32_t rev = 0u, uint32_t shift = 0u) { return xcd_map(blockIdx.x, gridDim.x, rev, shift); }
 
 // Gather base[idx] with a 32-bit byte offset from the (wave-uniform) array base: one shift instead of 64-bit address
 // arithmetic per access (scalar base + 32-bit vector offset addressing).  Arrays gathered this way stay below 4 GiB:
@@ -224,6 +218,12 @@ template <class R>
 struct Pair {
     R a, b;
 };
+// An array of an odd number of records ends in the middle of its last pair: gat2 of the last slot reads one record past the end.
+// Every device array the kernels read through gat2 comes from dev_alloc (sphx_launch.inc), which allocates GAT2_PAD bytes behind
+// the last record; DevTemp carries the pad too.  (The other hipMalloc calls hold no array gat2 reads: in sphx_launch.inc the device
+// scalars and the viewer's copy, in sphx_tiles.cpp the halo exchange buffers.)
+constexpr size_t GAT2_PAD = 16;
+static_assert(GAT2_PAD >= sizeof(float4), "the pad must hold a whole 16-byte pair load past the last record");
 __device__ __forceinline__ Pair<float2> gat2(const float2* __restrict__ base, uint32_t g) {
     const float4 q = gat((const float4*)base, g >> 1);
     return Pair<float2>{make_float2(q.x, q.y), make_float2(q.z, q.w)};
@@ -735,7 +735,7 @@ __global__ __launch_bounds__(256) void k_scatter(const uint32_t* __restrict__ ci
                                                   uint32_t* __restrict__ hist, uint32_t rev) {
     // (lane t of a workgroup takes the particles b0 + t, b0 + 256 + t, ...: every load and every store of a wavefront is one run of
     // consecutive words — particles arrive nearly sorted, so consecutive particles go to consecutive slots)
-    const uint32_t b0 = xcd_bid(rev & 1u, rev >> 8) * (256u * SCATTER_PER_LANE) + threadIdx.x;  // (rev: bit 0 direction, bits 8.. chunk shift)
+    const uint32_t b0 = xcd_bid(xcd_packed_rev(rev), xcd_packed_shift(rev)) * (256u * SCATTER_PER_LANE) + threadIdx.x;  // (rev: xcd_scatter_pack)
     if (b0 - threadIdx.x >= n) return;
     uint32_t w[SCATTER_PER_LANE];
 #pragma unroll
@@ -833,7 +833,7 @@ __global__ __launch_bounds__(256) void k_rank_gather(const uint32_t* __restrict_
     // is placed.  ONE is the default: unlike the scatter, whose lanes had a single 4-byte load each, this kernel has 24 bytes per slot
     // in flight and moves its bytes at 5.3 TB/s with one slot per lane — 126 / 128 / 145 us at 16 M with one / two / four
     // (profiles/r05_experiments/regrid.txt).
-    const uint32_t b0 = xcd_bid(rev & 1u, rev >> 8) * (256u * GATHER_PER_LANE);
+    const uint32_t b0 = xcd_bid(xcd_packed_rev(rev), xcd_packed_shift(rev)) * (256u * GATHER_PER_LANE);  // (rev: xcd_pack)
     if (b0 >= n) return;
     // The words of order[] around p: a cell holds three or four particles, so the cell mates the ranking below looks at are almost
     // always among them — and so are the two ends of the cell (ORDER_HEAD; round 5: the cell index of the record and the cell's range

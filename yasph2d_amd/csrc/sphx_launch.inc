@@ -100,7 +100,7 @@ constexpr uint32_t NT_COLD_FROM = 6000000u;
 // Consts::xcd_shift: chunks of 128 blocks of 256 particles (xcd_bid; a context of fewer than 8 x 128 blocks falls back to contiguous
 // eighths by construction).  Measured at 16 M and 1 M, from t = 0 and in the late windows (profiles/r06_experiments/xcd_chunks.txt):
 // 32 ... 128 blocks are within noise of each other, 512 costs 0.3-0.8 %, 2 048 gives half the late windows' gain back.
-inline uint32_t xcd_shift_of(const sphx_ctx* c) { return c->xcd_chunk >= 0 ? (uint32_t)c->xcd_chunk : 7u; }
+inline uint32_t xcd_shift_of(const sphx_ctx* c) { return c->xcd_chunk >= 0 ? xcd_shift_clamp(c->xcd_chunk) : 7u; }
 // Launch wrapper: `bytes` = algorithmic HBM bytes of this launch (DESIGN.md §4), used for the roofline line of bench.py.
 template <class F>
 inline void launch(sphx_ctx* c, const char* name, double bytes, F&& f) {
@@ -145,8 +145,8 @@ int dev_alloc(sphx_ctx* c, T** p, size_t count) {
         *p = nullptr;
     }
     if (count == 0) count = 1;
-    // (+16 bytes: the staging's two-slots-per-lane loads may read one record past the last slot of an array, nb_stage_load)
-    SPHX_HIP(c, hipMalloc((void**)p, count * sizeof(T) + 16));
+    // (+GAT2_PAD: the staging's two-slots-per-lane loads may read one record past the last slot of an array, gat2 / nb_stage_load)
+    SPHX_HIP(c, hipMalloc((void**)p, count * sizeof(T) + GAT2_PAD));
     return SPHX_OK;
 }
 template <class T>
@@ -162,7 +162,7 @@ struct DevTemp {
     ~DevTemp() {
         if (p) hipFree(p);
     }
-    hipError_t alloc(size_t count) { return hipMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T)); }
+    hipError_t alloc(size_t count) { return hipMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T) + GAT2_PAD); }  // (pad: as dev_alloc)
     operator T*() const { return p; }
 };
 
@@ -544,6 +544,15 @@ void drop_fused_count(sphx_ctx* c) {
     c->count_done = false;
     if (c->gdyn.hist && c->gdyn.len()) hipMemsetAsync(c->gdyn.hist, 0, (size_t)c->gdyn.len() * 4, c->stream);
 }
+// A call that failed on the device (SPHX_ERR_HIP, SPHX_ERR_NONFINITE) may have stopped between a cell count and the scatter that
+// counts the histogram back down: with or without a pending fused count, neither histogram is known to be zero any more.  Called by
+// step_finish's failure path and by every sphx_upload (new positions: any count made before is void anyway), so that a failure in
+// any entry point — step_begin's warm-up build included — is cleaned up by the re-upload the context then asks for.
+void clear_histograms(sphx_ctx* c) {
+    c->count_done = false;
+    for (Grid* g : {&c->gdyn, &c->gstat})
+        if (g->hist && g->len()) hipMemsetAsync(g->hist, 0, (size_t)g->len() * 4, c->stream);
+}
 
 // A cell count made by a tile's density correction (TileClassArgs) is made from ADVECTED positions and leaves out what the tile
 // retires: it is only good for the packing pass that takes over from there (tile_pack_impl).  Whoever else comes first drops it.
@@ -597,7 +606,7 @@ int build_grid(sphx_ctx* c, Grid& g, const float2* pos, uint32_t n, const Gather
     uint32_t first = 0;
     if (&g == &c->gdyn) {
         if (counted || partial) {
-            c->count_done = false;  // consumed: the scan below clears the histogram as always
+            c->count_done = false;  // consumed: k_scatter counts the histogram back down to zero as always
             if (partial) first = c->count_n;
         } else {
             drop_fused_count(c);
@@ -639,7 +648,7 @@ int build_grid(sphx_ctx* c, Grid& g, const float2* pos, uint32_t n, const Gather
     if (n) {
         launch(c, "cell_scatter", 12.0 * n, [&] {
             hipLaunchKernelGGL(k_scatter, dim3((nblocks(n, 256 * SCATTER_PER_LANE) + 7u) & ~7u), dim3(256), 0, st, (const uint32_t*)c->key, (const uint32_t*)c->slot, n, (const uint2*)g.fine,
-                               c->order, g.cbits(), g.hist, c->K.rev | ((xcd_shift_of(c) > 2u ? xcd_shift_of(c) - 2u : 0u) << 8));  // (its blocks hold 1 024 particles)
+                               c->order, g.cbits(), g.hist, xcd_scatter_pack(c->K.rev, xcd_shift_of(c)));  // (its blocks hold 1 024 particles)
         });
         const uint32_t ng = n;
         if (tile_n) {
@@ -663,7 +672,7 @@ int build_grid(sphx_ctx* c, Grid& g, const float2* pos, uint32_t n, const Gather
         if (ng)
             launch(c, "gather_attributes", gbytes * ng, [&] {
                 hipLaunchKernelGGL(k_rank_gather, dim3(gb2), dim3(256), 0, st, (const uint32_t*)c->order, (const uint32_t*)c->key, ng, n,
-                                   (const uint2*)g.fine, ga, tile_n ? (const uint32_t*)&ds->sort_total : (const uint32_t*)nullptr, g.cbits(), c->K.rev | (xcd_shift_of(c) << 8));
+                                   (const uint2*)g.fine, ga, tile_n ? (const uint32_t*)&ds->sort_total : (const uint32_t*)nullptr, g.cbits(), xcd_pack(c->K.rev, xcd_shift_of(c)));
             });
     }
     return SPHX_OK;
@@ -1337,7 +1346,7 @@ int sphx_create(const sphx_params* params, sphx_ctx** out) {
     if (const char* e = std::getenv("SPHX_NT_COLD_STORES")) c->nt_cold_stores = e[0] != '0' ? 1 : 0;
     if (const char* e = std::getenv("SPHX_TILE_FUSE_CLASS")) c->tile_fuse_class = e[0] != '0';
     if (const char* e = std::getenv("SPHX_FUSE_DIV")) c->fuse_div = e[0] != '0';
-    if (const char* e = std::getenv("SPHX_XCD_CHUNK")) c->xcd_chunk = std::max(0, std::atoi(e));  // log2(blocks per chunk); 0: contiguous eighths
+    if (const char* e = std::getenv("SPHX_XCD_CHUNK")) c->xcd_chunk = (int)xcd_shift_clamp(std::atoi(e));  // log2(blocks per chunk); 0: contiguous eighths
     if (const char* e = std::getenv("SPHX_ALTERNATE_SWEEP")) c->alternate_sweep = e[0] == '2' ? 2 : (e[0] != '0');  // (0: every launch bottom-up; 2: the scatter toggles too — A/B forms)
     if (const char* e = std::getenv("SPHX_FUSE_WARM")) c->fuse_warm = e[0] != '0';  // (A/B: the divergence warm start as a walk of its own behind k_neighbor_build<1>)
     c->P = *params;
@@ -1530,6 +1539,7 @@ int sphx_upload(sphx_ctx* c, const float* pos_xy, const float* vel_xy, uint32_t 
     if (c->in_step) return c->fail(SPHX_ERR_NOT_READY, "sphx_upload between step_begin and step_finish");
     SPHX_HIP(c, hipSetDevice(c->device));
     SPHX_HIP(c, hipStreamSynchronize(c->stream));
+    clear_histograms(c);
     int rc;
     if ((rc = alloc_particles(c, n))) return rc;
     c->N = n;
@@ -1730,7 +1740,11 @@ int sphx_step_finish(sphx_ctx* c, float dt, sphx_step_stats* out) {
     s.vmax = c->step_vmax;
     int rc;
     auto broken = [&](int code) {  // the device state is not a consistent particle set any more
-        if (code == SPHX_ERR_HIP || code == SPHX_ERR_NONFINITE) c->uploaded = false;
+        if (code == SPHX_ERR_HIP || code == SPHX_ERR_NONFINITE) {
+            c->uploaded = false;
+            clear_histograms(c);
+        }
+        drop_fused_count(c);  // (a count of the next build made by this step's density correction: that build does not come)
         c->ahead.valid = false;
         c->div_error_fused = c->div_warm_fused = false;
         c->fuse_count_ok = false;
@@ -1747,6 +1761,7 @@ int sphx_step_finish(sphx_ctx* c, float dt, sphx_step_stats* out) {
                 // the prediction already ran with the device's dt: the velocities on the device are not the host's any more
                 c->uploaded = false;
                 c->law_active = false;
+                drop_fused_count(c);
                 return c->fail(SPHX_ERR_INVALID_ARGUMENT, "dt differs from the sphx_timer_law handed to sphx_step_begin_law; upload the state again");
             }
             pre = c->pre_seq;
