@@ -49,7 +49,9 @@ extern "C" {
                             * 2: sphx_step_stats.remote_entries, sphx_multi_*, frame-loop calls, sphx_sub_regrid_{div,warm}, SPHX_FLAG_DENSE_CELL
                             * 3: sphx_comm_ops.abort, sphx_multi_info_t list statistics, sphx_shm_abort (and sphx_shm_open as a collective),
                             *    sphx_build_stats, sphx_sub_run_ahead, sphx_tile_carry_warmstart, sphx_tile_defer_advect, sphx_sub_predict_iteration, sphx_tile_band_packs,
-                            *    sphx_multi_info_t.band_packs (was reserved) */
+                            *    sphx_multi_info_t.band_packs (was reserved)
+                            * 5 (additive): sphx_params.viscosity_model / .fluid_viscosity (were reserved[0..1]; zero = XSPH, the behaviour
+                            *    before), SPHX_VISCOSITY_*, sphx_get_viscosity */
 
 /* ---- status codes ---- */
 enum {
@@ -75,6 +77,13 @@ enum {
     SPHX_FLAG_DENSE_CELL = 32u              /* a cell held more than 4096 particles (a collapse to a point, or strays parked together):
                                                their order INSIDE that cell follows arrival, not the previous index — the stable rank
                                                costs occupancy^2 loads and would stall the GPU; everything else is unaffected */
+};
+
+/* sphx_params.viscosity_model: the ViscosityModel the DFSPH / WCSPH solver is generic over (src/sph/viscositymodel/,
+ * DFSPHSolver<V> dfsph.rs:16-47, WCSPHSolver<V> wscsph.rs:14-42).  Zero is XSPH, so a zero-filled struct behaves as before. */
+enum {
+    SPHX_VISCOSITY_XSPH = 0,     /* XSPHViscosityModel (xsph.rs): xsph_epsilon */
+    SPHX_VISCOSITY_PHYSICAL = 1  /* PhysicalViscosityModel (physical.rs): fluid_viscosity * m * Viscosity::laplacian / rho_j (viscosity.rs:44-46) */
 };
 
 /* kernel kinds for sphx_update_densities (src/sph/smoothing_kernel/) */
@@ -107,7 +116,11 @@ typedef struct sphx_params {
                                           entries.  0 = default (512, the table's capacity); SPHX_LISTS_32BIT = 32-bit global indices
                                           everywhere (traversals gather from global memory); smaller values only put more workgroups on
                                           that fallback (test aid).  Results never depend on it. */
-    uint32_t reserved[3];
+    uint32_t viscosity_model;          /* SPHX_VISCOSITY_*; sphx_create rejects other values (SPHX_ERR_INVALID_ARGUMENT) */
+    float fluid_viscosity;             /* PhysicalViscosityModel::fluid_viscosity (mu, Pa s), physical.rs:8,14: default 1.0016/1000 (water);
+                                          main.rs:96 sets 0.01.  Only the physical model reads it; it must be finite (negative is accepted,
+                                          as in the reference) */
+    uint32_t reserved[1];
 } sphx_params;
 #define SPHX_LISTS_32BIT 0xFFFFFFFFu
 
@@ -190,7 +203,7 @@ int sphx_step_begin_law(sphx_ctx* ctx, float dt_prev, const sphx_timer_law* law,
  *             update_densities(Poly6) (:153), update_accellerations (:59-118, :154), max |v + a*dt| (:158-161) -> *out_vmax
  *   host    = dt = time_manager.update_simulation_step(2*radius, vmax).as_secs_f32()   (:162-164)
  *   phase B = leap frog 2 (:168-177)
- * Constants as WCSPHSolver::new (:31-49): Poly6 density kernel, Spiky pressure kernel, XSPH viscosity, Tait gamma 7,
+ * Constants as WCSPHSolver::new (:31-49): Poly6 density kernel, Spiky pressure kernel, XSPH viscosity (or the physical model: sphx_params.viscosity_model), Tait gamma 7,
  * set_compressibility(0.01, 1.0), boundary_force_factor 1.  sphx_clear_cached also drops the accelerations (:122-124).
  * One context runs one solver: the DFSPH and the WCSPH step share the acceleration array. */
 int sphx_wcsph_step_begin(sphx_ctx* ctx, float dt, float* out_vmax);
@@ -222,6 +235,10 @@ int sphx_grid_info(const sphx_ctx* ctx, int which, uint32_t* out4);
 /* derived kernel constants: out[0..2] = Wendland {h_inv, normalizer, normalizer_grad} (wendland_quintic_c2.rs:24-30),
  * out[3..5] = Poly6 {hsq, normalizer, normalizer_grad} (poly6.rs:16-23) */
 int sphx_get_constants(const sphx_ctx* ctx, float* out6);
+/* the viscosity model the context runs (any pointer may be NULL): the model, fluid_viscosity and the Viscosity kernel's
+ * normalizer_laplacian = 360 / (29 pi h^5) (viscosity.rs:24).  A shim calls it once after sphx_create: a library older than
+ * these fields does not export it (and would ignore the reserved words the fields occupy). */
+int sphx_get_viscosity(const sphx_ctx* ctx, uint32_t* model, float* fluid_viscosity, float* normalizer_laplacian);
 
 
 /* ---- spatial tiles (multi-GPU) ------------------------------------------------------------------------------

@@ -12,10 +12,10 @@ import numpy as np
 
 from . import _lib
 from ._lib import (FLAG_DENSITY_ITER_CAP, FLAG_DIVERGENCE_ITER_CAP, FLAG_DENSE_CELL, FLAG_NEIGHBOR_CAP, FLAG_STRAY_PARTICLES, FLAG_WARMUP, KERNEL_POLY6,  # noqa: F401
-                   KERNEL_SPIKY, KERNEL_WENDLAND_C2, SphxError, SphxKernelTime, SphxParams, SphxStepStats)
+                   KERNEL_SPIKY, KERNEL_WENDLAND_C2, VISCOSITY_PHYSICAL, VISCOSITY_XSPH, SphxError, SphxKernelTime, SphxParams, SphxStepStats)
 
 __all__ = ["SphxContext", "FluidParticleWorld", "TimeManager", "DFSPHSolver", "DFSPHMultiSolver", "default_params", "duration_from_secs_f32",
-           "duration_as_secs_f32", "SphxError", "WCSPHSolver"]
+           "duration_as_secs_f32", "SphxError", "WCSPHSolver", "VISCOSITY_XSPH", "VISCOSITY_PHYSICAL"]
 
 
 def _p(a):
@@ -25,14 +25,26 @@ def _p(a):
 LISTS_32BIT = 0xFFFFFFFF  # sphx_params.list_span_limit: never compress the neighbour lists
 
 
-def default_params(smoothing_factor=2.0, particle_density=10000.0, fluid_density=100.0, device=0, fixed_iterations=(0, 0)):
-    """sphx_default_params: the constants of the reference app (main.rs:85-89, dfsph.rs:49-55)."""
+_VISCOSITY_MODELS = {"xsph": VISCOSITY_XSPH, "physical": VISCOSITY_PHYSICAL}
+
+
+def default_params(smoothing_factor=2.0, particle_density=10000.0, fluid_density=100.0, device=0, fixed_iterations=(0, 0), viscosity="xsph",
+                   fluid_viscosity=None):
+    """sphx_default_params: the constants of the reference app (main.rs:85-89, dfsph.rs:49-55).
+
+    viscosity: the solver's ViscosityModel, "xsph" (XSPHViscosityModel, main.rs:100) or "physical" (PhysicalViscosityModel,
+    physical.rs); fluid_viscosity: its mu (None keeps the library default 1.0016e-3, physical.rs:14; main.rs:96 sets 0.01)."""
+    if viscosity not in _VISCOSITY_MODELS:
+        raise ValueError("viscosity must be one of %s, not %r" % (sorted(_VISCOSITY_MODELS), viscosity))
     p = SphxParams()
     rc = _lib.lib().sphx_default_params(smoothing_factor, particle_density, fluid_density, C.byref(p))
     if rc:
         raise SphxError(rc, "sphx_default_params")
     p.device = device
     p.fixed_density_iterations, p.fixed_divergence_iterations = fixed_iterations
+    p.viscosity_model = _VISCOSITY_MODELS[viscosity]
+    if fluid_viscosity is not None:
+        p.fluid_viscosity = fluid_viscosity
     return p
 
 
@@ -204,6 +216,12 @@ class SphxContext:
         out = np.zeros(6, np.float32)
         self._chk(self.L.sphx_get_constants(self.h, _p(out)))
         return out
+
+    def viscosity(self):
+        """sphx_get_viscosity: (model name, fluid_viscosity, normalizer_laplacian) the context runs."""
+        m, mu, nlap = C.c_uint32(), C.c_float(), C.c_float()
+        self._chk(self.L.sphx_get_viscosity(self.h, C.byref(m), C.byref(mu), C.byref(nlap)))
+        return {VISCOSITY_XSPH: "xsph", VISCOSITY_PHYSICAL: "physical"}[m.value], np.float32(mu.value), np.float32(nlap.value)
 
     def profile_enable(self, on=True):
         self._chk(self.L.sphx_profile_enable(self.h, int(on)))

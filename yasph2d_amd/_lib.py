@@ -12,6 +12,7 @@ CSRC = os.path.join(_HERE, "csrc")
 OK, ERR_INVALID_ARGUMENT, ERR_NO_DEVICE, ERR_HIP, ERR_NOT_READY, ERR_NONFINITE, ERR_NEIGHBOR_PANIC, ERR_CAPACITY, ERR_OUT_OF_DOMAIN = range(9)
 FLAG_NEIGHBOR_CAP, FLAG_DENSITY_ITER_CAP, FLAG_DIVERGENCE_ITER_CAP, FLAG_WARMUP, FLAG_STRAY_PARTICLES, FLAG_DENSE_CELL = 1, 2, 4, 8, 16, 32
 KERNEL_WENDLAND_C2, KERNEL_POLY6, KERNEL_SPIKY = 0, 1, 2
+VISCOSITY_XSPH, VISCOSITY_PHYSICAL = 0, 1  # sphx_params.viscosity_model
 
 
 class SphxParams(C.Structure):
@@ -31,7 +32,9 @@ class SphxParams(C.Structure):
         ("fixed_divergence_iterations", C.c_uint32),
         ("device", C.c_int32),
         ("list_span_limit", C.c_uint32),
-        ("reserved", C.c_uint32 * 3),
+        ("viscosity_model", C.c_uint32),
+        ("fluid_viscosity", C.c_float),
+        ("reserved", C.c_uint32 * 1),
     ]
 
 
@@ -135,6 +138,7 @@ SIGNATURES = {
     "sphx_grid_info": (_i, [_vp, _i, C.POINTER(_u32)]),
     "sphx_last_flags": (_u32, [_vp]),
     "sphx_get_constants": (_i, [_vp, _vp]),
+    "sphx_get_viscosity": (_i, [_vp, C.POINTER(_u32), C.POINTER(_f), C.POINTER(_f)]),
     "sphx_reserve": (_i, [_vp, _u32]),
     "sphx_tile_configure": (_i, [_vp, _i, _u32, _u32, _u32, _i, _i]),
     "sphx_tile_upload": (_i, [_vp, _vp, _vp, _vp, _u32]),

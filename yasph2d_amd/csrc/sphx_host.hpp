@@ -107,7 +107,7 @@ struct Solver {
     virtual void simulation_step(FluidParticleWorld& fluid_world, TimeManager& time_manager) = 0;
 };
 
-// DFSPHSolver<XSPHViscosityModel> (dfsph.rs:16-61) running on the HIP device through the C ABI of sphx.h
+// DFSPHSolver<V> (dfsph.rs:16-61; V = sphx_params.viscosity_model, XSPH unless the params say otherwise) running on the HIP device through the C ABI of sphx.h
 class HipDfsphSolver : public Solver {
    public:
     HipDfsphSolver(const FluidParticleWorld& world, const sphx_params* params_or_null);
@@ -123,11 +123,13 @@ class HipDfsphSolver : public Solver {
     std::string last_error;
     sphx_step_stats last_stats{};
     sphx_ctx* ctx() { return ctx_; }
+    // the params a null params_or_null stands for: sphx_default_params + the world's properties (a caller that changes one field,
+    // e.g. the viscosity model, starts from these)
+    static sphx_params params_of(const FluidParticleWorld& world, const sphx_params* params_or_null);
 
    protected:
     struct NoContext {};
     explicit HipDfsphSolver(NoContext) {}  // for solvers that hold their device state elsewhere (HipDfsphMultiSolver)
-    static sphx_params params_of(const FluidParticleWorld& world, const sphx_params* params_or_null);
     virtual int device_step(FluidParticleWorld& fluid_world, TimeManager& time_manager);  // the two-phase step on the device
     sphx_ctx* ctx_ = nullptr;
 

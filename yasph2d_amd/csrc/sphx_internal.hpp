@@ -94,6 +94,21 @@ struct Consts {
     uint32_t rev;  // this launch sweeps the particle blocks from the top down (xcd_bid; alternates from launch to launch, sphx_ctx::alternate_sweep)
 };
 
+// The viscosity model (sphx_params.viscosity_model; PhysicalViscosityModel, physical.rs, with the Viscosity kernel's Laplacian,
+// viscosity.rs:19-47).  Kept out of Consts on purpose: Consts travels by value in the middle of every kernel's argument list, and
+// three more words there would move the kernel-argument offsets of every kernel.  The model is a compile-time choice of the two
+// kernels that evaluate it (k_nonpressure, k_wcsph_accel); only their physical instantiations take this struct as a trailing
+// argument, the XSPH ones an empty ViscArg that occupies no kernel-argument space, so their code is the code from before.
+struct ViscConsts {
+    uint32_t visc_model;  // SPHX_VISCOSITY_* (host dispatch only)
+    float mu;             // PhysicalViscosityModel::fluid_viscosity
+    float vis_nlap;       // Viscosity::normalizer_laplacian = 360 / ((29 pi) h^5), viscosity.rs:24
+};
+template <int VM>
+struct ViscArg {};
+template <>
+struct ViscArg<SPHX_VISCOSITY_PHYSICAL> : ViscConsts {};
+
 // wave-sliced neighbour lists (one 16 KiB slice per 64 particles); counts[i] = count_dynamic | count_total << 7 = NeighborRange
 // (neighborhood_search.rs:269-273) in 16 bits; wave[i >> 6] = entries of the wavefront's quarter of the out-of-window table
 // remote[(i >> 8) * REMOTE_CAP + ((i >> 6) & 3) * WAVE_REMOTE ..] | wide << 31 (the list format is decided per wavefront)
@@ -280,6 +295,7 @@ struct ProfPending {
 struct sphx_ctx {
     sphx_params P;
     sphx::Consts K;
+    sphx::ViscConsts VK;  // the viscosity model's constants (set by sphx_create, next to K)
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;

@@ -2513,13 +2513,21 @@ __global__ __launch_bounds__(64) void k_publish_vmax(DevScalars* scal, VmaxArgs 
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// a10 + a11: non-pressure acceleration with XSPH (dfsph.rs:436-469, xsph.rs:21-23) and max |v + a*dt|^2 (dfsph.rs:474-477)
+// a10 + a11: non-pressure acceleration with the viscosity model VM (dfsph.rs:436-469; XSPH xsph.rs:21-23 or physical physical.rs:21-23)
+// and max |v + a*dt|^2 (dfsph.rs:474-477)
 // ------------------------------------------------------------------------------------------------------------------
 #ifndef NONP_BOUNDS
 #define NONP_BOUNDS __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
 #endif
+// fluid_viscosity * m * L(r) / rho_j, evaluated left to right (physical.rs:22), L(r) = normalizer_laplacian * (h - r) without an
+// r < h test (viscosity.rs:44-46); mu_m = fluid_viscosity * m
+__device__ __forceinline__ float physical_visc(const Consts& K, const ViscConsts& V, float mu_m, float r, float rho_j) {
+    return mu_m * (V.vis_nlap * (K.h - r)) / rho_j;
+}
+template <int VM>
 __global__ NONP_BOUNDS void k_nonpressure(PVr PV, const float* __restrict__ density, uint32_t n, uint32_t soff, Consts K,
-                                                      float dt, NbView nb, float2* __restrict__ accel, DevScalars* __restrict__ scal, uint32_t vslot) {
+                                                      float dt, NbView nb, float2* __restrict__ accel, DevScalars* __restrict__ scal, uint32_t vslot,
+                                                      ViscArg<VM> V) {
     __shared__ Stage<2, 1> rec;  // position, velocity; density
     const uint32_t blk = xcd_bid(K.rev, K.xcd_shift);
     const uint32_t i = blk * 256 + threadIdx.x;
@@ -2546,21 +2554,42 @@ __global__ NONP_BOUNDS void k_nonpressure(PVr PV, const float* __restrict__ dens
         const float4 pvi = h.wide ? ldpv(PV, i) : rec.vec01(oi);
         const uint32_t cd = h.cd;
         float ax = K.ax, ay = K.ay;
-        const float em = K.xsph_eps * K.mass;
         struct Rec {
             float4 pv;
             float rho;
         };
-        auto consume = [&](const Rec& r, uint32_t) {
-            const float dx = r.pv.x - pvi.x, dy = r.pv.y - pvi.y;
-            const float r_sq = dx * dx + dy * dy;
-            const float f = em * poly6_eval(K, r_sq) / (r.rho * dt);
-            ax = ax + f * (r.pv.z - pvi.z);
-            ay = ay + f * (r.pv.w - pvi.w);
-        };
-        nb_traverse(
-            h, cd, [&](uint32_t o) { return Rec{rec.vec01(o), rec.scal<0>(o)}; },
-            [&](uint32_t g) { return Rec{ldpv(PV, g), gat(density, g)}; }, consume);
+        if constexpr (VM == SPHX_VISCOSITY_PHYSICAL) {
+            // the same walk with r = sqrt(r_sq) (dfsph.rs:461): only ALU is added, the staged record already holds everything
+            const float mu_m = V.mu * K.mass;
+            auto walk = [&](auto fast) {
+                auto consume = [&](const Rec& r, uint32_t) {
+                    const float dx = r.pv.x - pvi.x, dy = r.pv.y - pvi.y;
+                    const float r_sq = dx * dx + dy * dy;
+                    const float f = physical_visc(K, V, mu_m, sqrt_dist<decltype(fast)::value>(r_sq), r.rho);
+                    ax = ax + f * (r.pv.z - pvi.z);
+                    ay = ay + f * (r.pv.w - pvi.w);
+                };
+                nb_traverse(
+                    h, cd, [&](uint32_t o) { return Rec{rec.vec01(o), rec.scal<0>(o)}; },
+                    [&](uint32_t g) { return Rec{ldpv(PV, g), gat(density, g)}; }, consume);
+            };
+            if (K.q_noclamp)  // (kernel argument: a scalar branch; sqrt_dist)
+                walk(std::true_type{});
+            else
+                walk(std::false_type{});
+        } else {
+            const float em = K.xsph_eps * K.mass;
+            auto consume = [&](const Rec& r, uint32_t) {
+                const float dx = r.pv.x - pvi.x, dy = r.pv.y - pvi.y;
+                const float r_sq = dx * dx + dy * dy;
+                const float f = em * poly6_eval(K, r_sq) / (r.rho * dt);
+                ax = ax + f * (r.pv.z - pvi.z);
+                ay = ay + f * (r.pv.w - pvi.w);
+            };
+            nb_traverse(
+                h, cd, [&](uint32_t o) { return Rec{rec.vec01(o), rec.scal<0>(o)}; },
+                [&](uint32_t g) { return Rec{ldpv(PV, g), gat(density, g)}; }, consume);
+        }
         accel[i] = make_float2(ax, ay);
         const float px = pvi.z + ax * dt, py = pvi.w + ay * dt;
         vsq = tile_owns(K, pvi.x, pvi.y) ? px * px + py * py : 0.0f;  // ghosts of a tile are somebody else's particles
@@ -2633,9 +2662,11 @@ __device__ __forceinline__ float powi7(float a) {
 __device__ __forceinline__ float wcsph_pressure(const Consts& K, float local_density) {
     return K.wc_stiffness * (powi7(fmaxf(local_density / K.rho0, 1.0f)) - 1.0f);
 }
-// update_accellerations (wscsph.rs:59-118) + max |v + a*dt|^2 (wscsph.rs:158-161)
+// update_accellerations (wscsph.rs:59-118) with the viscosity model VM + max |v + a*dt|^2 (wscsph.rs:158-161)
+template <int VM>
 __global__ TRAV_BOUNDS void k_wcsph_accel(PVr PV, const float* __restrict__ density, uint32_t n, uint32_t soff, Consts K,
-                                          float dt, NbView nb, float2* __restrict__ accel, DevScalars* __restrict__ scal, uint32_t vslot) {
+                                          float dt, NbView nb, float2* __restrict__ accel, DevScalars* __restrict__ scal, uint32_t vslot,
+                                          ViscArg<VM> V) {
     __shared__ Stage<2, 1> rec;  // position, velocity; density
     const uint32_t blk = xcd_bid(K.rev, K.xcd_shift);
     const uint32_t i = blk * 256 + threadIdx.x;
@@ -2680,7 +2711,11 @@ __global__ TRAV_BOUNDS void k_wcsph_accel(PVr PV, const float* __restrict__ dens
                     const float sg = K.sp_ngrad * dd * dd / (r + 1.0e-10f);                          // Spiky::gradient, spiky.rs:34-37
                     float tx = ax + pu * (sg * dx);
                     float ty = ay + pu * (sg * dy);
-                    const float f = K.xsph_eps * K.mass * poly6_eval(K, r_sq) / (q.rho * dt);        // xsph.rs:21-23
+                    float f;
+                    if constexpr (VM == SPHX_VISCOSITY_PHYSICAL)
+                        f = physical_visc(K, V, V.mu * K.mass, r, q.rho);                             // physical.rs:21-23
+                    else
+                        f = K.xsph_eps * K.mass * poly6_eval(K, r_sq) / (q.rho * dt);               // xsph.rs:21-23
                     ax = tx + f * (q.pv.z - pvi.z);
                     ay = ty + f * (q.pv.w - pvi.w);
                 } else {

@@ -1207,8 +1207,12 @@ uint32_t take_vmax_slot(sphx_ctx* c) {
 void enqueue_nonpressure(sphx_ctx* c, float dt_prev, uint32_t vslot) {
     const uint32_t n = c->N;
     launch(c, "nonpressure_accel_vmax", (16.0 + 8 + 4 + list_bytes(c)) * n, [&] {
-        hipLaunchKernelGGL(k_nonpressure, dim3(nblocks(n)), dim3(256), 0, c->stream, c->pv(), (const float*)c->density, n, c->soff(), c->K, dt_prev,
-                           c->nbv(), c->accel, c->d_scal, vslot);
+        if (c->VK.visc_model == SPHX_VISCOSITY_PHYSICAL)
+            hipLaunchKernelGGL(k_nonpressure<SPHX_VISCOSITY_PHYSICAL>, dim3(nblocks(n)), dim3(256), 0, c->stream, c->pv(), (const float*)c->density, n,
+                               c->soff(), c->K, dt_prev, c->nbv(), c->accel, c->d_scal, vslot, ViscArg<SPHX_VISCOSITY_PHYSICAL>{c->VK});
+        else
+            hipLaunchKernelGGL(k_nonpressure<SPHX_VISCOSITY_XSPH>, dim3(nblocks(n)), dim3(256), 0, c->stream, c->pv(), (const float*)c->density, n,
+                               c->soff(), c->K, dt_prev, c->nbv(), c->accel, c->d_scal, vslot, ViscArg<SPHX_VISCOSITY_XSPH>{});
     });
 }
 
@@ -1312,6 +1316,8 @@ int sphx_default_params(float smoothing_factor, float particle_density, float fl
     p->grid_min[0] = -100.0f;                                          // neighborhood_search.rs:478
     p->grid_min[1] = -100.0f;
     p->xsph_epsilon = 0.05f;                                           // xsph.rs:14
+    p->viscosity_model = SPHX_VISCOSITY_XSPH;                          // main.rs:99-100: DFSPHSolver::new(xsphviscosity, ..)
+    p->fluid_viscosity = 1.0016f / 1000.0f;                            // physical.rs:14 (water at 20 degrees)
     p->max_avg_density_error = 0.01f / 100.0f;                         // dfsph.rs:49
     p->max_density_iterations = 200;                                   // dfsph.rs:50
     p->max_divergence_error = 0.1f / 100.0f;                           // dfsph.rs:53
@@ -1327,6 +1333,14 @@ int sphx_create(const sphx_params* params, sphx_ctx** out) {
     *out = nullptr;
     if (!(params->smoothing_length > 0) || !(params->particle_mass > 0) || !(params->fluid_density > 0)) {
         g_create_error = "smoothing_length, particle_mass and fluid_density must be positive";
+        return SPHX_ERR_INVALID_ARGUMENT;
+    }
+    if (params->viscosity_model != SPHX_VISCOSITY_XSPH && params->viscosity_model != SPHX_VISCOSITY_PHYSICAL) {
+        g_create_error = "viscosity_model must be SPHX_VISCOSITY_XSPH (0) or SPHX_VISCOSITY_PHYSICAL (1)";
+        return SPHX_ERR_INVALID_ARGUMENT;
+    }
+    if (!std::isfinite(params->fluid_viscosity)) {  // (negative values are accepted, as PhysicalViscosityModel does)
+        g_create_error = "fluid_viscosity must be finite";
         return SPHX_ERR_INVALID_ARGUMENT;
     }
     int ndev = 0;
@@ -1371,6 +1385,9 @@ int sphx_create(const sphx_params* params, sphx_ctx** out) {
     K.mass = params->particle_mass;
     K.rho0 = params->fluid_density;
     K.xsph_eps = params->xsph_epsilon;
+    c->VK.visc_model = params->viscosity_model;
+    c->VK.mu = params->fluid_viscosity;
+    c->VK.vis_nlap = 360.0f / (29.0f * PI_F * rs_powi(h, 5));  // Viscosity::new, viscosity.rs:24: (29 pi) h^5 in f32, powi as compiler-rt
     K.tile = TileRect{0u, 65536u, 0u, 65536u};
     K.remote_cap = params->list_span_limit == SPHX_LISTS_32BIT ? 0u : params->list_span_limit == 0 ? REMOTE_CAP : std::min(params->list_span_limit, REMOTE_CAP);
     {
@@ -1827,8 +1844,12 @@ int sphx_wcsph_step_begin(sphx_ctx* c, float dt, float* out_vmax) {
     const uint32_t seq = ++c->seq;
     const VmaxArgs va{1u, take_vmax_slot(c), c->mbox_dev, seq};
     launch(c, "wcsph_accelerations_vmax", (16.0 + 4 + 8 + 4 + list_bytes(c)) * n, [&] {
-        hipLaunchKernelGGL(k_wcsph_accel, g, b, 0, st, c->pv(), (const float*)c->density, n, c->soff(), c->K, dt, c->nbv(), c->accel,
-                           c->d_scal, va.vslot);
+        if (c->VK.visc_model == SPHX_VISCOSITY_PHYSICAL)
+            hipLaunchKernelGGL(k_wcsph_accel<SPHX_VISCOSITY_PHYSICAL>, g, b, 0, st, c->pv(), (const float*)c->density, n, c->soff(), c->K, dt, c->nbv(),
+                               c->accel, c->d_scal, va.vslot, ViscArg<SPHX_VISCOSITY_PHYSICAL>{c->VK});
+        else
+            hipLaunchKernelGGL(k_wcsph_accel<SPHX_VISCOSITY_XSPH>, g, b, 0, st, c->pv(), (const float*)c->density, n, c->soff(), c->K, dt, c->nbv(),
+                               c->accel, c->d_scal, va.vslot, ViscArg<SPHX_VISCOSITY_XSPH>{});
     });
     hipLaunchKernelGGL(k_publish_vmax, dim3(1), dim3(64), 0, st, c->d_scal, va);
     if ((rc = wait_mailbox(c, seq))) return rc;
@@ -2040,6 +2061,14 @@ int sphx_grid_info(const sphx_ctx* c, int which, uint32_t* out4) {
     out4[1] = g.len();
     out4[2] = g.nbx;
     out4[3] = g.nby;
+    return SPHX_OK;
+}
+
+int sphx_get_viscosity(const sphx_ctx* c, uint32_t* model, float* fluid_viscosity, float* normalizer_laplacian) {
+    if (!c) return SPHX_ERR_INVALID_ARGUMENT;
+    if (model) *model = c->VK.visc_model;
+    if (fluid_viscosity) *fluid_viscosity = c->VK.mu;
+    if (normalizer_laplacian) *normalizer_laplacian = c->VK.vis_nlap;
     return SPHX_OK;
 }
 

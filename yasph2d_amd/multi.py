@@ -213,6 +213,10 @@ class MultiSolver:
         for k in range(self.info()["local_tiles"]):
             self.tile_context(k).set_tiling_invariant(on)
 
+    def viscosity(self, k=0):
+        """The viscosity model local tile k runs (SphxContext.viscosity): every tile context is created from the same params."""
+        return self.tile_context(k).viscosity()
+
     def tile_context(self, k=0):
         """Borrowed SphxContext view of a local tile (inspection, profiling)."""
         from . import SphxContext
