@@ -18,7 +18,7 @@
  * What is the contract and what is scaffolding (the header has grown beyond the boundary SURVEY.md 8(b) asks for):
  *   STABLE — the drop-in boundary a Rust shim binds:
  *       lifecycle (sphx_default_params, sphx_create, sphx_destroy, sphx_last_error, sphx_abi_version), the particle-array
- *       surface (sphx_set_boundary, sphx_upload, sphx_download*, sphx_num_*, sphx_view_*), the Solver trait (sphx_clear_cached,
+ *       surface (sphx_set_boundary, sphx_upload, sphx_download*, sphx_num_*, sphx_view_*, sphx_sample_*), the Solver trait (sphx_clear_cached,
  *       sphx_step_begin[_law], sphx_step_finish, sphx_wcsph_step_*), the same trait over a device list (sphx_multi_create[_rank],
  *       sphx_multi_destroy, sphx_multi_set_boundary, sphx_multi_upload, sphx_multi_clear_cached, sphx_multi_step_begin/finish,
  *       sphx_multi_simulation_step[s], sphx_multi_download, sphx_multi_num_owned, sphx_multi_last_error, sphx_comm_ops) and
@@ -51,7 +51,8 @@ extern "C" {
                             *    sphx_build_stats, sphx_sub_run_ahead, sphx_tile_carry_warmstart, sphx_tile_defer_advect, sphx_sub_predict_iteration, sphx_tile_band_packs,
                             *    sphx_multi_info_t.band_packs (was reserved)
                             * 5 (additive): sphx_params.viscosity_model / .fluid_viscosity (were reserved[0..1]; zero = XSPH, the behaviour
-                            *    before), SPHX_VISCOSITY_*, sphx_get_viscosity */
+                            *    before), SPHX_VISCOSITY_*, sphx_get_viscosity
+                            * 5 (additive): sphx_sample_points, sphx_sample_grid, sphx_sample_out, SPHX_SAMPLE_DEVICE_POINTERS */
 
 /* ---- status codes ---- */
 enum {
@@ -167,6 +168,58 @@ int sphx_view_request(sphx_ctx* ctx, uint32_t stride, uint32_t* out_count);
 int sphx_view_fetch(sphx_ctx* ctx, int wait, const float** out_xys, uint32_t* out_count);
 uint32_t sphx_num_particles(const sphx_ctx* ctx);  /* Particles::num_dynamic_particles  fluidparticleworld.rs:37 */
 uint32_t sphx_num_boundary(const sphx_ctx* ctx);   /* Particles::num_boundary_particles fluidparticleworld.rs:41 */
+
+/* ---- field sampling: density, fluid fraction and velocity at arbitrary points (an SPH "measure tool") -------------------------------
+ * Kernel interpolation over the particles at query points, from the cell grids the latest neighbour build left on the device: one short
+ * kernel, nothing added to the step.  The contract, for a query point q (fp32 x, y) and the kernel W of kind kernel_kind
+ * (SPHX_KERNEL_*: the kinds sphx_update_densities takes; Wendland is the DFSPH kernel):
+ *   Candidates: with (cx, cy) the cell of q, computed as for a particle (sat_u16((q - grid_min) * cell_inv), neighborhood_search.rs:52-58),
+ *     the fluid particles of the 3x3 cells around (cx, cy), then the boundary particles of those cells; each in ascending device
+ *     (cell-sorted) index, i.e. the order of sphx_download / sphx_download_boundary.  A particle the grid holds no cell for (a stray,
+ *     SPHX_FLAG_STRAY_PARTICLES) contributes nothing, as in the neighbour build.
+ *   Acceptance: dx = x_j.x - q.x, dy = x_j.y - q.y, d2 = dx*dx + dy*dy (unfused); accepted iff d2 <= radius_sq (radius_sq = h*h in fp32).
+ *     Unlike the neighbour build there is no d2 > 1e-10 exclusion: a query point is not a particle, nothing at distance 0 is "self".
+ *     w = W(d2, r) with r = sqrtf(d2) (correctly rounded): Wendland w_norm*(1-q)^2*(1-q)^2*(q+0.25) with q = min(w_hinv*r, 1),
+ *     Poly6 p6_norm*d^3 with d = max(h*h - d2, 0), Spiky sp_norm*d^3 with d = max(h - r, 0), as sphx_update_densities evaluates them.
+ *   Outputs (any subset; every sum starts at 0.0f and is accumulated in candidate order, one fp32 rounding per operation):
+ *     density  = rho = rho + w*m over the fluid and then the boundary candidates, unclamped (the sum FluidParticleWorld::update_densities
+ *                forms before its max(fluid_density), fluidparticleworld.rs:197-231);
+ *     fraction = sum over fluid candidates of a_j, a_j = (m / rho_j) * w, rho_j = the density sphx_download returns for particle j:
+ *                ~1 in the bulk, ~0.5 at the free surface, 0 away from the fluid;
+ *     velocity = (sum a_j*v_j.x / fraction, sum a_j*v_j.y / fraction) (Shepard-normalised, v_j = sphx_download's velocity; the products
+ *                a_j*v_j are summed, then divided once), (0, 0) where fraction == 0;
+ *     count    = accepted fluid candidates (no cap: the build's 64-neighbour cap does not apply).
+ *   A point far outside the domain or a non-finite one gets zeros and count 0 (a NaN coordinate saturates to cell 0 and fails every
+ *   distance test); it never faults.
+ * When a query is allowed: the cell grids and density[] must belong to the current positions — after sphx_step_finish, after
+ * sphx_wcsph_step_finish (not after a step over zero fluid particles: it builds no grid), and after sphx_update_neighborhood followed by
+ * sphx_update_densities.  After sphx_upload or sphx_set_boundary,
+ * between a step_begin and its step_finish (either solver), after a failed step, or after a neighbour update without a density update the
+ * call returns SPHX_ERR_NOT_READY and sphx_last_error says which step is missing.  A tile context (sphx_tile_*, sphx_multi_tile_ctx) is
+ * refused with SPHX_ERR_INVALID_ARGUMENT: its arrays hold ghosts and miss the particles other tiles own.
+ * No side effects: a query only reads (it does not touch the run-ahead pass, densities, lists, ids, SPHX_FLAG_* or sphx_last_flags); a run
+ * with queries between its steps is bit-identical to the same run without them.
+ * Argument errors (SPHX_ERR_INVALID_ARGUMENT, the message names the argument): out NULL or requesting no output, xy NULL with m > 0,
+ * an unknown kernel_kind or flag bit; for the lattice dx / dy not finite or <= 0, x0 / y0 not finite, nx * ny >= 2^31.  m == 0 and
+ * nx * ny == 0 are successful no-ops (once the arguments pass). */
+enum { SPHX_SAMPLE_DEVICE_POINTERS = 1u }; /* xy and every output are device pointers on the context's device: the call is enqueued on the
+                                              context's stream and returns without waiting (order it with sphx_synchronize / sphx_set_stream).
+                                              Without it: host pointers; the call returns when the outputs are written (the library copies
+                                              through a device scratch it grows on demand and frees in sphx_destroy). */
+typedef struct sphx_sample_out {
+    float* density;    /* [m] or NULL */
+    float* fraction;   /* [m] or NULL */
+    float* velocity;   /* [2m] interleaved xy, or NULL */
+    uint32_t* count;   /* [m] or NULL */
+} sphx_sample_out;
+/* m points, xy interleaved.  They are processed in the caller's order, one lane each: pass large point sets SPATIALLY COHERENT (e.g. sorted
+ * by cell) — neighbouring lanes then gather the same cells; random order costs several times more ("Sampling the fields"). */
+int sphx_sample_points(sphx_ctx* ctx, const float* xy, uint32_t m, int kernel_kind, uint32_t flags, const sphx_sample_out* out);
+/* The lattice point (ix, iy) is (x0 + (float)ix * dx, y0 + (float)iy * dy) in fp32 (unfused), output index iy * nx + ix (row 0 at y0,
+ * the bottom).  Both calls share one device function for the walk of a point: sampling the lattice and sampling the same fp32 points
+ * through sphx_sample_points give bit-identical outputs. */
+int sphx_sample_grid(sphx_ctx* ctx, float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, int kernel_kind,
+                     uint32_t flags, const sphx_sample_out* out);
 
 /* ---- Solver trait (solver/mod.rs:12-18) ---------------------------------------------------------------------- */
 /* Solver::clear_cached_data (dfsph.rs:406-412) */

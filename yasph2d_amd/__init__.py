@@ -15,7 +15,7 @@ from ._lib import (FLAG_DENSITY_ITER_CAP, FLAG_DIVERGENCE_ITER_CAP, FLAG_DENSE_C
                    KERNEL_SPIKY, KERNEL_WENDLAND_C2, VISCOSITY_PHYSICAL, VISCOSITY_XSPH, SphxError, SphxKernelTime, SphxParams, SphxStepStats)
 
 __all__ = ["SphxContext", "FluidParticleWorld", "TimeManager", "DFSPHSolver", "DFSPHMultiSolver", "default_params", "duration_from_secs_f32",
-           "duration_as_secs_f32", "SphxError", "WCSPHSolver", "VISCOSITY_XSPH", "VISCOSITY_PHYSICAL"]
+           "duration_as_secs_f32", "SphxError", "WCSPHSolver", "VISCOSITY_XSPH", "VISCOSITY_PHYSICAL", "SAMPLE_FIELDS", "gauge_elevation"]
 
 
 def _p(a):
@@ -54,6 +54,69 @@ def duration_from_secs_f32(secs):
 
 def duration_as_secs_f32(ns):
     return _lib.lib().sphx_duration_as_secs_f32(ns)
+
+
+SAMPLE_FIELDS = ("density", "fraction", "velocity", "count")
+
+
+def _sample_fields(fields):
+    fields = (fields,) if isinstance(fields, str) else tuple(fields)
+    bad = [f for f in fields if f not in SAMPLE_FIELDS]
+    if bad or not fields:
+        raise ValueError("fields must be a non-empty subset of %s, not %r" % (SAMPLE_FIELDS, fields))
+    return fields
+
+
+def _is_torch(a):
+    return type(a).__module__.split(".")[0] == "torch"
+
+
+def _numpy_outputs(fields, shape):
+    return {f: np.zeros(shape + ((2,) if f == "velocity" else ()), np.uint32 if f == "count" else np.float32) for f in fields}
+
+
+def _torch_outputs(fields, shape, device):
+    import torch
+
+    return {f: torch.empty(shape + ((2,) if f == "velocity" else ()), dtype=torch.int32 if f == "count" else torch.float32, device=device)
+            for f in fields}
+
+
+def _out_struct(outs, ptr):
+    o = _lib.SphxSampleOut()
+    for f, a in outs.items():
+        setattr(o, f, ptr(a) or 1)  # (an empty tensor has no storage: a non-NULL dummy still names the field; nothing is written)
+    return o
+
+
+def gauge_elevation(ctx, xs, y_lo, y_hi, dy, kernel=KERNEL_WENDLAND_C2):
+    """Free-surface elevation at each gauge x (the water height of a dam-break gauge).
+
+    For each x, `fraction` is sampled on a one-column lattice from y_lo in steps of dy: ny = floor((y_hi - y_lo) / dy) + 1 samples
+    (float64 on the host), at the fp32 points y_k = fl(y_lo + fl(k * dy)).  k = the highest sample with fraction >= 0.5; the elevation is
+    y_k if k is the top sample, else the float64 linear interpolation to 0.5 between samples k and k + 1; NaN where the column holds no
+    such sample.  Returns a float64 array, one value per gauge."""
+    ny = int(np.floor((float(y_hi) - float(y_lo)) / float(dy))) + 1
+    if ny <= 0:
+        raise ValueError("need y_hi >= y_lo and dy > 0")
+    y = np.float32(y_lo) + np.arange(ny, dtype=np.float32) * np.float32(dy)
+    out = []
+    for x in np.atleast_1d(np.asarray(xs, np.float64)):
+        f = ctx.sample_grid((np.float32(x), np.float32(y_lo)), (np.float32(1.0), np.float32(dy)), (ny, 1), kernel=kernel,
+                            fields=("fraction",))["fraction"][:, 0]
+        out.append(_elevation(y, f))
+    return np.array(out, np.float64)
+
+
+def _elevation(y, f):
+    wet = np.nonzero(f >= np.float32(0.5))[0]
+    if len(wet) == 0:
+        return float("nan")
+    k = int(wet[-1])
+    if k == len(f) - 1:
+        return float(y[k])
+    fk, fk1 = float(f[k]), float(f[k + 1])
+    return float(y[k]) + (fk - 0.5) / (fk - fk1) * (float(y[k + 1]) - float(y[k]))
 
 
 class SphxContext:
@@ -222,6 +285,54 @@ class SphxContext:
         m, mu, nlap = C.c_uint32(), C.c_float(), C.c_float()
         self._chk(self.L.sphx_get_viscosity(self.h, C.byref(m), C.byref(mu), C.byref(nlap)))
         return {VISCOSITY_XSPH: "xsph", VISCOSITY_PHYSICAL: "physical"}[m.value], np.float32(mu.value), np.float32(nlap.value)
+
+    def sample(self, points, kernel=KERNEL_WENDLAND_C2, fields=SAMPLE_FIELDS):
+        """sphx_sample_points: the fields at m query points (the contract is in include/sphx.h).
+
+        points: float32 [m, 2], either a numpy array (host path) or a torch tensor on the context's device (device path).
+        fields: any of "density", "fraction", "velocity", "count".  Returns {field: array}: shape [m] ([m, 2] for velocity; count
+        uint32 — int32 for torch, which has no uint32 arithmetic), numpy for numpy points, torch tensors for torch points.
+        The device path synchronises torch's current stream before the call (the points and the freshly allocated outputs are then
+        complete), enqueues the query on the context's own stream and waits for that stream before it returns: the tensors it
+        returns hold finished results and no stream of the caller has to be ordered against the library's.  Pass large point sets
+        spatially coherent (e.g. sorted by cell): the library processes them in the given order."""
+        flags = _sample_fields(fields)
+        if _is_torch(points):
+            import torch
+
+            if points.device.type != "cuda" or points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 2:
+                raise ValueError("points must be a float32 [m, 2] tensor on the context's device")
+            if self.params is not None and points.device.index not in (None, self.params.device):
+                raise ValueError("points are on %s, the context on device %d" % (points.device, self.params.device))
+            pts = points.contiguous()
+            m = pts.shape[0]
+            outs = _torch_outputs(flags, (m,), pts.device)
+            torch.cuda.current_stream(pts.device).synchronize()
+            self._chk(self.L.sphx_sample_points(self.h, C.c_void_p(pts.data_ptr()), m, kernel, _lib.SAMPLE_DEVICE_POINTERS,
+                                                C.byref(_out_struct(outs, lambda t: t.data_ptr()))))
+            self.synchronize()
+            return outs
+        pts = np.ascontiguousarray(points, np.float32)
+        if pts.ndim != 2 or pts.shape[1] != 2:
+            raise ValueError("points must be a float32 [m, 2] array, not shape %s" % (pts.shape,))
+        m = len(pts)
+        outs = _numpy_outputs(flags, (m,))
+        self._chk(self.L.sphx_sample_points(self.h, _p(pts), m, kernel, 0, C.byref(_out_struct(outs, lambda a: a.ctypes.data))))
+        return outs
+
+    def sample_grid(self, origin, spacing, shape, kernel=KERNEL_WENDLAND_C2, fields=SAMPLE_FIELDS):
+        """sphx_sample_grid: the fields on the lattice origin + (ix * dx, iy * dy) (fp32, unfused), shape = (ny, nx); row 0 lies at
+        origin[1] (the bottom).  spacing: (dx, dy) or one number for both.  Returns {field: numpy array} of shape (ny, nx)
+        ((ny, nx, 2) for velocity), bit-identical to sample() at the same fp32 points."""
+        flags = _sample_fields(fields)
+        dx, dy = (spacing, spacing) if np.ndim(spacing) == 0 else spacing
+        ny, nx = (int(v) for v in shape)
+        if nx < 0 or ny < 0:
+            raise ValueError("shape must be (ny, nx) with non-negative sizes")
+        outs = _numpy_outputs(flags, (ny, nx))
+        self._chk(self.L.sphx_sample_grid(self.h, origin[0], origin[1], dx, dy, nx, ny, kernel, 0,
+                                          C.byref(_out_struct(outs, lambda a: a.ctypes.data))))
+        return outs
 
     def profile_enable(self, on=True):
         self._chk(self.L.sphx_profile_enable(self.h, int(on)))

@@ -82,6 +82,13 @@ def build(force=False):
     subprocess.check_call(args, stdout=subprocess.DEVNULL)
 
 
+SAMPLE_DEVICE_POINTERS = 1  # sphx_sample_points / sphx_sample_grid flags
+
+
+class SphxSampleOut(C.Structure):
+    _fields_ = [("density", C.c_void_p), ("fraction", C.c_void_p), ("velocity", C.c_void_p), ("count", C.c_void_p)]
+
+
 class SphxMultiOptions(C.Structure):
     _fields_ = [("halo_cells", C.c_uint32), ("fixed_halo", C.c_uint32), ("rebalance_every", C.c_uint32), ("layout", C.c_uint32),
                 ("cap_records", C.c_uint32), ("overlap_exchange", C.c_uint32), ("reserved", C.c_uint32 * 2)]
@@ -122,6 +129,8 @@ SIGNATURES = {
     "sphx_download_boundary": (_i, [_vp, _vp, _vp]),
     "sphx_num_particles": (_u32, [_vp]),
     "sphx_num_boundary": (_u32, [_vp]),
+    "sphx_sample_points": (_i, [_vp, _vp, _u32, _i, _u32, C.POINTER(SphxSampleOut)]),
+    "sphx_sample_grid": (_i, [_vp, _f, _f, _f, _f, _u32, _u32, _i, _u32, C.POINTER(SphxSampleOut)]),
     "sphx_clear_cached": (_i, [_vp]),
     "sphx_step_begin": (_i, [_vp, _f, C.POINTER(_f)]),
     "sphx_step_begin_law": (_i, [_vp, _f, _vp, _vp]),

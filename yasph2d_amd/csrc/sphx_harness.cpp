@@ -2,9 +2,14 @@
 // draw (main.rs:85-129 set-up, :177-196 scene, :279 `sph_solver.simulation_step(&mut fluid_world, &mut time_manager)`).
 //
 //   sphx_harness [--solver dfsph|wcsph] [--viscosity xsph|physical[:mu]] [--scale S | --particles N] [--steps K] [--warmup W] [--no-law] [--sync]
+//                [--gauges x1,x2,... [--gauge-range lo:hi:dy]]
 //
 // --viscosity: the solver's ViscosityModel (main.rs:93-100): XSPH (default) or PhysicalViscosityModel with fluid_viscosity mu
 // (default 1.0016e-3, physical.rs:14; main.rs:96 sets 0.01).
+//
+// --gauges: after the run, the free-surface elevation at each x (sphx_sample_grid of the fluid fraction on a one-column lattice from lo
+// in steps of dy up to hi, the rule of yasph2d_amd.gauge_elevation): "gauge_elevations": [...] in the JSON line, null where a column
+// holds no fluid.  Default range lo = 0, hi = 2.5 * scale (the top of the scene), dy = particle_radius / 2.
 //
 // Prints one JSON line: particle-steps/s over the K timed steps, the timer's final step, iteration statistics and an FNV-1a
 // checksum of the final (downloaded) positions/velocities, which tests compare with the Python-driven run of the same scene.
@@ -16,6 +21,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "sphx_host.hpp"
 
@@ -28,12 +34,45 @@ static uint64_t fnv1a(const void* data, size_t n, uint64_t h = 14695981039346656
     return h;
 }
 
+// the whole string as a finite number (a typo must not become 0)
+static bool parse_double(const std::string& s, double* out) {
+    char* end = nullptr;
+    *out = std::strtod(s.c_str(), &end);
+    return !s.empty() && end == s.c_str() + s.size() && std::isfinite(*out);
+}
+
+// Free-surface elevation of one gauge (yasph2d_amd.gauge_elevation): the fluid fraction on the lattice column y_k = fl(lo + fl(k * dy)),
+// k < ny = floor((hi - lo) / dy) + 1; the highest sample with fraction >= 0.5, interpolated linearly (float64) to 0.5 towards the
+// sample above it; NaN without such a sample.  Returns false when the query fails.
+static bool gauge_elevation(sph::HipDfsphSolver& solver, double x, double lo, double hi, double dy, double* out) {
+    const long ny = (long)std::floor((hi - lo) / dy) + 1;
+    if (ny <= 0 || ny >= (1l << 31)) return false;
+    std::vector<float> f((size_t)ny);
+    sphx_sample_out o{};
+    o.fraction = f.data();
+    if (solver.sample_grid((float)x, (float)lo, 1.0f, (float)dy, 1u, (uint32_t)ny, SPHX_KERNEL_WENDLAND_C2, 0u, &o) != SPHX_OK) return false;
+    auto y_of = [&](long k) { return (double)((float)lo + (float)k * (float)dy); };
+    long k = ny - 1;
+    while (k >= 0 && !(f[(size_t)k] >= 0.5f)) --k;
+    if (k < 0)
+        *out = NAN;
+    else if (k == ny - 1)
+        *out = y_of(k);
+    else {
+        const double fk = f[(size_t)k], fk1 = f[(size_t)k + 1];
+        *out = y_of(k) + (fk - 0.5) / (fk - fk1) * (y_of(k + 1) - y_of(k));
+    }
+    return true;
+}
+
 int main(int argc, char** argv) {
     std::string solver_kind = "dfsph";
     float scale = 1.0f;
     long steps = 100, warmup = 5;
     bool law = true, sync = false;
     std::string viscosity = "xsph";
+    std::string gauges_arg, gauge_range_arg;
+    bool want_gauges = false, want_range = false;
     for (int a = 1; a < argc; ++a) {
         const std::string s = argv[a];
         auto next = [&]() -> const char* { return a + 1 < argc ? argv[++a] : "0"; };
@@ -45,6 +84,8 @@ int main(int argc, char** argv) {
         else if (s == "--warmup") warmup = std::atol(next());
         else if (s == "--no-law") law = false;
         else if (s == "--sync") sync = true;
+        else if (s == "--gauges") gauges_arg = next(), want_gauges = true;
+        else if (s == "--gauge-range") gauge_range_arg = next(), want_range = true;
         else {
             std::fprintf(stderr, "unknown argument %s\n", s.c_str());
             return 2;
@@ -53,6 +94,33 @@ int main(int argc, char** argv) {
     const bool wcsph = solver_kind == "wcsph";
     sph::FluidParticleWorld world(2.0f, 10000.0f, 100.0f);  // main.rs:85-89
     sph::reset_fluid(world, scale);                          // main.rs:177-196
+    std::vector<double> gauge_x;
+    double gauge_lo = 0.0, gauge_hi = 2.5 * (double)scale, gauge_dy = (double)world.properties.particle_radius() / 2.0;
+    if (want_gauges) {
+        bool ok = !gauges_arg.empty();
+        for (size_t p = 0; ok && p <= gauges_arg.size();) {
+            const size_t q = std::min(gauges_arg.find(',', p), gauges_arg.size());
+            double v;
+            ok = parse_double(gauges_arg.substr(p, q - p), &v);
+            gauge_x.push_back(v);
+            p = q + 1;
+        }
+        if (!ok) {
+            std::fprintf(stderr, "invalid --gauges %s (x1,x2,... finite numbers)\n", gauges_arg.c_str());
+            return 2;
+        }
+    }
+    if (want_range) {
+        const size_t c1 = gauge_range_arg.find(':'), c2 = c1 == std::string::npos ? c1 : gauge_range_arg.find(':', c1 + 1);
+        bool ok = want_gauges && c2 != std::string::npos && gauge_range_arg.find(':', c2 + 1) == std::string::npos &&
+                  parse_double(gauge_range_arg.substr(0, c1), &gauge_lo) && parse_double(gauge_range_arg.substr(c1 + 1, c2 - c1 - 1), &gauge_hi) &&
+                  parse_double(gauge_range_arg.substr(c2 + 1), &gauge_dy) && gauge_dy > 0.0 && gauge_hi >= gauge_lo &&
+                  (gauge_hi - gauge_lo) / gauge_dy < 2147483647.0;
+        if (!ok) {
+            std::fprintf(stderr, "invalid --gauge-range %s (lo:hi:dy, finite, lo <= hi, dy > 0, with --gauges)\n", gauge_range_arg.c_str());
+            return 2;
+        }
+    }
     sphx_params params = sph::HipDfsphSolver::params_of(world, nullptr);
     {
         const size_t colon = viscosity.find(':');
@@ -111,11 +179,29 @@ int main(int argc, char** argv) {
         by_id[4 * id + 2] = world.particles.velocities[i].x;
         by_id[4 * id + 3] = world.particles.velocities[i].y;
     }
+    std::string gauge_json;  // (empty without --gauges: the line stays what it was)
+    if (want_gauges) {
+        gauge_json = ", \"gauge_elevations\": [";
+        for (size_t g = 0; g < gauge_x.size(); ++g) {
+            double e;
+            if (!gauge_elevation(*solver, gauge_x[g], gauge_lo, gauge_hi, gauge_dy, &e)) {
+                std::fprintf(stderr, "gauge at x = %g: %s\n", gauge_x[g], sphx_last_error(solver->ctx()));
+                return 1;
+            }
+            char buf[64];
+            if (std::isnan(e))
+                std::snprintf(buf, sizeof(buf), "null");
+            else
+                std::snprintf(buf, sizeof(buf), "%.17g", e);
+            gauge_json += (g ? ", " : "") + std::string(buf);
+        }
+        gauge_json += "]";
+    }
     std::printf("{\"solver\": \"%s\", \"viscosity\": \"%s\", \"fluid_viscosity\": %.9g, \"particles\": %zu, \"boundary\": %zu, \"steps\": %ld, \"particle_steps_per_s\": %.6e, \"ms_per_step\": %.6f, "
                 "\"timer_step_ns\": %llu, \"simulated_ns\": %llu, \"mean_density_iterations\": %.4f, \"mean_divergence_iterations\": %.4f, "
-                "\"state_fnv1a\": \"%016llx\"}\n",
+                "\"state_fnv1a\": \"%016llx\"%s}\n",
                 solver_kind.c_str(), params.viscosity_model == SPHX_VISCOSITY_PHYSICAL ? "physical" : "xsph", (double)params.fluid_viscosity, n, world.particles.boundary_particles.size(), steps, (double)n * (double)steps / el, el / (double)steps * 1e3,
                 (unsigned long long)tm.simulation_step().ns, (unsigned long long)tm.total_simulated_time.ns, steps ? (double)id_sum / steps : 0.0,
-                steps ? (double)iv_sum / steps : 0.0, (unsigned long long)fnv1a(by_id.data(), by_id.size() * 4));
+                steps ? (double)iv_sum / steps : 0.0, (unsigned long long)fnv1a(by_id.data(), by_id.size() * 4), gauge_json.c_str());
     return 0;
 }

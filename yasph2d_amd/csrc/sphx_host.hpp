@@ -123,6 +123,14 @@ class HipDfsphSolver : public Solver {
     std::string last_error;
     sphx_step_stats last_stats{};
     sphx_ctx* ctx() { return ctx_; }
+    // field sampling (sphx_sample_points / sphx_sample_grid; the contract and the state rules are in sphx.h): density, fluid fraction,
+    // velocity and neighbour count at query points of the solver's current state, e.g. after simulation_step
+    int sample_points(const float* xy, uint32_t m, int kernel_kind, uint32_t flags, const sphx_sample_out* out) {
+        return sphx_sample_points(ctx_, xy, m, kernel_kind, flags, out);
+    }
+    int sample_grid(float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, int kernel_kind, uint32_t flags, const sphx_sample_out* out) {
+        return sphx_sample_grid(ctx_, x0, y0, dx, dy, nx, ny, kernel_kind, flags, out);
+    }
     // the params a null params_or_null stands for: sphx_default_params + the world's properties (a caller that changes one field,
     // e.g. the viscosity model, starts from these)
     static sphx_params params_of(const FluidParticleWorld& world, const sphx_params* params_or_null);

@@ -305,6 +305,12 @@ struct sphx_ctx {
     uint32_t cached_n = 0;     // alpha_values.len() of the reference (dfsph.rs:419)
     bool uploaded = false, boundary_changed = true, tails_dirty = true, in_step = false;
     uint32_t fast_walk_ok = 0;  // this smoothing length allows the FAST walks (sqrt_dist); K.q_noclamp = fast_walk_ok while the lists are fresh
+    // field sampling (sphx_sample_*): 2 = the cell grids and density[] belong to the current positions (a build plus densities), 1 = a
+    // build without densities since, 0 = positions / boundary replaced or a step open; sample_missing says what a query is waiting for
+    uint32_t sample_ready = 0;
+    const char* sample_missing = "no neighbour build yet: run a step, or sphx_update_neighborhood + sphx_update_densities";
+    float* sample_buf = nullptr;  // device scratch of the host-pointer queries (points + outputs), grown on demand
+    size_t sample_cap = 0;        // ... in 4-byte words
     uint32_t num_density_iters = 1, num_divergence_iters = 0;  // dfsph.rs:51,55
     float step_dt_prev = 0, step_vmax = 0;
     uint32_t step_flags = 0;

@@ -3218,3 +3218,5 @@ __global__ __launch_bounds__(64) void k_publish(DevScalars* scal, Mailbox* mb, u
 // launch layer
 // ======================================================================================================================
 #include "sphx_launch.inc"
+// field sampling at points and on lattices (kernels + C ABI)
+#include "sphx_sample.inc"

@@ -693,9 +693,28 @@ int ensure_index_scratch(sphx_ctx* c) {
     return SPHX_OK;
 }
 
+// Field sampling (sphx_sample_*, sphx_sample.inc) reads the cell grids and density[]: a query is refused (SPHX_ERR_NOT_READY, with
+// `missing` as the message) from here until a neighbour build AND the densities of its positions have completed (sphx_ctx::sample_ready).
+static inline void sample_went_stale(sphx_ctx* c, const char* missing) {
+    c->sample_ready = 0u;
+    c->sample_missing = missing;
+}
+// A finished step whose neighbour build ran (sample_ready == 1: the build completed, its densities are the step's) may be sampled.  A
+// step over zero fluid particles runs no build: the static grid of a new boundary may not exist yet.
+static inline void sample_after_step(sphx_ctx* c) {
+    if (c->sample_ready == 1u)
+        c->sample_ready = 2u;
+    else
+        sample_went_stale(c, "no neighbour build has run since the particles or the boundary changed (a step over zero fluid particles runs "
+                             "none): call sphx_update_neighborhood + sphx_update_densities");
+}
 // Positions are about to change (or have changed) without the neighbour lists being rebuilt first: the walks go back to the forms
 // that are right for any distance (sqrt_dist in sphx_kernels.hip) until the next build.
-static inline void lists_went_stale(sphx_ctx* c) { c->K.q_noclamp = 0u; }
+static inline void lists_went_stale(sphx_ctx* c) {
+    c->K.q_noclamp = 0u;
+    // (a caller that has already dropped the sampling state keeps its own, more specific message)
+    if (c->sample_ready) sample_went_stale(c, "the positions changed since the last neighbour build: run a step, or sphx_update_neighborhood + sphx_update_densities");
+}
 
 // (Re)allocate the [N|B] arrays for capN fluid + capB boundary slots, keeping the fluid prefix of posA/vel — and, while the tail does
 // not move (capN unchanged: sphx_set_boundary with a larger boundary), the boundary tail the current lists still point into: the
@@ -819,6 +838,7 @@ int recover_directory(sphx_ctx* c, float advect_dt, uint32_t advect_below = 0xFF
 int update_neighborhood(sphx_ctx* c, bool extra_alpha, float advect_dt, bool fuse, bool fuse_div = false, bool fuse_warm = false) {
     int rc;
     drop_class_count(c);
+    sample_went_stale(c, "the last neighbour build did not complete: upload the state again");
     if (c->boundary_changed) {
         if ((rc = build_static(c))) return rc;
     }
@@ -949,6 +969,8 @@ int update_neighborhood(sphx_ctx* c, bool extra_alpha, float advect_dt, bool fus
         if ((rc = wait_mailbox(c, tile_n))) return rc;  // tile_n carries the sequence number of the publish inside build_grid
         c->N = std::min(c->mbox->sort_total, c->N);
     }
+    c->sample_ready = 1u;  // (the callers that also complete the densities of this build raise it to 2)
+    c->sample_missing = "the densities of the last neighbour build are missing: call sphx_update_densities";
     return SPHX_OK;
 }
 
@@ -1472,7 +1494,7 @@ void sphx_destroy(sphx_ctx* c) {
     dev_free(&c->density); dev_free(&c->alpha); dev_free(&c->alpha2); dev_free(&c->kappa); dev_free(&c->stiff); dev_free(&c->kappa2); dev_free(&c->stiff2);
     dev_free(&c->pid); dev_free(&c->pid2); dev_free(&c->key); dev_free(&c->slot); dev_free(&c->order);
     dev_free(&c->bpos); dev_free(&c->bpos2); dev_free(&c->bid); dev_free(&c->bid2); dev_free(&c->nb_list); dev_free(&c->nb_wave); dev_free(&c->nb_counts); dev_free(&c->nb_remote);
-    dev_free(&c->scan_partials); dev_free(&c->scan_state); dev_free(&c->d_scal); dev_free(&c->tile_blk);
+    dev_free(&c->scan_partials); dev_free(&c->scan_state); dev_free(&c->d_scal); dev_free(&c->tile_blk); dev_free(&c->sample_buf);
     free_grid(c->gdyn);
     free_grid(c->gstat);
     if (c->mbox) hipHostFree((void*)c->mbox);
@@ -1529,6 +1551,8 @@ int sphx_set_boundary(sphx_ctx* c, const float* xy, uint32_t n) {
     if (!c || (n && !xy)) return SPHX_ERR_INVALID_ARGUMENT;
     c->ahead.valid = false;
     if (c->in_step) return c->fail(SPHX_ERR_NOT_READY, "sphx_set_boundary between step_begin and step_finish");
+    sample_went_stale(c, "sphx_set_boundary replaced the boundary (its grid is rebuilt by the next neighbour build): run a step, or "
+                         "sphx_update_neighborhood + sphx_update_densities");
     SPHX_HIP(c, hipSetDevice(c->device));
     int rc;
     if (n > c->capB) {
@@ -1554,6 +1578,8 @@ int sphx_upload(sphx_ctx* c, const float* pos_xy, const float* vel_xy, uint32_t 
     if (!c || (n && !pos_xy)) return SPHX_ERR_INVALID_ARGUMENT;
     c->ahead.valid = false;
     if (c->in_step) return c->fail(SPHX_ERR_NOT_READY, "sphx_upload between step_begin and step_finish");
+    // (first: a failed reallocation below leaves the particle arrays freed)
+    sample_went_stale(c, "sphx_upload replaced the particles: run a step, or sphx_update_neighborhood + sphx_update_densities");
     SPHX_HIP(c, hipSetDevice(c->device));
     SPHX_HIP(c, hipStreamSynchronize(c->stream));
     clear_histograms(c);
@@ -1620,6 +1646,7 @@ int sphx_update_densities(sphx_ctx* c, int kind) {
         launch_density<2>(c, true, false);
     else
         return c->fail(SPHX_ERR_INVALID_ARGUMENT, "unknown kernel kind");
+    if (c->sample_ready == 1u) c->sample_ready = 2u;  // a neighbour build plus its densities: the fields may be sampled
     return SPHX_OK;
 }
 
@@ -1640,6 +1667,7 @@ int sphx_step_begin_law(sphx_ctx* c, float dt_prev, const sphx_timer_law* law, f
     if (law && (law->timestep_min_ns > law->timestep_max_ns || !(law->particle_diameter > 0) || !(law->cfl_factor > 0) || law->simulation_step_ns == 0))
         return c->fail(SPHX_ERR_INVALID_ARGUMENT, "sphx_timer_law: need 0 < min <= max, a positive diameter, cfl factor and current step");
     SPHX_HIP(c, hipSetDevice(c->device));
+    sample_went_stale(c, "the last DFSPH step did not finish: run a step, or sphx_update_neighborhood + sphx_update_densities");
     const bool ahead_ok = c->ahead.queued && c->ahead.valid;
     c->ahead.valid = false;
     c->step_flags = 0;
@@ -1809,6 +1837,7 @@ int sphx_step_finish(sphx_ctx* c, float dt, sphx_step_stats* out) {
     c->law_active = false;
     s.flags = c->step_flags;
     if (out) *out = s;
+    sample_after_step(c);  // re-grid, densities (fused into the build) and the divergence loop, which moves no particle
     return SPHX_OK;
 }
 
@@ -1822,6 +1851,7 @@ int sphx_wcsph_step_begin(sphx_ctx* c, float dt, float* out_vmax) {
     if (c->tile_mode) return c->fail(SPHX_ERR_INVALID_ARGUMENT, "WCSPH is not available on tiles");
     if (!(dt > 0) || !std::isfinite(dt)) return c->fail(SPHX_ERR_INVALID_ARGUMENT, "dt must be positive and finite");
     SPHX_HIP(c, hipSetDevice(c->device));
+    sample_went_stale(c, "the last WCSPH step did not finish: run a step, or sphx_update_neighborhood + sphx_update_densities");
     c->step_flags = 0;
     c->step_dt_prev = dt;
     const uint32_t n = c->N;
@@ -1888,6 +1918,7 @@ int sphx_wcsph_step_finish(sphx_ctx* c, float dt, sphx_step_stats* out) {
     }
     s.flags = c->step_flags;
     if (out) *out = s;
+    sample_after_step(c);  // phase A re-gridded the leap-frogged positions and took their Poly6 densities; leap frog 2 moves none
     return SPHX_OK;
 }
 
