@@ -1050,108 +1050,158 @@ int alloc_particles(sphx_ctx* c, uint32_t n) {
 // The device judges the residual itself (LoopArgs) unless the residual needs an all-reduce over tiles or the A/B switch is set.
 inline bool device_loop(const sphx_ctx* c) { return !c->tile_mode && !c->host_loop; }
 
-// One iteration of a solver loop queued on the stream: [warm start, dfsph.rs:199-205 / :354-360, before the first one],
-// compute_density_error / compute_density_change, correct_velocity_*.  dt_dev != nullptr: the kernels take the step from
-// device memory (queued by sphx_step_begin_law before the host knows dt).  iter: 1-based index inside its loop; gen: generation
-// number of a device-run loop (0: the host judges the residual).  Returns the mailbox sequence of the residual.
-// pred != nullptr (first density iteration, no warm start in front of it): the iteration's compute_density_error also does the
-// velocity prediction (k_compute_error<false, true>) — the caller has NOT launched k_predict.
-uint32_t enqueue_iteration(sphx_ctx* c, bool divergence, float dt, const float* dt_dev, uint32_t iter, uint32_t gen, uint32_t* out_warm,
-                           const PredArgs* pred = nullptr) {
+// ---- one solver iteration: a launcher per kernel family and the one path that queues them (DESIGN.md §4) ----------------------------
+// Each launcher owns grid and block, the argument list, the choice of instantiation, the launch() label and the byte formula.
+
+// v* = v + a dt (dfsph.rs:484-492).  va / tl: the kernel reads the non-pressure pass's maximum and derives dt itself (sphx_step_begin_law).
+void launch_predict(sphx_ctx* c, const char* label, float dt, const VmaxArgs& va = VmaxArgs{}, const TimerLaw& tl = TimerLaw{}) {
+    const uint32_t n = c->N;
+    launch(c, label, 24.0 * n, [&] { hipLaunchKernelGGL(k_predict, dim3(nblocks(n)), dim3(256), 0, c->stream, c->vel, (const float2*)c->accel, n, dt, c->d_scal, va, tl); });
+}
+
+// compute_density_error / compute_density_change (dfsph.rs:217 / :372).  pred != nullptr: the density kernel does the velocity
+// prediction on the way, from accel[] into vel2[].  clear_hist: the cell count the previous iteration's correction left, wiped on the
+// way.  (No warm_zero array: the zeroing of dfsph.rs:206-208 / :361-363 is implicit, the first correction starts the sum from zero.)
+void launch_compute_error(sphx_ctx* c, bool divergence, float dt, const float* dt_dev, const LoopArgs& la, uint32_t* clear_hist, uint32_t clear_len,
+                          const PredArgs* pred) {
     const uint32_t n = c->N;
     hipStream_t st = c->stream;
     const dim3 g(nblocks(n)), b(256);
-    const float rho0 = c->K.rho0;
-    const float inv_dt = 1.0f / dt;
-    const float lim = -0.5f * rho0 * rho0;
-    float* warm = divergence ? c->stiff : c->kappa;
-    const uint32_t prev_iters = divergence ? c->num_divergence_iters : c->num_density_iters;
     const double lb = list_bytes(c);
-    const bool first = iter == 1;
-    LoopArgs la{};
-    if (gen) {
-        la.enabled = 1;
-        la.iter = iter;
-        la.fixed = divergence ? c->P.fixed_divergence_iterations : c->P.fixed_density_iterations;
-        la.max_iters = divergence ? c->P.max_divergence_iterations : c->P.max_density_iterations;
-        la.gen = gen;
-        la.n_total = n;
-        la.tol = divergence ? c->P.max_divergence_error : c->P.max_avg_density_error;
-        la.rho0 = rho0;
-        la.dt = dt;
-    }
-    if (first) {
-        *out_warm = 0;
-        if (prev_iters > 1) {  // dfsph.rs:199 / :354
-            *out_warm = 1;
-            const double bytes = (16 + 8 + 8 + 4 + lb) * n;  // own position + velocity read, velocity written, staged positions, warm-start values
-            if (divergence && c->div_warm_fused)  // the neighbour build has applied it
-                c->div_warm_fused = false;
-            else if (divergence)
-                launch(c, "correct_divergence_error_warmstart", bytes, [&] {
-                    hipLaunchKernelGGL((k_correct<true, false>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K, inv_dt, lim,
-                                       c->nbv(), dt_dev, CountArgs{}, c->d_scal, LoopArgs{}, ResArgs{}, 0u, TileClassArgs{});
-                });
-            else
-                launch(c, "correct_density_error_warmstart", bytes, [&] {
-                    hipLaunchKernelGGL((k_correct<true, true>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K, inv_dt, lim,
-                                       c->nbv(), dt_dev, CountArgs{}, c->d_scal, LoopArgs{}, ResArgs{}, 0u, TileClassArgs{});
-                });
-        }
-    }
-    float* const wz = nullptr;  // the zeroing of dfsph.rs:206-208 / :361-363 is implicit: the first correction starts the sum from zero
-    const uint32_t seq = ++c->seq;
-    const ResArgs ra{1u, ++c->res_seq, c->mbox_dev, seq};  // the correction reads (and publishes) the residual its compute_error leaves
     if (divergence) {
-        if (first && c->div_error_fused)  // the neighbour build has left this iteration's errors, residual and zeroed warm-start values
-            c->div_error_fused = false;
-        else
-            launch(c, "compute_density_change", (16 + 4 + 4 + lb) * n, [&] {
-                hipLaunchKernelGGL((k_compute_error<true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n,
-                                   c->soff(), c->K, dt, c->nbv(), c->kbuf, wz, c->d_scal, dt_dev, la, (uint32_t*)nullptr, 0u, PredArgs{});
-            });
-        launch(c, "correct_velocity_with_divergence_error", (16 + 8 + 12 + 8 + lb) * n, [&] {
-            hipLaunchKernelGGL((k_correct<false, false>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K, inv_dt, lim, c->nbv(),
-                               dt_dev, CountArgs{}, c->d_scal, la, ra, first ? 1u : 0u, TileClassArgs{});
+        launch(c, "compute_density_change", (16 + 4 + 4 + lb) * n, [&] {
+            hipLaunchKernelGGL((k_compute_error<true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt, c->nbv(),
+                               c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{});
+        });
+    } else if (pred) {
+        PredArgs pa = *pred;
+        pa.accel = c->accel;
+        pa.vel_out = c->vel2;
+        launch(c, "velocity_prediction+compute_density_error", (16 + 8 + 8 + 4 + 4 + 4 + lb) * n, [&] {
+            hipLaunchKernelGGL((k_compute_error<false, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt,
+                               c->nbv(), c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, pa);
         });
     } else {
-        const bool counting = c->fuse_count_ok && !c->no_fused_count && !c->tile_mode && c->gdyn.len();
-        // device-run loop: every correction counts; an iteration that follows another wipes that one's count first (k_compute_error)
-        uint32_t* clear_hist = (gen && !first && counting && c->count_done) ? c->gdyn.hist : nullptr;
-        if (pred) {
-            PredArgs pa = *pred;
-            pa.accel = c->accel;
-            pa.vel_out = c->vel2;
-            launch(c, "velocity_prediction+compute_density_error", (16 + 8 + 8 + 4 + 4 + 4 + lb) * n, [&] {
-                hipLaunchKernelGGL((k_compute_error<false, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n,
-                                   c->soff(), c->K, dt, c->nbv(), c->kbuf, wz, c->d_scal, dt_dev, la, clear_hist, c->gdyn.len(), pa);
-            });
-            std::swap(c->vel, c->vel2);  // the predicted velocities are the velocities from here on (the boundary tail is zero in both)
-        } else {
-            launch(c, "compute_density_error", (16 + 4 + 4 + 4 + lb) * n + (clear_hist ? 4.0 * c->gdyn.len() : 0.0), [&] {
-                hipLaunchKernelGGL((k_compute_error<false>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n,
-                                   c->soff(), c->K, dt, c->nbv(), c->kbuf, wz, c->d_scal, dt_dev, la, clear_hist, c->gdyn.len(), PredArgs{});
-            });
-        }
-        CountArgs ca{};
-        if (counting) {
-            // host-run loop: every correction counts, the count of a correction that turned out not to be the last is dropped here;
-            // device-run loop: the same, dropped by the next iteration's compute_error (above)
-            if (!gen || first) drop_fused_count(c);
-            ca.g = c->gdyn.view();
-            ca.hist = c->gdyn.hist;
-            ca.cidx = c->key;
-            ca.slot = c->slot;
-            ca.dt = dt;
-            c->count_done = true;
-            c->count_n = n;
-        }
-        launch(c, "correct_velocity_with_density_error", (16 + 8 + 12 + 8 + lb + (ca.hist ? 8 : 0)) * n, [&] {
-            hipLaunchKernelGGL((k_correct<false, true>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K, inv_dt, lim, c->nbv(),
-                               dt_dev, ca, c->d_scal, la, ra, first ? 1u : 0u, TileClassArgs{});
+        launch(c, "compute_density_error", (16 + 4 + 4 + 4 + lb) * n + (clear_hist ? 4.0 * clear_len : 0.0), [&] {
+            hipLaunchKernelGGL((k_compute_error<false>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt, c->nbv(),
+                               c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{});
         });
     }
+}
+
+// correct_velocity_with_{density,divergence}_error (dfsph.rs:218 / :373).  ca.hist: the density correction also makes the next build's
+// cell count (+8 B per particle); tc.pid: and the tile's send classification (+4 B).
+void launch_correct(sphx_ctx* c, bool divergence, float dt, const float* dt_dev, const CountArgs& ca, const LoopArgs& la, const ResArgs& ra, bool first,
+                    const TileClassArgs& tc) {
+    const uint32_t n = c->N, f = first ? 1u : 0u;
+    hipStream_t st = c->stream;
+    const dim3 g(nblocks(n)), b(256);
+    const float inv_dt = 1.0f / dt, lim = -0.5f * c->K.rho0 * c->K.rho0;
+    float* warm = divergence ? c->stiff : c->kappa;
+    launch(c, divergence ? "correct_velocity_with_divergence_error" : "correct_velocity_with_density_error",
+           (16 + 8 + 12 + 8 + list_bytes(c) + (ca.hist ? (tc.pid ? 8 + 4 : 8) : 0)) * n, [&] {
+               if (divergence)
+                   hipLaunchKernelGGL((k_correct<false, false>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K, inv_dt,
+                                      lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, f, tc);
+               else if (tc.pid)
+                   hipLaunchKernelGGL((k_correct<false, true, true>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K,
+                                      inv_dt, lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, f, tc);
+               else
+                   hipLaunchKernelGGL((k_correct<false, true>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K, inv_dt,
+                                      lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, f, tc);
+           });
+}
+
+// The warm start in front of a loop (dfsph.rs:199-205 / :354-360).  labelled = false (the tile sub-step): a bare launch, outside
+// launch() — no label, no profile record, and K.rev / K.xcd_shift / K.nt_cold stay as the launch before it left them.
+void launch_warmstart(sphx_ctx* c, bool divergence, float dt, const float* dt_dev, bool labelled) {
+    const uint32_t n = c->N;
+    const dim3 g(nblocks(n)), b(256);
+    const float inv_dt = 1.0f / dt, lim = -0.5f * c->K.rho0 * c->K.rho0;
+    auto go = [&] {
+        if (divergence)
+            hipLaunchKernelGGL((k_correct<true, false>), g, b, 0, c->stream, c->vel, (const float2*)c->posA, (const float*)c->kbuf, c->stiff, n, c->soff(), c->K,
+                               inv_dt, lim, c->nbv(), dt_dev, CountArgs{}, c->d_scal, LoopArgs{}, ResArgs{}, 0u, TileClassArgs{});
+        else
+            hipLaunchKernelGGL((k_correct<true, true>), g, b, 0, c->stream, c->vel, (const float2*)c->posA, (const float*)c->kbuf, c->kappa, n, c->soff(), c->K,
+                               inv_dt, lim, c->nbv(), dt_dev, CountArgs{}, c->d_scal, LoopArgs{}, ResArgs{}, 0u, TileClassArgs{});
+    };
+    if (!labelled) return go();
+    // own position + velocity read, velocity written, staged positions, warm-start values
+    launch(c, divergence ? "correct_divergence_error_warmstart" : "correct_density_error_warmstart", (16 + 8 + 8 + 4 + list_bytes(c)) * n, go);
+}
+
+// What one solver iteration is queued with: everything in which the single context's loops (enqueue_context_iteration) and the tile
+// sub-steps (sub_iteration_impl) differ.  DESIGN.md §4 has the table.
+struct IterSpec {
+    bool divergence, first;          // first: first iteration of its loop (the correction starts the warm-start sum from zero)
+    float dt;
+    const float* dt_dev = nullptr;   // != nullptr: the kernels take the step from device memory
+    uint32_t* out_warm = nullptr;    // != nullptr: the first iteration decides the warm start itself (dfsph.rs:199 / :354) and says so here
+    const PredArgs* pred = nullptr;  // != nullptr: compute_density_error also does the velocity prediction — no k_predict in front
+    LoopArgs la{};                   // enabled: the device judges the residual itself
+    uint32_t* clear_hist = nullptr;  // handed to compute_density_error, with clear_len
+    uint32_t clear_len = 0;
+    CountArgs ca{};                  // hist != nullptr: the density correction counts the next build's cells ...
+    bool drop_count = false;         // ... once the count an earlier correction left has been dropped
+    TileClassArgs tc{};
+};
+inline CountArgs count_args(const sphx_ctx* c, float dt) { return CountArgs{c->gdyn.view(), c->gdyn.hist, c->key, c->slot, dt}; }
+
+// One iteration of a solver loop queued on the stream: [warm start, before the first one], compute_density_error /
+// compute_density_change, correct_velocity_* (dfsph.rs:217-218 / :372-373).  The only place that does.  Returns the mailbox sequence
+// number of the residual.
+uint32_t enqueue_iteration(sphx_ctx* c, const IterSpec& s) {
+    if (s.out_warm && s.first) {
+        const bool warm = (s.divergence ? c->num_divergence_iters : c->num_density_iters) > 1;  // dfsph.rs:199 / :354
+        *s.out_warm = warm ? 1u : 0u;
+        if (warm && s.divergence && c->div_warm_fused)  // the neighbour build has applied it
+            c->div_warm_fused = false;
+        else if (warm)
+            launch_warmstart(c, s.divergence, s.dt, s.dt_dev, true);
+    }
+    const uint32_t seq = ++c->seq;
+    const ResArgs ra{1u, ++c->res_seq, c->mbox_dev, seq};  // the correction reads (and publishes) the residual its compute_error leaves
+    if (s.divergence && s.first && c->div_error_fused)  // the neighbour build has left this iteration's errors, residual and zeroed warm-start values
+        c->div_error_fused = false;
+    else
+        launch_compute_error(c, s.divergence, s.dt, s.dt_dev, s.la, s.clear_hist, s.clear_len, s.pred);
+    if (s.pred) std::swap(c->vel, c->vel2);  // the predicted velocities are the velocities from here on (the boundary tail is zero in both)
+    if (s.drop_count) drop_fused_count(c);
+    if (s.ca.hist) {
+        c->count_done = true;
+        c->count_n = c->N;
+    }
+    launch_correct(c, s.divergence, s.dt, s.dt_dev, s.ca, s.la, ra, s.first, s.tc);
     return seq;
+}
+
+// The single context's form of it.  dt_dev: queued by sphx_step_begin_law before the host knows dt.  iter: 1-based index inside its
+// loop; gen: generation number of a device-run loop (0: the host judges the residual).  pred (first density iteration, no warm start
+// in front of it): the caller has NOT launched k_predict.
+uint32_t enqueue_context_iteration(sphx_ctx* c, bool divergence, float dt, const float* dt_dev, uint32_t iter, uint32_t gen, uint32_t* out_warm,
+                                   const PredArgs* pred = nullptr) {
+    IterSpec s{divergence, iter == 1, dt, dt_dev, out_warm, pred};
+    if (gen) {
+        s.la.enabled = 1;
+        s.la.iter = iter;
+        s.la.fixed = divergence ? c->P.fixed_divergence_iterations : c->P.fixed_density_iterations;
+        s.la.max_iters = divergence ? c->P.max_divergence_iterations : c->P.max_density_iterations;
+        s.la.gen = gen;
+        s.la.n_total = c->N;
+        s.la.tol = divergence ? c->P.max_divergence_error : c->P.max_avg_density_error;
+        s.la.rho0 = c->K.rho0;
+        s.la.dt = dt;
+    }
+    if (!divergence) s.clear_len = c->gdyn.len();
+    if (!divergence && c->fuse_count_ok && !c->no_fused_count && !c->tile_mode && c->gdyn.len()) {
+        // Every correction counts.  Host-run loop: the count of a correction that turned out not to be the last is dropped in front of
+        // the next one; device-run loop: an iteration that follows another has its compute_error wipe that one's count.
+        s.ca = count_args(c, dt);
+        s.drop_count = !gen || s.first;
+        if (!s.drop_count && c->count_done) s.clear_hist = c->gdyn.hist;
+    }
+    return enqueue_iteration(c, s);
 }
 
 // dfsph.rs:221-236 / :376-391 for one published residual sum; sets the iteration-cap flag like the reference prints its warning
@@ -1238,6 +1288,23 @@ void enqueue_nonpressure(sphx_ctx* c, float dt_prev, uint32_t vslot) {
     });
 }
 
+// Run-ahead (sphx_ctx::ahead): the NEXT step's non-pressure pass, with dt_prev = the step that is being finished, goes behind what is
+// on the stream.  publish (tile sub-steps): its maximum is published under a mailbox sequence number of its own, taken once the pass
+// is queued; the single context's pass is published by the sphx_step_begin_law that adopts it.
+void enqueue_run_ahead(sphx_ctx* c, float dt, bool publish) {
+    const uint32_t vslot = take_vmax_slot(c);
+    c->ahead.queued = c->ahead.valid = true;
+    c->ahead.vslot = vslot;
+    c->ahead.seq = 0;
+    c->ahead.n = c->N;
+    std::memcpy(&c->ahead.dt_bits, &dt, 4);
+    enqueue_nonpressure(c, dt, vslot);
+    if (publish) {
+        c->ahead.seq = ++c->seq;
+        hipLaunchKernelGGL(k_publish_vmax, dim3(1), dim3(64), 0, c->stream, c->d_scal, VmaxArgs{1u, vslot, c->mbox_dev, c->ahead.seq});
+    }
+}
+
 // One solver loop (dfsph.rs:195-247 density / :346-402 divergence).  pre_seq != 0: `pre_q` iterations (the first one publishing
 // pre_seq) of loop generation pre_gen are already on the stream.
 // run_ahead (last loop of a step only): see sphx_ctx::ahead.
@@ -1256,19 +1323,11 @@ int solver_loop(sphx_ctx* c, bool divergence, float dt, uint32_t* out_iters, flo
         if (!pre_seq) {
             if (++c->loop_gen == 0) c->loop_gen = 1;
             gen = c->loop_gen;
-            seq1 = enqueue_iteration(c, divergence, dt, nullptr, 1, gen, out_warm);
+            seq1 = enqueue_context_iteration(c, divergence, dt, nullptr, 1, gen, out_warm);
             q = 1;
         }
-        while (q < std::min(prev, cap)) enqueue_iteration(c, divergence, dt, nullptr, ++q, gen, out_warm);
-        if (run_ahead && c->run_ahead) {
-            const uint32_t ahead_slot = take_vmax_slot(c);
-            c->ahead.queued = c->ahead.valid = true;
-            c->ahead.vslot = ahead_slot;
-            c->ahead.seq = 0;
-            c->ahead.n = c->N;
-            std::memcpy(&c->ahead.dt_bits, &dt, 4);
-            enqueue_nonpressure(c, dt, c->ahead.vslot);
-        }
+        while (q < std::min(prev, cap)) enqueue_context_iteration(c, divergence, dt, nullptr, ++q, gen, out_warm);
+        if (run_ahead && c->run_ahead) enqueue_run_ahead(c, dt, false);
         uint32_t w = q;  // the iteration whose verdict the host waits for: the last predicted one first
         for (;;) {
             bool done = false;
@@ -1277,7 +1336,7 @@ int solver_loop(sphx_ctx* c, bool divergence, float dt, uint32_t* out_iters, flo
             c->ahead.valid = false;  // more iterations follow: the pass queued above has read velocities that were not final
             // iteration w has published without meeting the test: the prediction was too low.  From here on keep one full iteration
             // queued behind the one that is running (the host then never sits on the device's critical path).
-            while (q < w + 2) enqueue_iteration(c, divergence, dt, nullptr, ++q, gen, out_warm);
+            while (q < w + 2) enqueue_context_iteration(c, divergence, dt, nullptr, ++q, gen, out_warm);
             w += 1;
         }
         iters = c->mbox->loop_iters;
@@ -1296,7 +1355,7 @@ int solver_loop(sphx_ctx* c, bool divergence, float dt, uint32_t* out_iters, flo
             if (k == iters) *io_flags |= fl;
         }
     } else {
-        uint32_t seq = pre_seq ? pre_seq : enqueue_iteration(c, divergence, dt, nullptr, 1, 0, out_warm);
+        uint32_t seq = pre_seq ? pre_seq : enqueue_context_iteration(c, divergence, dt, nullptr, 1, 0, out_warm);
         for (;;) {
             iters += 1;
             // the residual was published by compute_error; the correction kernel runs while the host reads it
@@ -1304,7 +1363,7 @@ int solver_loop(sphx_ctx* c, bool divergence, float dt, uint32_t* out_iters, flo
             bool more;
             if ((rc = judge_residual(c, divergence, c->mbox->err_sum, iters, dt, &avg, &more, io_flags))) return rc;
             if (!more) break;
-            seq = enqueue_iteration(c, divergence, dt, nullptr, iters + 1, 0, out_warm);
+            seq = enqueue_context_iteration(c, divergence, dt, nullptr, iters + 1, 0, out_warm);
         }
     }
     *out_iters = iters;
@@ -1729,20 +1788,19 @@ int sphx_step_begin_law(sphx_ctx* c, float dt_prev, const sphx_timer_law* law, f
         pa.law = tl;
         const PredArgs* const pred = fuse_pred ? &pa : nullptr;
         if (!fuse_pred)
-            launch(c, "velocity_prediction", 24.0 * n,
-                   [&] { hipLaunchKernelGGL(k_predict, dim3(nblocks(n)), dim3(256), 0, c->stream, c->vel, (const float2*)c->accel, n, 1.0f, c->d_scal, va, tl); });
+            launch_predict(c, "velocity_prediction", 1.0f, va, tl);
         c->fuse_count_ok = true;
         if (device_loop(c)) {
             // as many constant-density iterations as the previous step needed, all reading the device's dt; the device stops the loop
             if (++c->loop_gen == 0) c->loop_gen = 1;
             c->pre_gen = c->loop_gen;
             const uint32_t want = std::min(std::max(1u, c->num_density_iters), c->P.max_density_iterations + 1);
-            c->pre_seq = enqueue_iteration(c, false, 1.0f, dt_dev, 1, c->pre_gen, &c->pre_warm, pred);
-            for (c->pre_queued = 1; c->pre_queued < want;) enqueue_iteration(c, false, 1.0f, dt_dev, ++c->pre_queued, c->pre_gen, &c->pre_warm);
+            c->pre_seq = enqueue_context_iteration(c, false, 1.0f, dt_dev, 1, c->pre_gen, &c->pre_warm, pred);
+            for (c->pre_queued = 1; c->pre_queued < want;) enqueue_context_iteration(c, false, 1.0f, dt_dev, ++c->pre_queued, c->pre_gen, &c->pre_warm);
         } else {
             c->pre_gen = 0;
             c->pre_queued = 1;
-            c->pre_seq = enqueue_iteration(c, false, 1.0f, dt_dev, 1, 0, &c->pre_warm, pred);
+            c->pre_seq = enqueue_context_iteration(c, false, 1.0f, dt_dev, 1, 0, &c->pre_warm, pred);
         }
         c->fuse_count_ok = false;
         c->law_active = true;
@@ -1777,7 +1835,6 @@ int sphx_step_finish(sphx_ctx* c, float dt, sphx_step_stats* out) {
     }
     SPHX_HIP(c, hipSetDevice(c->device));
     const uint32_t n = c->N;
-    hipStream_t st = c->stream;
     sphx_step_stats s;
     std::memset(&s, 0, sizeof(s));
     s.dt_prev = c->step_dt_prev;
@@ -1797,7 +1854,6 @@ int sphx_step_finish(sphx_ctx* c, float dt, sphx_step_stats* out) {
         return code;
     };
     if (n) {
-        const dim3 g(nblocks(n)), b(256);
         uint32_t pre = 0, pre_q = 0, pre_gen = 0;
         if (c->law_active) {
             uint32_t bits;
@@ -1814,8 +1870,7 @@ int sphx_step_finish(sphx_ctx* c, float dt, sphx_step_stats* out) {
             pre_gen = c->pre_gen;
             s.warmstart_density = c->pre_warm;
         } else {
-            launch(c, "velocity_prediction", 24.0 * n,
-                   [&] { hipLaunchKernelGGL(k_predict, g, b, 0, st, c->vel, (const float2*)c->accel, n, dt, c->d_scal, VmaxArgs{}, TimerLaw{}); });
+            launch_predict(c, "velocity_prediction", dt);
         }
         c->law_active = false;
         c->fuse_count_ok = true;
@@ -1909,9 +1964,7 @@ int sphx_wcsph_step_finish(sphx_ctx* c, float dt, sphx_step_stats* out) {
     s.dt = dt;
     s.vmax = c->step_vmax;
     if (n) {
-        launch(c, "wcsph_leapfrog2", 24.0 * n, [&] {
-            hipLaunchKernelGGL(k_predict, dim3(nblocks(n)), dim3(256), 0, c->stream, c->vel, (const float2*)c->accel, n, 0.5f * dt, c->d_scal, VmaxArgs{}, TimerLaw{});
-        });
+        launch_predict(c, "wcsph_leapfrog2", 0.5f * dt);  // (the same kernel as the DFSPH prediction)
         int rc = publish_and_wait(c);  // neighbour-entry count and the sticky flags of this step's build
         if (rc) return rc;
         s.neighbor_entries = c->nb_last;
@@ -2459,7 +2512,7 @@ int sphx_sub_predict(sphx_ctx* c, float dt) {
     flush_pending_advect(c);
     SPHX_HIP(c, hipSetDevice(c->device));
     const uint32_t n = c->N;
-    if (n) launch(c, "velocity_prediction", 24.0 * n, [&] { hipLaunchKernelGGL(k_predict, dim3(nblocks(n)), dim3(256), 0, c->stream, c->vel, (const float2*)c->accel, n, dt, c->d_scal, VmaxArgs{}, TimerLaw{}); });
+    if (n) launch_predict(c, "velocity_prediction", dt);
     return SPHX_OK;
 }
 
@@ -2477,14 +2530,7 @@ int sphx_sub_warmstart(sphx_ctx* c, int divergence, float dt) {
     SPHX_HIP(c, hipSetDevice(c->device));
     const uint32_t n = c->N;
     if (!n) return SPHX_OK;
-    const float inv_dt = 1.0f / dt, lim = -0.5f * c->K.rho0 * c->K.rho0;
-    const dim3 g(nblocks(n)), b(256);
-    if (divergence)
-        hipLaunchKernelGGL((k_correct<true, false>), g, b, 0, c->stream, c->vel, (const float2*)c->posA, (const float*)c->kbuf, c->stiff, n, c->soff(), c->K, inv_dt, lim,
-                           c->nbv(), (const float*)nullptr, CountArgs{}, c->d_scal, LoopArgs{}, ResArgs{}, 0u, TileClassArgs{});
-    else
-        hipLaunchKernelGGL((k_correct<true, true>), g, b, 0, c->stream, c->vel, (const float2*)c->posA, (const float*)c->kbuf, c->kappa, n, c->soff(), c->K, inv_dt, lim,
-                           c->nbv(), (const float*)nullptr, CountArgs{}, c->d_scal, LoopArgs{}, ResArgs{}, 0u, TileClassArgs{});
+    launch_warmstart(c, divergence != 0, dt, nullptr, false);
     return SPHX_OK;
 }
 
@@ -2518,88 +2564,41 @@ static int sub_iteration_impl(sphx_ctx* c, int divergence, float dt, int first, 
     *out_err_sum = 0.0;
     if (out_n_owned) *out_n_owned = 0;
     if (!n) return SPHX_OK;
-    hipStream_t st = c->stream;
-    const dim3 g(nblocks(n)), b(256);
-    const float inv_dt = 1.0f / dt, lim = -0.5f * c->K.rho0 * c->K.rho0;
-    float* warm = divergence ? c->stiff : c->kappa;
-    float* const wz = nullptr;  // (the first correction starts the warm-start sum from zero itself)
-    const uint32_t seq = ++c->seq;
-    const ResArgs ra{1u, ++c->res_seq, c->mbox_dev, seq};
-    const bool fused = c->div_error_fused;  // sphx_sub_regrid_div has done this loop's first compute_density_change
-    c->div_error_fused = false;
     c->div_warm_fused = false;
-    if (fused && !(divergence && first)) return c->fail(SPHX_ERR_NOT_READY, "sphx_sub_regrid_div must be followed by the first divergence iteration");
-    if (divergence) {
-        if (!fused)
-            launch(c, "compute_density_change", (16 + 4 + 4 + list_bytes(c)) * n, [&] {
-                hipLaunchKernelGGL((k_compute_error<true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(),
-                                   c->K, dt, c->nbv(), c->kbuf, wz, c->d_scal, (const float*)nullptr, LoopArgs{}, (uint32_t*)nullptr, 0u, PredArgs{});
-            });
-        launch(c, "correct_velocity_with_divergence_error", (16 + 8 + 12 + 8 + list_bytes(c)) * n, [&] {
-            hipLaunchKernelGGL((k_correct<false, false>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K, inv_dt, lim,
-                               c->nbv(), (const float*)nullptr, CountArgs{}, c->d_scal, LoopArgs{}, ra, first ? 1u : 0u, TileClassArgs{});
-        });
-    } else {
-        if (with_predict) {
-            PredArgs pa{};  // (va.enabled = 0: dt is the argument)
-            pa.accel = c->accel;
-            pa.vel_out = c->vel2;
-            launch(c, "velocity_prediction+compute_density_error", (16 + 8 + 8 + 4 + 4 + 4 + list_bytes(c)) * n, [&] {
-                hipLaunchKernelGGL((k_compute_error<false, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(),
-                                   c->K, dt, c->nbv(), c->kbuf, wz, c->d_scal, (const float*)nullptr, LoopArgs{}, (uint32_t*)nullptr, 0u, pa);
-            });
-            std::swap(c->vel, c->vel2);  // the predicted velocities are the velocities from here on
-        } else
-        launch(c, "compute_density_error", (16 + 4 + 4 + 4 + list_bytes(c)) * n, [&] {
-            hipLaunchKernelGGL((k_compute_error<false>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(),
-                               c->K, dt, c->nbv(), c->kbuf, wz, c->d_scal, (const float*)nullptr, LoopArgs{}, (uint32_t*)nullptr, 0u, PredArgs{});
-        });
-        // Tile path: whichever correction turns out to be the last one of the loop has the advected positions in registers — it does
-        // the re-grid's cell count of the particles the tile keeps and the send counts of the halo exchange that follows (what
-        // k_tile_count / k_tile_pack read every particle again for).  Every correction does; the next one wipes the count.
-        CountArgs ca{};
-        TileClassArgs tc{};
-        if (c->tile_mode && c->tile_fuse_class && c->tile_defer_advect && c->tile_blk && !c->no_fused_count && c->gdyn.len() && !c->boundary_changed &&
-            !c->need_expand && !c->need_recover && !c->recover_streak && !c->tails_dirty && c->builds_since_cover + 1 < COVER_PERIOD) {
-            drop_fused_count(c);
-            ca.g = c->gdyn.view();
-            ca.hist = c->gdyn.hist;
-            ca.cidx = c->key;
-            ca.slot = c->slot;
-            ca.dt = dt;
-            tc.pid = c->pid;
-            tc.blk = c->tile_blk;
-            tc.any = c->tile_blk + (size_t)(nblocks(c->capN) + 8) * MAX_TILE_PEERS;  // (behind the counts: tile_upload's allocation)
-            tc.halo = c->tile_halo;
-            tc.n = c->tile_npeers;
-            for (uint32_t k = 0; k < c->tile_npeers; ++k) tc.rect[k] = c->tile_peer[k];
-            c->count_done = true;
-            c->count_n = n;
-            c->tile_class_done = true;
-            c->count_from_class = true;
-            c->tile_class_n = n;
-            std::memcpy(&c->tile_class_dt_bits, &dt, 4);
-        }
-        launch(c, "correct_velocity_with_density_error", (16 + 8 + 12 + 8 + list_bytes(c) + (ca.hist ? 8 + 4 : 0)) * n, [&] {
-            if (tc.pid)
-                hipLaunchKernelGGL((k_correct<false, true, true>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K, inv_dt,
-                                   lim, c->nbv(), (const float*)nullptr, ca, c->d_scal, LoopArgs{}, ra, first ? 1u : 0u, tc);
-            else
-                hipLaunchKernelGGL((k_correct<false, true>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K, inv_dt,
-                                   lim, c->nbv(), (const float*)nullptr, ca, c->d_scal, LoopArgs{}, ra, first ? 1u : 0u, tc);
-        });
+    if (c->div_error_fused && !(divergence && first)) {  // sphx_sub_regrid_div has done a loop's first compute_density_change
+        c->div_error_fused = false;
+        ++c->seq, ++c->res_seq;  // (the numbers this iteration would have published under stay taken)
+        return c->fail(SPHX_ERR_NOT_READY, "sphx_sub_regrid_div must be followed by the first divergence iteration");
+    }
+    // (no dt_dev, no LoopArgs: the caller all-reduces the residual; no out_warm: the warm start is sphx_sub_warmstart)
+    IterSpec s{divergence != 0, first != 0, dt};
+    const PredArgs host_dt{};  // (va.enabled = 0: dt is the argument)
+    if (with_predict) s.pred = &host_dt;
+    // Tile path: whichever correction turns out to be the last one of the loop has the advected positions in registers — it does
+    // the re-grid's cell count of the particles the tile keeps and the send counts of the halo exchange that follows (what
+    // k_tile_count / k_tile_pack read every particle again for).  Every correction does; the next one wipes the count.
+    if (!divergence && c->tile_mode && c->tile_fuse_class && c->tile_defer_advect && c->tile_blk && !c->no_fused_count && c->gdyn.len() &&
+        !c->boundary_changed && !c->need_expand && !c->need_recover && !c->recover_streak && !c->tails_dirty && c->builds_since_cover + 1 < COVER_PERIOD) {
+        s.drop_count = true;
+        s.ca = count_args(c, dt);
+        s.tc.pid = c->pid;
+        s.tc.blk = c->tile_blk;
+        s.tc.any = c->tile_blk + (size_t)(nblocks(c->capN) + 8) * MAX_TILE_PEERS;  // (behind the counts: tile_upload's allocation)
+        s.tc.halo = c->tile_halo;
+        s.tc.n = c->tile_npeers;
+        for (uint32_t k = 0; k < c->tile_npeers; ++k) s.tc.rect[k] = c->tile_peer[k];
+    }
+    const uint32_t seq = enqueue_iteration(c, s);
+    if (s.drop_count) {  // (the tile-class count was made)
+        c->tile_class_done = true;
+        c->count_from_class = true;
+        c->tile_class_n = n;
+        std::memcpy(&c->tile_class_dt_bits, &dt, 4);
     }
     if (c->sub_ahead_dt > 0.0f) {
         const float dtn = c->sub_ahead_dt;
         c->sub_ahead_dt = 0.0f;
-        const uint32_t vslot = take_vmax_slot(c);
-        c->ahead.queued = c->ahead.valid = true;
-        c->ahead.vslot = vslot;
-        c->ahead.n = n;
-        std::memcpy(&c->ahead.dt_bits, &dtn, 4);
-        enqueue_nonpressure(c, dtn, vslot);
-        c->ahead.seq = ++c->seq;
-        hipLaunchKernelGGL(k_publish_vmax, dim3(1), dim3(64), 0, st, c->d_scal, VmaxArgs{1u, vslot, c->mbox_dev, c->ahead.seq});
+        enqueue_run_ahead(c, dtn, true);
     }
     int rc = wait_mailbox(c, seq);
     if (rc) return rc;
