@@ -18,7 +18,7 @@
  * What is the contract and what is scaffolding (the header has grown beyond the boundary SURVEY.md 8(b) asks for):
  *   STABLE — the drop-in boundary a Rust shim binds:
  *       lifecycle (sphx_default_params, sphx_create, sphx_destroy, sphx_last_error, sphx_abi_version), the particle-array
- *       surface (sphx_set_boundary, sphx_upload, sphx_download*, sphx_num_*, sphx_view_*, sphx_sample_*), the Solver trait (sphx_clear_cached,
+ *       surface (sphx_set_boundary, sphx_upload, sphx_download*, sphx_num_*, sphx_view_*, sphx_sample_*, sphx_render*), the Solver trait (sphx_clear_cached,
  *       sphx_step_begin[_law], sphx_step_finish, sphx_wcsph_step_*), the same trait over a device list (sphx_multi_create[_rank],
  *       sphx_multi_destroy, sphx_multi_set_boundary, sphx_multi_upload, sphx_multi_clear_cached, sphx_multi_step_begin/finish,
  *       sphx_multi_simulation_step[s], sphx_multi_download, sphx_multi_num_owned, sphx_multi_last_error, sphx_comm_ops) and
@@ -52,7 +52,8 @@ extern "C" {
                             *    sphx_multi_info_t.band_packs (was reserved)
                             * 5 (additive): sphx_params.viscosity_model / .fluid_viscosity (were reserved[0..1]; zero = XSPH, the behaviour
                             *    before), SPHX_VISCOSITY_*, sphx_get_viscosity
-                            * 5 (additive): sphx_sample_points, sphx_sample_grid, sphx_sample_out, SPHX_SAMPLE_DEVICE_POINTERS */
+                            * 5 (additive): sphx_sample_points, sphx_sample_grid, sphx_sample_out, SPHX_SAMPLE_DEVICE_POINTERS
+                            * 5 (additive): sphx_render, sphx_render_fit, sphx_render_view, sphx_render_out, SPHX_RENDER_* */
 
 /* ---- status codes ---- */
 enum {
@@ -220,6 +221,62 @@ int sphx_sample_points(sphx_ctx* ctx, const float* xy, uint32_t m, int kernel_ki
  * through sphx_sample_points give bit-identical outputs. */
 int sphx_sample_grid(sphx_ctx* ctx, float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, int kernel_kind,
                      uint32_t flags, const sphx_sample_out* out);
+
+/* ---- rendering: the reference app's picture of the particles (main.rs:239-275 draw_fluid, recording mode :310-331, :380-397) ---------
+ * Every fluid particle a disc coloured heatmap_color(|v| * speed_scale), drawn in array order over the grey boundary particles over the
+ * background, through the Camera of camera.rs — as an RGBA8 image and / or an image of owners, on the device: a frame is 4 bytes per pixel
+ * instead of 12 per particle (sphx_view_*).  The contract, for pixel (ix, iy) of a view, all in fp32 and unfused:
+ *   inv = 1.0f / pixel_per_world_unit;
+ *   qx = center[0] + (((float)ix + 0.5f) - 0.5f * (float)width) * inv,
+ *   qy = center[1] - (((float)iy + 0.5f) - 0.5f * (float)height) * inv      (the inverse of Camera::world_to_screen_coords, camera.rs:43-51,
+ *                                                                             at the pixel centre; row 0 is the TOP row)
+ *   r = max(radius != 0 ? radius : particle_radius, min_pixel_radius * inv), r2 = r * r.
+ *   Particle j COVERS the pixel iff dx = x_j.x - qx, dy = x_j.y - qy, d2 = dx*dx + dy*dy, d2 <= r2.  A non-finite position covers nothing.
+ *   owner = the highest device index j (the order of sphx_download) among ALL fluid particles that cover the pixel — the reference draws
+ *           its instances in array order, later over earlier (main.rs:242-258); else SPHX_RENDER_BOUNDARY if any boundary particle covers
+ *           it (boundary instances come first, main.rs:160-170); else SPHX_RENDER_NONE.  Not a cell neighbourhood: all particles.
+ *   rgba  = the background / boundary bytes as given; for a fluid owner j with velocity v (sphx_download's): s = sqrtf(v.x*v.x + v.y*v.y)
+ *           (correctly rounded), t = s * speed_scale, c_k = t * 3.0f - (float)k for k = 0, 1, 2 (heatmap_color, main.rs:74-80) clamped to
+ *           [0, 1] with a NaN becoming 0, byte (uint8_t)(c_k * 255.0f + 0.5f), alpha 255.
+ * The result is a pure function of the downloaded arrays and the view.  Deviations from the reference's GPU pipeline: an exact disc
+ * instead of Mesh::new_circle's polygon (tolerance 0.0003, main.rs:104-112), pixel-centre coverage without multisampling, no sRGB
+ * conversion (parity unpinned: ggez is not in the tree).
+ * min_pixel_radius makes a zoomed-out frame useful: every point of the image is within sqrt(0.5) ~ 0.7071 pixels of a pixel centre, so with
+ * min_pixel_radius >= 0.7072 every particle inside the image covers at least one pixel.
+ * When the call is allowed: wherever sphx_download is (after an upload, after a finished step of either solver; a pending advection is
+ * applied first, as there); it needs no neighbour build and no densities.  Between a step_begin and its step_finish: SPHX_ERR_NOT_READY.
+ * Before any upload (N = 0): the boundary over the background.  A tile context (sphx_tile_*, sphx_multi_tile_ctx) is refused with
+ * SPHX_ERR_INVALID_ARGUMENT (it holds ghosts).  N <= 2^32 - 3 (two owner codes are taken).
+ * Argument errors (SPHX_ERR_INVALID_ARGUMENT, the message names the argument): view / out NULL, both outputs NULL, unknown flag bits,
+ * pixel_per_world_unit / center / radius / min_pixel_radius / speed_scale not finite, pixel_per_world_unit <= 0, radius < 0 or
+ * > smoothing_length, min_pixel_radius < 0 or > 4, width * height >= 2^28.  width * height == 0 is a successful no-op.  The two upper
+ * bounds keep a call's work bounded whatever the view: a disc of radius h is overdrawn ~13 times at rest density, a disc of 4 pixels
+ * touches at most 81 pixels per particle.
+ * No side effects: like a sampling query the call only reads; a run with renders between its steps is bit-identical to one without. */
+typedef struct sphx_render_view {
+    uint32_t width, height;      /* pixels; row 0 is the TOP row (screen coordinates, camera.rs:43-51) */
+    float center[2];             /* Camera::position: the world point in the middle of the image */
+    float pixel_per_world_unit;  /* Camera::pixel_per_world_unit (finite, > 0) */
+    float radius;                /* disc radius in world units, <= smoothing_length; 0 = particle_radius (main.rs:103-108) */
+    float min_pixel_radius;      /* lower bound of the disc radius, in pixels, <= 4; 0 = none (the reference) */
+    float speed_scale;           /* heat-map argument t = |v| * speed_scale; main.rs:255 uses 0.1 */
+    uint8_t background[4];       /* main.rs:369: (0.4, 0.4, 0.45, 1) -> 102, 102, 115, 255 */
+    uint8_t boundary[4];         /* main.rs:153-158: 0.2 grey -> 51, 51, 51, 255 */
+    uint32_t reserved[2];
+} sphx_render_view;              /* 48 bytes */
+typedef struct sphx_render_out {
+    uint8_t* rgba;    /* [height*width*4], bytes r, g, b, a, or NULL (a device pointer must be 4-byte aligned) */
+    uint32_t* owner;  /* [height*width] or NULL */
+} sphx_render_out;
+enum { SPHX_RENDER_NONE = 0xFFFFFFFFu, SPHX_RENDER_BOUNDARY = 0xFFFFFFFEu };
+enum { SPHX_RENDER_DEVICE_POINTERS = 1u }; /* as SPHX_SAMPLE_DEVICE_POINTERS: the outputs are device pointers, the call is enqueued on the
+                                              context's stream and does not wait */
+/* Camera::center_around_world_rect (camera.rs:21-35) for the screen (0, 0, width, height) and the world rectangle (x, y, w, h):
+ * pixel_per_world_unit = min(width / w, height / h), center = (x + w * 0.5, y + h * 0.5); plus the app's defaults (radius 0,
+ * min_pixel_radius 0, speed_scale 0.1, the two colours above).  Pure host code, needs no context and no GPU.  SPHX_ERR_INVALID_ARGUMENT
+ * for out NULL, a non-finite number, or w / h <= 0. */
+int sphx_render_fit(uint32_t width, uint32_t height, float x, float y, float w, float h, sphx_render_view* out);
+int sphx_render(sphx_ctx* ctx, const sphx_render_view* view, uint32_t flags, const sphx_render_out* out);
 
 /* ---- Solver trait (solver/mod.rs:12-18) ---------------------------------------------------------------------- */
 /* Solver::clear_cached_data (dfsph.rs:406-412) */

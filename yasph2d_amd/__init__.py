@@ -15,7 +15,8 @@ from ._lib import (FLAG_DENSITY_ITER_CAP, FLAG_DIVERGENCE_ITER_CAP, FLAG_DENSE_C
                    KERNEL_SPIKY, KERNEL_WENDLAND_C2, VISCOSITY_PHYSICAL, VISCOSITY_XSPH, SphxError, SphxKernelTime, SphxParams, SphxStepStats)
 
 __all__ = ["SphxContext", "FluidParticleWorld", "TimeManager", "DFSPHSolver", "DFSPHMultiSolver", "default_params", "duration_from_secs_f32",
-           "duration_as_secs_f32", "SphxError", "WCSPHSolver", "VISCOSITY_XSPH", "VISCOSITY_PHYSICAL", "SAMPLE_FIELDS", "gauge_elevation"]
+           "duration_as_secs_f32", "SphxError", "WCSPHSolver", "VISCOSITY_XSPH", "VISCOSITY_PHYSICAL", "SAMPLE_FIELDS", "gauge_elevation",
+           "render_fit", "write_png", "SCENE_RECT"]
 
 
 def _p(a):
@@ -87,6 +88,61 @@ def _out_struct(outs, ptr):
     for f, a in outs.items():
         setattr(o, f, ptr(a) or 1)  # (an empty tensor has no storage: a non-NULL dummy still names the field; nothing is written)
     return o
+
+
+SCENE_RECT = (-0.1, -0.1, 2.1, 1.6)  # the world rectangle the reference app's camera is fitted to (main.rs:137), at scale 1
+_VIEW_FIELDS = ("width", "height", "center", "pixel_per_world_unit", "radius", "min_pixel_radius", "speed_scale", "background", "boundary")
+
+
+def _set_view_fields(view, fields):
+    for k, val in fields.items():
+        if k not in _VIEW_FIELDS:
+            raise TypeError("unknown view field %r (one of %s)" % (k, ", ".join(_VIEW_FIELDS)))
+        if k in ("center", "background", "boundary"):
+            val = tuple(val)
+            if len(val) != len(getattr(view, k)):
+                raise ValueError("%s takes %d values" % (k, len(getattr(view, k))))
+            val = type(getattr(view, k))(*val)
+        setattr(view, k, val)
+    return view
+
+
+def render_fit(width, height, world_rect=SCENE_RECT, **view_fields):
+    """sphx_render_fit: the camera of Camera::center_around_world_rect (camera.rs:21-35) for a width x height screen and the world
+    rectangle (x, y, w, h), with the reference app's drawing defaults, as a SphxRenderView; view_fields override single fields
+    (radius, min_pixel_radius, speed_scale, background, boundary, center, pixel_per_world_unit).  Needs no GPU."""
+    v = _lib.SphxRenderView()
+    x, y, w, h = (float(t) for t in world_rect)
+    rc = _lib.lib().sphx_render_fit(int(width), int(height), x, y, w, h, C.byref(v))
+    if rc:
+        raise SphxError(rc, "sphx_render_fit: world_rect must be finite with w, h > 0")
+    return _set_view_fields(v, view_fields)
+
+
+def _copy_view(view):
+    v = _lib.SphxRenderView()
+    C.memmove(C.byref(v), C.byref(view), C.sizeof(v))
+    return v
+
+
+def write_png(path, rgba):
+    """Write a uint8 (H, W, 4) RGBA or (H, W, 3) RGB image as a PNG (8 bits per channel, filter 0 on every row; standard library only)."""
+    import struct
+    import zlib
+
+    a = np.ascontiguousarray(rgba, np.uint8)
+    if a.ndim != 3 or a.shape[2] not in (3, 4) or a.shape[0] == 0 or a.shape[1] == 0:
+        raise ValueError("rgba must be a non-empty uint8 (H, W, 4) or (H, W, 3) array, not shape %s" % (a.shape,))
+    h, w, ch = a.shape
+
+    def chunk(kind, data):
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+    rows = np.zeros((h, 1 + w * ch), np.uint8)  # one filter-type byte (0 = None) in front of every row
+    rows[:, 1:] = a.reshape(h, w * ch)
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 6 if ch == 4 else 2, 0, 0, 0)) +
+                chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))
 
 
 def gauge_elevation(ctx, xs, y_lo, y_hi, dy, kernel=KERNEL_WENDLAND_C2):
@@ -333,6 +389,56 @@ class SphxContext:
         self._chk(self.L.sphx_sample_grid(self.h, origin[0], origin[1], dx, dy, nx, ny, kernel, 0,
                                           C.byref(_out_struct(outs, lambda a: a.ctypes.data))))
         return outs
+
+    def render(self, view=None, *, out=None, owner=False, rgba=True, **view_fields):
+        """sphx_render: the particles drawn as discs (the contract is in include/sphx.h).
+
+        view: a SphxRenderView (render_fit); None = render_fit(width, height, world_rect) with width = 1920, height = 1080 and
+        world_rect = SCENE_RECT unless given among view_fields.  Other view_fields override single fields of (a copy of) the view.
+        Host path (out None): returns the image as a uint8 (H, W, 4) numpy array; with owner=True the pair (image, uint32 (H, W) owners:
+        a device index, _lib.RENDER_BOUNDARY or _lib.RENDER_NONE); with rgba=False the owners alone.
+        Device path: out = a torch uint8 tensor of shape (H, W, 4) on the context's device (or None with rgba=False) — the image is
+        written into it; owner=True allocates an int32 (H, W) tensor, owner=<such a tensor> uses it (torch has no uint32 arithmetic: the
+        two codes read -1 and -2).
+        Like sample(), the device path synchronises torch's current stream before the call and the context's stream after it."""
+        if view is None:
+            width, height = view_fields.pop("width", 1920), view_fields.pop("height", 1080)
+            view = render_fit(width, height, view_fields.pop("world_rect", SCENE_RECT))
+        else:
+            view = _copy_view(view)
+        _set_view_fields(view, view_fields)
+        owner_tensor = owner if _is_torch(owner) else None
+        owner = owner_tensor is not None or bool(owner)
+        if not rgba and not owner:
+            raise ValueError("nothing to render: rgba and owner are both off")
+        h, w = view.height, view.width
+        o = _lib.SphxRenderOut()
+        if out is not None or owner_tensor is not None:
+            import torch
+
+            dev = out.device if out is not None else owner_tensor.device
+            if out is not None and (not _is_torch(out) or out.device.type != "cuda" or out.dtype != torch.uint8 or tuple(out.shape) != (h, w, 4)
+                                    or not out.is_contiguous()):
+                raise ValueError("out must be a contiguous uint8 (%d, %d, 4) tensor on the context's device" % (h, w))
+            if not rgba and out is not None:
+                raise ValueError("out given with rgba=False")
+            own = None
+            if owner:
+                own = owner_tensor if owner_tensor is not None else torch.empty((h, w), dtype=torch.int32, device=dev)
+                if own.dtype != torch.int32 or tuple(own.shape) != (h, w) or not own.is_contiguous() or own.device != dev:
+                    raise ValueError("owner must be a contiguous int32 (%d, %d) tensor on the device of out" % (h, w))
+            o.rgba = (out.data_ptr() or 1) if out is not None else None
+            o.owner = (own.data_ptr() or 1) if own is not None else None
+            torch.cuda.current_stream(dev).synchronize()
+            self._chk(self.L.sphx_render(self.h, C.byref(view), _lib.RENDER_DEVICE_POINTERS, C.byref(o)))
+            self.synchronize()
+            return own if out is None else ((out, own) if own is not None else out)
+        img = np.zeros((h, w, 4), np.uint8) if rgba else None
+        own = np.zeros((h, w), np.uint32) if owner else None
+        o.rgba = (img.ctypes.data or 1) if rgba else None
+        o.owner = (own.ctypes.data or 1) if owner else None
+        self._chk(self.L.sphx_render(self.h, C.byref(view), 0, C.byref(o)))
+        return own if not rgba else ((img, own) if owner else img)
 
     def profile_enable(self, on=True):
         self._chk(self.L.sphx_profile_enable(self.h, int(on)))

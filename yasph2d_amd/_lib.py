@@ -89,6 +89,20 @@ class SphxSampleOut(C.Structure):
     _fields_ = [("density", C.c_void_p), ("fraction", C.c_void_p), ("velocity", C.c_void_p), ("count", C.c_void_p)]
 
 
+RENDER_DEVICE_POINTERS = 1  # sphx_render flags
+RENDER_NONE, RENDER_BOUNDARY = 0xFFFFFFFF, 0xFFFFFFFE  # owner codes
+
+
+class SphxRenderView(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("center", C.c_float * 2), ("pixel_per_world_unit", C.c_float),
+                ("radius", C.c_float), ("min_pixel_radius", C.c_float), ("speed_scale", C.c_float), ("background", C.c_uint8 * 4),
+                ("boundary", C.c_uint8 * 4), ("reserved", C.c_uint32 * 2)]
+
+
+class SphxRenderOut(C.Structure):
+    _fields_ = [("rgba", C.c_void_p), ("owner", C.c_void_p)]
+
+
 class SphxMultiOptions(C.Structure):
     _fields_ = [("halo_cells", C.c_uint32), ("fixed_halo", C.c_uint32), ("rebalance_every", C.c_uint32), ("layout", C.c_uint32),
                 ("cap_records", C.c_uint32), ("overlap_exchange", C.c_uint32), ("reserved", C.c_uint32 * 2)]
@@ -131,6 +145,8 @@ SIGNATURES = {
     "sphx_num_boundary": (_u32, [_vp]),
     "sphx_sample_points": (_i, [_vp, _vp, _u32, _i, _u32, C.POINTER(SphxSampleOut)]),
     "sphx_sample_grid": (_i, [_vp, _f, _f, _f, _f, _u32, _u32, _i, _u32, C.POINTER(SphxSampleOut)]),
+    "sphx_render_fit": (_i, [_u32, _u32, _f, _f, _f, _f, C.POINTER(SphxRenderView)]),
+    "sphx_render": (_i, [_vp, C.POINTER(SphxRenderView), _u32, C.POINTER(SphxRenderOut)]),
     "sphx_clear_cached": (_i, [_vp]),
     "sphx_step_begin": (_i, [_vp, _f, C.POINTER(_f)]),
     "sphx_step_begin_law": (_i, [_vp, _f, _vp, _vp]),

@@ -3,6 +3,7 @@
 //
 //   sphx_harness [--solver dfsph|wcsph] [--viscosity xsph|physical[:mu]] [--scale S | --particles N] [--steps K] [--warmup W] [--no-law] [--sync]
 //                [--gauges x1,x2,... [--gauge-range lo:hi:dy]]
+//                [--record DIR [--record-fps F] [--record-size WxH] [--record-min-pixel-radius P]]
 //
 // --viscosity: the solver's ViscosityModel (main.rs:93-100): XSPH (default) or PhysicalViscosityModel with fluid_viscosity mu
 // (default 1.0016e-3, physical.rs:14; main.rs:96 sets 0.01).
@@ -10,6 +11,14 @@
 // --gauges: after the run, the free-surface elevation at each x (sphx_sample_grid of the fluid fraction on a one-column lattice from lo
 // in steps of dy up to hi, the rule of yasph2d_amd.gauge_elevation): "gauge_elevations": [...] in the JSON line, null where a column
 // holds no fluid.  Default range lo = 0, hi = 2.5 * scale (the top of the scene), dy = particle_radius / 2.
+//
+// --record: the reference's recording mode (main.rs:310-331, :344-346, :380-397).  The timer gets TargetFrameLength(1 / F) (F = 60), the
+// camera is the app's (main.rs:137: Rect(-0.1, -0.1, 2.1, 1.6) x scale fitted to a W x H screen, 1920x1080), and every completed frame is
+// drawn on the device (sphx_render) and written as DIR/<frame>.ppm (binary P6, alpha dropped).  Before each step (warm-up steps included),
+// frame k = 1, 2, ... is written while k / F - total_simulated_time < simulation_step: CaughtUpWithRenderTime of timemanager.rs:212-228
+// with force_frame_delta(1 / F).  The accepted-lag and max_simulated_time_per_frame terms of that loop only matter against a wall
+// clock and are left out; the run still ends after --steps steps.  The JSON line gains "frames": n and "last_frame_fnv" (FNV-1a of the
+// last RGBA image).  --record-min-pixel-radius: sphx_render_view.min_pixel_radius (0: the reference's discs).
 //
 // Prints one JSON line: particle-steps/s over the K timed steps, the timer's final step, iteration statistics and an FNV-1a
 // checksum of the final (downloaded) positions/velocities, which tests compare with the Python-driven run of the same scene.
@@ -22,6 +31,8 @@
 #include <memory>
 #include <string>
 #include <vector>
+
+#include <sys/stat.h>
 
 #include "sphx_host.hpp"
 
@@ -73,6 +84,8 @@ int main(int argc, char** argv) {
     std::string viscosity = "xsph";
     std::string gauges_arg, gauge_range_arg;
     bool want_gauges = false, want_range = false;
+    std::string record_dir, record_fps_arg, record_size_arg, record_mpr_arg;
+    bool want_record = false, want_fps = false, want_size = false, want_mpr = false;
     for (int a = 1; a < argc; ++a) {
         const std::string s = argv[a];
         auto next = [&]() -> const char* { return a + 1 < argc ? argv[++a] : "0"; };
@@ -86,6 +99,10 @@ int main(int argc, char** argv) {
         else if (s == "--sync") sync = true;
         else if (s == "--gauges") gauges_arg = next(), want_gauges = true;
         else if (s == "--gauge-range") gauge_range_arg = next(), want_range = true;
+        else if (s == "--record") record_dir = a + 1 < argc ? argv[++a] : "", want_record = true;
+        else if (s == "--record-fps") record_fps_arg = next(), want_fps = true;
+        else if (s == "--record-size") record_size_arg = next(), want_size = true;
+        else if (s == "--record-min-pixel-radius") record_mpr_arg = next(), want_mpr = true;
         else {
             std::fprintf(stderr, "unknown argument %s\n", s.c_str());
             return 2;
@@ -121,6 +138,25 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    double record_fps = 60.0, record_mpr = 0.0;
+    uint32_t record_w = 1920, record_h = 1080;
+    if (want_record || want_fps || want_size || want_mpr) {
+        bool ok = want_record && !record_dir.empty();
+        if (ok && want_fps) ok = parse_double(record_fps_arg, &record_fps) && record_fps > 0.0 && record_fps <= 1e9;
+        if (ok && want_mpr) ok = parse_double(record_mpr_arg, &record_mpr) && record_mpr >= 0.0 && record_mpr <= 4.0;
+        if (ok && want_size) {
+            const size_t x = record_size_arg.find('x');
+            double w = 0, h = 0;
+            ok = x != std::string::npos && parse_double(record_size_arg.substr(0, x), &w) && parse_double(record_size_arg.substr(x + 1), &h) &&
+                 w >= 1.0 && h >= 1.0 && w == std::floor(w) && h == std::floor(h) && w * h < 268435456.0;
+            record_w = ok ? (uint32_t)w : 0u, record_h = ok ? (uint32_t)h : 0u;
+        }
+        if (!ok) {
+            std::fprintf(stderr, "invalid --record options (--record DIR [--record-fps F > 0] [--record-size WxH, W * H < 2^28] "
+                                 "[--record-min-pixel-radius P in [0, 4]])\n");
+            return 2;
+        }
+    }
     sphx_params params = sph::HipDfsphSolver::params_of(world, nullptr);
     {
         const size_t colon = viscosity.find(':');
@@ -150,7 +186,47 @@ int main(int argc, char** argv) {
     sph::TimeManager tm = sph::TimeManager::adaptive(sph::Duration::from_secs_f32(1.0f / 120.0f / 3.0f), sph::Duration::from_secs_f32(1.0f / 60.0f / 400.0f),
                                                      wcsph ? 0.2f : 1.5f);  // main.rs:115-127
     const size_t n = world.particles.positions.size();
+    // recording mode
+    sph::Camera camera = sph::Camera::center_around_world_rect(record_w, record_h, -0.1f * scale, -0.1f * scale, 2.1f * scale, 1.6f * scale);  // main.rs:137
+    camera.view.min_pixel_radius = (float)record_mpr;
+    const uint64_t frame_ns = (uint64_t)std::llround(1e9 / record_fps);  // Duration::from_secs_f64(1.0 / RECORDING_FPS)
+    uint64_t frames = 0, last_frame_fnv = 0;
+    std::vector<uint8_t> image;
+    if (want_record) {
+        tm.timestep_target_frame = sph::Duration{frame_ns};  // main.rs:323-326
+        mkdir(record_dir.c_str(), 0777);
+        image.resize((size_t)record_w * record_h * 4);
+    }
+    auto record_due_frames = [&]() {
+        for (;;) {
+            const uint64_t due = (frames + 1) * frame_ns, done = tm.total_simulated_time.ns;
+            if ((due > done ? due - done : 0) >= tm.simulation_step().ns) return;  // PerformStepAndCallAgain
+            // frame `frames + 1` is complete: draw it
+            sphx_render_out o{image.data(), nullptr};
+            const int rc = solver->render(camera, 0u, &o);
+            if (rc != SPHX_OK) {
+                std::fprintf(stderr, "render failed: %s (status %d)\n", sphx_last_error(solver->ctx()), rc);
+                std::exit(1);
+            }
+            ++frames;
+            last_frame_fnv = fnv1a(image.data(), image.size());
+            const std::string path = record_dir + "/" + std::to_string(frames) + ".ppm";
+            FILE* f = std::fopen(path.c_str(), "wb");
+            bool ok = f != nullptr;
+            if (ok) {
+                std::vector<uint8_t> rgb((size_t)record_w * record_h * 3);
+                for (size_t p = 0; p < (size_t)record_w * record_h; ++p) std::memcpy(&rgb[3 * p], &image[4 * p], 3);
+                ok = std::fprintf(f, "P6\n%u %u\n255\n", record_w, record_h) > 0 && std::fwrite(rgb.data(), 1, rgb.size(), f) == rgb.size();
+                ok = std::fclose(f) == 0 && ok;
+            }
+            if (!ok) {
+                std::fprintf(stderr, "cannot write %s\n", path.c_str());
+                std::exit(1);
+            }
+        }
+    };
     auto step = [&]() {
+        if (want_record) record_due_frames();
         tm.on_step_started();
         solver->simulation_step(world, tm);
         if (solver->last_status != SPHX_OK) {
@@ -196,6 +272,11 @@ int main(int argc, char** argv) {
             gauge_json += (g ? ", " : "") + std::string(buf);
         }
         gauge_json += "]";
+    }
+    if (want_record) {
+        char buf[96];
+        std::snprintf(buf, sizeof(buf), ", \"frames\": %llu, \"last_frame_fnv\": \"%016llx\"", (unsigned long long)frames, (unsigned long long)last_frame_fnv);
+        gauge_json += buf;
     }
     std::printf("{\"solver\": \"%s\", \"viscosity\": \"%s\", \"fluid_viscosity\": %.9g, \"particles\": %zu, \"boundary\": %zu, \"steps\": %ld, \"particle_steps_per_s\": %.6e, \"ms_per_step\": %.6f, "
                 "\"timer_step_ns\": %llu, \"simulated_ns\": %llu, \"mean_density_iterations\": %.4f, \"mean_divergence_iterations\": %.4f, "

@@ -521,6 +521,24 @@ uint64_t sphx_timer_total_simulated_ns(const sphx_timer* t) { return t->t.total_
 uint32_t sphx_timer_num_steps(const sphx_timer* t) { return t->t.num_simulation_steps; }
 void sphx_timer_set_target_frame(sphx_timer* t, uint64_t target_ns) { t->t.timestep_target_frame.ns = target_ns; }
 void sphx_timer_on_step_started(sphx_timer* t) { t->t.on_step_started(); }
+// Camera::center_around_world_rect (camera.rs:21-35) over the screen (0, 0, width, height), plus the app's drawing defaults
+int sphx_render_fit(uint32_t width, uint32_t height, float x, float y, float w, float h, sphx_render_view* out) {
+    if (!out || !std::isfinite(x) || !std::isfinite(y) || !std::isfinite(w) || !std::isfinite(h) || !(w > 0.0f) || !(h > 0.0f))
+        return SPHX_ERR_INVALID_ARGUMENT;
+    std::memset(out, 0, sizeof(*out));
+    out->width = width;
+    out->height = height;
+    const float ppx = (float)width / w, ppy = (float)height / h;  // screen_extent.div_element_wise(world_extent)
+    out->pixel_per_world_unit = ppx < ppy ? ppx : ppy;
+    out->center[0] = x + w * 0.5f;
+    out->center[1] = y + h * 0.5f;
+    out->speed_scale = 0.1f;  // main.rs:255
+    const uint8_t bg[4] = {102, 102, 115, 255}, bd[4] = {51, 51, 51, 255};  // main.rs:369, :153-158
+    std::memcpy(out->background, bg, 4);
+    std::memcpy(out->boundary, bd, 4);
+    return SPHX_OK;
+}
+
 int sphx_timer_law_of(const sphx_timer* t, float particle_diameter, sphx_timer_law* out) {
     if (!t || !out) return SPHX_ERR_INVALID_ARGUMENT;
     sph::timer_law_of(t->t, particle_diameter, out);

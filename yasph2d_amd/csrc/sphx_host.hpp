@@ -100,6 +100,22 @@ struct TimeManager {
 // what sphx_step_begin_law needs to know about the timer (its public config + current step)
 void timer_law_of(const TimeManager& tm, Real particle_diameter, sphx_timer_law* out);
 
+// camera.rs:14-51 over the screen rectangle (0, 0, width, height): the camera is the sphx_render_view that sphx_render draws through
+struct Camera {
+    sphx_render_view view{};
+    static Camera center_around_world_rect(uint32_t width, uint32_t height, Real x, Real y, Real w, Real h) {  // camera.rs:21-35
+        Camera c;
+        sphx_render_fit(width, height, x, y, w, h, &c.view);
+        return c;
+    }
+    Real pixel_per_world_unit() const { return view.pixel_per_world_unit; }
+    Point position() const { return Point{view.center[0], view.center[1]}; }
+    Point world_to_screen_coords(Point world_pos) const {  // camera.rs:43-51 (screen.x = screen.y = 0)
+        const Real vx = (world_pos.x - view.center[0]) * view.pixel_per_world_unit, vy = (world_pos.y - view.center[1]) * view.pixel_per_world_unit;
+        return Point{vx + (Real)view.width * 0.5f, (Real)view.height * 0.5f - vy};
+    }
+};
+
 // solver/mod.rs:12-18
 struct Solver {
     virtual ~Solver() {}
@@ -131,6 +147,8 @@ class HipDfsphSolver : public Solver {
     int sample_grid(float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, int kernel_kind, uint32_t flags, const sphx_sample_out* out) {
         return sphx_sample_grid(ctx_, x0, y0, dx, dy, nx, ny, kernel_kind, flags, out);
     }
+    // draw_fluid (main.rs:239-275) through `camera` into host (flags 0) or device (SPHX_RENDER_DEVICE_POINTERS) images: sphx_render
+    int render(const Camera& camera, uint32_t flags, const sphx_render_out* out) { return sphx_render(ctx_, &camera.view, flags, out); }
     // the params a null params_or_null stands for: sphx_default_params + the world's properties (a caller that changes one field,
     // e.g. the viscosity model, starts from these)
     static sphx_params params_of(const FluidParticleWorld& world, const sphx_params* params_or_null);

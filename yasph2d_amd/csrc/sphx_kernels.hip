@@ -3220,3 +3220,5 @@ __global__ __launch_bounds__(64) void k_publish(DevScalars* scal, Mailbox* mb, u
 #include "sphx_launch.inc"
 // field sampling at points and on lattices (kernels + C ABI)
 #include "sphx_sample.inc"
+// the particles drawn as discs into an image (kernels + C ABI)
+#include "sphx_render.inc"
