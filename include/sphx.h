@@ -18,7 +18,7 @@
  * What is the contract and what is scaffolding (the header has grown beyond the boundary SURVEY.md 8(b) asks for):
  *   STABLE — the drop-in boundary a Rust shim binds:
  *       lifecycle (sphx_default_params, sphx_create, sphx_destroy, sphx_last_error, sphx_abi_version), the particle-array
- *       surface (sphx_set_boundary, sphx_upload, sphx_download*, sphx_num_*, sphx_view_*, sphx_sample_*, sphx_render*), the Solver trait (sphx_clear_cached,
+ *       surface (sphx_set_boundary, sphx_upload, sphx_append, sphx_remove, sphx_download*, sphx_num_*, sphx_view_*, sphx_sample_*, sphx_render*), the Solver trait (sphx_clear_cached,
  *       sphx_step_begin[_law], sphx_step_finish, sphx_wcsph_step_*), the same trait over a device list (sphx_multi_create[_rank],
  *       sphx_multi_destroy, sphx_multi_set_boundary, sphx_multi_upload, sphx_multi_clear_cached, sphx_multi_step_begin/finish,
  *       sphx_multi_simulation_step[s], sphx_multi_download, sphx_multi_num_owned, sphx_multi_last_error, sphx_comm_ops) and
@@ -53,7 +53,8 @@ extern "C" {
                             * 5 (additive): sphx_params.viscosity_model / .fluid_viscosity (were reserved[0..1]; zero = XSPH, the behaviour
                             *    before), SPHX_VISCOSITY_*, sphx_get_viscosity
                             * 5 (additive): sphx_sample_points, sphx_sample_grid, sphx_sample_out, SPHX_SAMPLE_DEVICE_POINTERS
-                            * 5 (additive): sphx_render, sphx_render_fit, sphx_render_view, sphx_render_out, SPHX_RENDER_* */
+                            * 5 (additive): sphx_render, sphx_render_fit, sphx_render_view, sphx_render_out, SPHX_RENDER_*
+                            * 5 (additive): sphx_append, sphx_remove, sphx_rect, SPHX_REMOVE_*, sphx_solver_append, sphx_solver_remove */
 
 /* ---- status codes ---- */
 enum {
@@ -158,7 +159,8 @@ int sphx_set_boundary(sphx_ctx* ctx, const float* xy, uint32_t n);
  * rebuilt when the particle count differs from the cached arrays' length (dfsph.rs:419) or after sphx_clear_cached. */
 int sphx_upload(sphx_ctx* ctx, const float* pos_xy, const float* vel_xy, uint32_t n);
 /* Any pointer may be NULL.  Arrays are in the library's current (cell-sorted) order — the reference also re-sorts in
- * place every step (neighborhood_search.rs:121-140).  particle_id[i] = index the particle had in the last sphx_upload. */
+ * place every step (neighborhood_search.rs:121-140).  particle_id[i] = index the particle had in the last sphx_upload, or the id
+ * sphx_append gave it since. */
 int sphx_download(sphx_ctx* ctx, float* pos_xy, float* vel_xy, float* density, uint32_t* particle_id);
 int sphx_download_boundary(sphx_ctx* ctx, float* xy, uint32_t* boundary_id);
 /* Viewer feed (the app draws every particle at its position, coloured by |v|, main.rs:239-258): {x, y, |v|} of
@@ -277,6 +279,46 @@ enum { SPHX_RENDER_DEVICE_POINTERS = 1u }; /* as SPHX_SAMPLE_DEVICE_POINTERS: th
  * for out NULL, a non-finite number, or w / h <= 0. */
 int sphx_render_fit(uint32_t width, uint32_t height, float x, float y, float w, float h, sphx_render_view* out);
 int sphx_render(sphx_ctx* ctx, const sphx_render_view* view, uint32_t flags, const sphx_render_out* out);
+
+/* ---- emitting and draining fluid: the particle set edited on the device (an inflow, an outflow, a keep-box) -----------------------------
+ * The reference can only add (a caller pushes onto the world's Vecs; dfsph.rs:418 "removing this way is impossible with this design") and
+ * carries a stop-gap for "endlessly falling particles" (main.rs:189-192).  Both calls edit the cell-ordered device arrays in place of the
+ * round trip sphx_download, filter / concatenate on the host, sphx_upload.  The contract:
+ *   Predicate (sphx_remove), in fp32 with IEEE comparisons — a NaN coordinate is in no rectangle:
+ *     in(r, p) = p.x >= r.x0 && p.x < r.x1 && p.y >= r.y0 && p.y < r.y1;  hit = in(r, p) for any of the n_rects rectangles.
+ *     A particle is removed iff hit — with SPHX_REMOVE_OUTSIDE iff !hit: the rectangles are then a keep-box, and NaN particles go.
+ *     +-inf bounds are allowed (half planes); x0 > x1 or y0 > y1 is an empty rectangle.  n_rects == 0 removes nothing, or everything with
+ *     SPHX_REMOVE_OUTSIDE.  A NaN bound, n_rects > SPHX_REMOVE_MAX_RECTS, rects NULL with n_rects > 0 or unknown flag bits:
+ *     SPHX_ERR_INVALID_ARGUMENT.
+ *   Remove: the survivors keep their relative (cell-sorted) order; position, velocity and particle_id travel with the particle.  alpha,
+ *     kappa, stiffness, the WCSPH accelerations and density[] are bound to their SLOT and are not moved — what the reference's Vec::resize
+ *     truncation (dfsph.rs:420-422, wscsph.rs:129) and the round trip leave behind.  The density sphx_download returns is unspecified until
+ *     the next step or sphx_update_densities.  N becomes the survivor count (0 is legal); *out_removed (may be NULL) the number removed.
+ *   Append: the m records go to [N, N + m) (vel_xy NULL = zero velocities), with particle_id first_id + k, where first_id = *out_first_id
+ *     (may be NULL) = the number of particles uploaded or appended since the last sphx_upload.  Ids are never reused (removing does not
+ *     free any); running past 2^32 returns SPHX_ERR_CAPACITY.  sphx_upload keeps its meaning (ids 0 .. n - 1) and resets the counter to n.
+ *     When N + m exceeds the allocated capacity the arrays grow by half (at least to N + m) and the present particles are copied on the
+ *     device; sphx_reserve before the upload avoids that.
+ *   Solver caches: both calls leave the cached array length (dfsph.rs:419) alone and mark the particle set as changed; the next
+ *     sphx_step_begin[_law] then runs the warm-up block (dfsph.rs:419-428, SPHX_FLAG_WARMUP) even when the count has come back to the cached
+ *     length (remove k, append k) — the one deliberate difference from the round trip, which would walk the lists of another set there.
+ *     The iteration counts (warm starts) are kept, the WCSPH accelerations as after sphx_upload of the same count.
+ *   Equivalence: apart from the ids and that corner, the state after sphx_append is the state download, concatenate, sphx_upload leaves
+ *     in a context with the same history, the state after sphx_remove the state download, filter, sphx_upload leaves; every later step
+ *     is bit-identical to that context's.
+ *   Nothing removed (or m == 0): the context is untouched — lists, sampling state and a queued run-ahead pass stay valid.
+ *   Something removed or appended: the neighbour lists and the sampling state are stale (sphx_sample_* returns SPHX_ERR_NOT_READY until a
+ *     step or sphx_update_neighborhood + sphx_update_densities); sphx_render and sphx_download work at once on the new set.
+ *   Refusals: SPHX_ERR_NOT_READY between a step_begin and its step_finish (either solver) and before the first sphx_upload (an upload of
+ *     zero particles counts); SPHX_ERR_INVALID_ARGUMENT on a tile context (sphx_tile_*, sphx_multi_tile_ctx: it holds ghosts) and in
+ *     tiling-invariant mode (sphx_set_tiling_invariant).  sphx_multi_* has no counterpart.
+ * Cost: sphx_remove reads 8 bytes per particle for the predicate and moves 40 bytes per survivor only when something goes; one 4-byte
+ * count comes back to the host (the call's only synchronisation).  sphx_append copies the new records and nothing else while they fit. */
+typedef struct sphx_rect { float x0, y0, x1, y1; } sphx_rect; /* [x0, x1) x [y0, y1) in world units */
+#define SPHX_REMOVE_MAX_RECTS 8
+enum { SPHX_REMOVE_OUTSIDE = 1u }; /* remove what is in NO rectangle */
+int sphx_append(sphx_ctx* ctx, const float* pos_xy, const float* vel_xy /* NULL = 0 */, uint32_t m, uint32_t* out_first_id /* may be NULL */);
+int sphx_remove(sphx_ctx* ctx, const sphx_rect* rects, uint32_t n_rects, uint32_t flags, uint32_t* out_removed /* may be NULL */);
 
 /* ---- Solver trait (solver/mod.rs:12-18) ---------------------------------------------------------------------- */
 /* Solver::clear_cached_data (dfsph.rs:406-412) */
@@ -610,6 +652,13 @@ int sphx_solver_simulation_step(sphx_solver* s, sphx_world* w, sphx_timer* t, in
 int sphx_solver_simulation_steps(sphx_solver* s, sphx_world* w, sphx_timer* t, int sync_world, uint32_t k, sphx_step_stats* out_stats,
                                  uint32_t* out_done);
 int sphx_solver_sync_world(sphx_solver* s, sphx_world* w); /* explicit download into the host world */
+/* sphx_append / sphx_remove on the solver's device state, for a caller that holds the solver object: no re-upload follows, ids survive.
+ * Afterwards the host world has the device's particle count; with sync_world != 0 its arrays are downloaded and current, with 0 they are
+ * marked as behind the device (as after a step with sync_world = 0).  SPHX_ERR_NOT_READY before the solver's first step and when the
+ * caller has edited the world's particles since the last step (that edit is waiting for an upload: step first);
+ * SPHX_ERR_INVALID_ARGUMENT on the multi-GPU solver. */
+int sphx_solver_append(sphx_solver* s, sphx_world* w, const float* pos_xy, const float* vel_xy, uint32_t m, int sync_world, uint32_t* out_first_id);
+int sphx_solver_remove(sphx_solver* s, sphx_world* w, const sphx_rect* rects, uint32_t n_rects, uint32_t flags, int sync_world, uint32_t* out_removed);
 sphx_ctx* sphx_solver_ctx(sphx_solver* s);
 const char* sphx_solver_last_error(const sphx_solver* s);
 

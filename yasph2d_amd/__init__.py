@@ -175,6 +175,28 @@ def _elevation(y, f):
     return float(y[k]) + (fk - 0.5) / (fk - fk1) * (float(y[k + 1]) - float(y[k]))
 
 
+def _rect_array(rects):
+    """One (x0, y0, x1, y1) tuple or a sequence of them -> (SphxRect array or None, count)."""
+    r = np.asarray(rects, np.float32)
+    if r.size == 0:
+        return None, 0
+    if r.ndim == 1:
+        r = r[None, :]
+    if r.ndim != 2 or r.shape[1] != 4:
+        raise ValueError("rects must be one (x0, y0, x1, y1) tuple or a sequence of them, not shape %s" % (r.shape,))
+    arr = (_lib.SphxRect * len(r))(*[_lib.SphxRect(*(float(v) for v in row)) for row in r])
+    return arr, len(r)
+
+
+def _append_arrays(pos, vel):
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 2)
+    if vel is not None:
+        vel = np.ascontiguousarray(vel, np.float32).reshape(-1, 2)
+        if len(vel) != len(pos):
+            raise ValueError("vel must have one row per row of pos")
+    return pos, vel
+
+
 class SphxContext:
     """Device solver context (sphx_ctx).  Mirrors DFSPHSolver + the solver-owned part of FluidParticleWorld."""
 
@@ -215,6 +237,21 @@ class SphxContext:
         if vel is not None:
             vel = np.ascontiguousarray(vel, np.float32).reshape(-1, 2)
         self._chk(self.L.sphx_upload(self.h, _p(pos), _p(vel), len(pos)))
+
+    def append(self, pos, vel=None):
+        """sphx_append: add particles behind the present ones on the device (vel None = zero) -> the id of the first new particle."""
+        pos, vel = _append_arrays(pos, vel)
+        first = C.c_uint32()
+        self._chk(self.L.sphx_append(self.h, _p(pos), _p(vel), len(pos), C.byref(first)))
+        return first.value
+
+    def remove(self, rects, outside=False):
+        """sphx_remove: drop the particles inside any of the rectangles (one (x0, y0, x1, y1) tuple or a sequence of them, half-open,
+        bounds may be infinite) — with outside=True those inside none of them (a keep-box) -> the number removed."""
+        arr, k = _rect_array(rects)
+        removed = C.c_uint32()
+        self._chk(self.L.sphx_remove(self.h, arr, k, _lib.REMOVE_OUTSIDE if outside else 0, C.byref(removed)))
+        return removed.value
 
     def clear_cached(self):
         self._chk(self.L.sphx_clear_cached(self.h))
@@ -654,6 +691,25 @@ class DFSPHSolver:
         rc = self.L.sphx_solver_sync_world(self.h, world.h)
         if rc:
             raise SphxError(rc, self.L.sphx_solver_last_error(self.h).decode())
+
+    def append(self, world, pos, vel=None, sync_world=True):
+        """sphx_solver_append: SphxContext.append on the solver's device state; the world follows (sync_world=False: its arrays are
+        only marked as behind the device).  No re-upload follows, ids survive. -> the id of the first new particle."""
+        pos, vel = _append_arrays(pos, vel)
+        first = C.c_uint32()
+        rc = self.L.sphx_solver_append(self.h, world.h, _p(pos), _p(vel), len(pos), int(sync_world), C.byref(first))
+        if rc:
+            raise SphxError(rc, self.L.sphx_solver_last_error(self.h).decode())
+        return first.value
+
+    def remove(self, world, rects, outside=False, sync_world=True):
+        """sphx_solver_remove: SphxContext.remove on the solver's device state; the world follows as in append(). -> the number removed."""
+        arr, k = _rect_array(rects)
+        removed = C.c_uint32()
+        rc = self.L.sphx_solver_remove(self.h, world.h, arr, k, _lib.REMOVE_OUTSIDE if outside else 0, int(sync_world), C.byref(removed))
+        if rc:
+            raise SphxError(rc, self.L.sphx_solver_last_error(self.h).decode())
+        return removed.value
 
     def context(self):
         """Borrowed SphxContext view (for inspection: neighbours, cells, solver state, profiling)."""

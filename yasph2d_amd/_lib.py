@@ -103,6 +103,14 @@ class SphxRenderOut(C.Structure):
     _fields_ = [("rgba", C.c_void_p), ("owner", C.c_void_p)]
 
 
+REMOVE_OUTSIDE = 1  # sphx_remove flags
+REMOVE_MAX_RECTS = 8
+
+
+class SphxRect(C.Structure):
+    _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("x1", C.c_float), ("y1", C.c_float)]
+
+
 class SphxMultiOptions(C.Structure):
     _fields_ = [("halo_cells", C.c_uint32), ("fixed_halo", C.c_uint32), ("rebalance_every", C.c_uint32), ("layout", C.c_uint32),
                 ("cap_records", C.c_uint32), ("overlap_exchange", C.c_uint32), ("reserved", C.c_uint32 * 2)]
@@ -139,6 +147,8 @@ SIGNATURES = {
     "sphx_last_error": (C.c_char_p, [_vp]),
     "sphx_set_boundary": (_i, [_vp, _vp, _u32]),
     "sphx_upload": (_i, [_vp, _vp, _vp, _u32]),
+    "sphx_append": (_i, [_vp, _vp, _vp, _u32, C.POINTER(_u32)]),
+    "sphx_remove": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32, C.POINTER(_u32)]),
     "sphx_download": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "sphx_download_boundary": (_i, [_vp, _vp, _vp]),
     "sphx_num_particles": (_u32, [_vp]),
@@ -263,6 +273,8 @@ SIGNATURES = {
     "sphx_solver_simulation_step": (_i, [_vp, _vp, _vp, _i, C.POINTER(SphxStepStats)]),
     "sphx_solver_simulation_steps": (_i, [_vp, _vp, _vp, _i, _u32, C.POINTER(SphxStepStats), C.POINTER(_u32)]),
     "sphx_solver_sync_world": (_i, [_vp, _vp]),
+    "sphx_solver_append": (_i, [_vp, _vp, _vp, _vp, _u32, _i, C.POINTER(_u32)]),
+    "sphx_solver_remove": (_i, [_vp, _vp, C.POINTER(SphxRect), _u32, _u32, _i, C.POINTER(_u32)]),
     "sphx_solver_ctx": (_vp, [_vp]),
     "sphx_solver_last_error": (C.c_char_p, [_vp]),
 }

@@ -4,6 +4,14 @@
 //   sphx_harness [--solver dfsph|wcsph] [--viscosity xsph|physical[:mu]] [--scale S | --particles N] [--steps K] [--warmup W] [--no-law] [--sync]
 //                [--gauges x1,x2,... [--gauge-range lo:hi:dy]]
 //                [--record DIR [--record-fps F] [--record-size WxH] [--record-min-pixel-radius P]]
+//                [--emit x,y,w,h[:every=K][:until=S][:vel=vx,vy]] [--drain x0,y0,x1,y1]... [--keep x0,y0,x1,y1]...
+//
+// --emit / --drain / --keep: fluid added and removed on the device between the steps (sphx_append / sphx_remove through the solver
+// object).  Steps are counted from 0 over warm-up and timed steps together; the edits come before a step, from step 1 on (step 0 uploads
+// the scene).  --emit appends the block add_fluid_rect(x, y, w, h, 0) makes, with velocity (vx, vy) (default 0), before every K-th step
+// (default 1) below step S (default: all).  --drain removes what is inside its rectangle, --keep what is outside all --keep rectangles,
+// before every step; bounds may be inf / -inf, both options may repeat, 8 rectangles in total.  The JSON line gains "emitted", "drained"
+// and "final_particles" (= particles + emitted - drained).
 //
 // --viscosity: the solver's ViscosityModel (main.rs:93-100): XSPH (default) or PhysicalViscosityModel with fluid_viscosity mu
 // (default 1.0016e-3, physical.rs:14; main.rs:96 sets 0.01).
@@ -76,6 +84,21 @@ static bool gauge_elevation(sph::HipDfsphSolver& solver, double x, double lo, do
     return true;
 }
 
+// `count` comma-separated numbers; a rectangle bound may be infinite, never NaN
+static bool parse_list(const std::string& s, size_t count, bool allow_inf, double* out) {
+    size_t p = 0;
+    for (size_t k = 0; k < count; ++k) {
+        const size_t q = std::min(s.find(',', p), s.size());
+        if (k + 1 < count && q == s.size()) return false;
+        const std::string t = k + 1 == count ? s.substr(p) : s.substr(p, q - p);
+        char* end = nullptr;
+        out[k] = std::strtod(t.c_str(), &end);
+        if (t.empty() || end != t.c_str() + t.size() || std::isnan(out[k]) || (!allow_inf && !std::isfinite(out[k]))) return false;
+        p = q + 1;
+    }
+    return true;
+}
+
 int main(int argc, char** argv) {
     std::string solver_kind = "dfsph";
     float scale = 1.0f;
@@ -86,6 +109,18 @@ int main(int argc, char** argv) {
     bool want_gauges = false, want_range = false;
     std::string record_dir, record_fps_arg, record_size_arg, record_mpr_arg;
     bool want_record = false, want_fps = false, want_size = false, want_mpr = false;
+    std::string emit_arg;
+    bool want_emit = false;
+    std::vector<sphx_rect> drain_rects, keep_rects;
+    auto add_rect = [&](std::vector<sphx_rect>& to, const char* opt, const std::string& arg) {
+        double v[4];
+        if (!parse_list(arg, 4, true, v) || drain_rects.size() + keep_rects.size() >= SPHX_REMOVE_MAX_RECTS) {
+            std::fprintf(stderr, "invalid %s %s (x0,y0,x1,y1; inf allowed; at most %d rectangles in --drain and --keep together)\n", opt, arg.c_str(),
+                         SPHX_REMOVE_MAX_RECTS);
+            std::exit(2);
+        }
+        to.push_back(sphx_rect{(float)v[0], (float)v[1], (float)v[2], (float)v[3]});
+    };
     for (int a = 1; a < argc; ++a) {
         const std::string s = argv[a];
         auto next = [&]() -> const char* { return a + 1 < argc ? argv[++a] : "0"; };
@@ -103,6 +138,9 @@ int main(int argc, char** argv) {
         else if (s == "--record-fps") record_fps_arg = next(), want_fps = true;
         else if (s == "--record-size") record_size_arg = next(), want_size = true;
         else if (s == "--record-min-pixel-radius") record_mpr_arg = next(), want_mpr = true;
+        else if (s == "--emit") emit_arg = next(), want_emit = true;
+        else if (s == "--drain") add_rect(drain_rects, "--drain", next());
+        else if (s == "--keep") add_rect(keep_rects, "--keep", next());
         else {
             std::fprintf(stderr, "unknown argument %s\n", s.c_str());
             return 2;
@@ -157,6 +195,33 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    std::vector<sph::Point> emit_pos;
+    std::vector<sph::Vector> emit_vel;
+    long emit_every = 1, emit_until = -1;
+    if (want_emit) {
+        double r[4], vel[2] = {0.0, 0.0}, num;
+        bool ok = true;
+        size_t p = std::min(emit_arg.find(':'), emit_arg.size());
+        ok = parse_list(emit_arg.substr(0, p), 4, false, r) && r[2] > 0.0 && r[3] > 0.0;
+        while (ok && p < emit_arg.size()) {
+            const size_t q = std::min(emit_arg.find(':', p + 1), emit_arg.size());
+            const std::string opt = emit_arg.substr(p + 1, q - p - 1);
+            if (opt.rfind("every=", 0) == 0) ok = parse_double(opt.substr(6), &num) && num >= 1.0 && num == std::floor(num) && num < 1e9, emit_every = ok ? (long)num : 1;
+            else if (opt.rfind("until=", 0) == 0) ok = parse_double(opt.substr(6), &num) && num >= 0.0 && num == std::floor(num) && num < 1e15, emit_until = ok ? (long)num : -1;
+            else if (opt.rfind("vel=", 0) == 0) ok = parse_list(opt.substr(4), 2, false, vel);
+            else ok = false;
+            p = q;
+        }
+        if (!ok) {
+            std::fprintf(stderr, "invalid --emit %s (x,y,w,h[:every=K][:until=S][:vel=vx,vy], finite, w, h > 0, K >= 1)\n", emit_arg.c_str());
+            return 2;
+        }
+        sph::FluidParticleWorld block(2.0f, 10000.0f, 100.0f);
+        block.add_fluid_rect((float)r[0], (float)r[1], (float)r[2], (float)r[3], 0.0f);
+        emit_pos = block.particles.positions;
+        emit_vel.assign(emit_pos.size(), sph::Vector{(float)vel[0], (float)vel[1]});
+    }
+    const bool want_edit = want_emit || !drain_rects.empty() || !keep_rects.empty();
     sphx_params params = sph::HipDfsphSolver::params_of(world, nullptr);
     {
         const size_t colon = viscosity.find(':');
@@ -225,7 +290,32 @@ int main(int argc, char** argv) {
             }
         }
     };
+    unsigned long long emitted = 0, drained = 0;
+    long step_index = 0;
+    auto edit = [&]() {  // before step `step_index` (>= 1: the device holds the scene)
+        auto check = [&](int rc, const char* what) {
+            if (rc != SPHX_OK) {
+                std::fprintf(stderr, "%s failed: %s (status %d)\n", what, solver->last_error.c_str(), rc);
+                std::exit(1);
+            }
+        };
+        if (want_emit && !emit_pos.empty() && step_index % emit_every == 0 && (emit_until < 0 || step_index < emit_until)) {
+            check(solver->append(world, &emit_pos[0].x, &emit_vel[0].x, (uint32_t)emit_pos.size(), sync, nullptr), "--emit");
+            emitted += emit_pos.size();
+        }
+        uint32_t gone = 0;
+        if (!drain_rects.empty()) {
+            check(solver->remove(world, drain_rects.data(), (uint32_t)drain_rects.size(), 0u, sync, &gone), "--drain");
+            drained += gone;
+        }
+        if (!keep_rects.empty()) {
+            check(solver->remove(world, keep_rects.data(), (uint32_t)keep_rects.size(), SPHX_REMOVE_OUTSIDE, sync, &gone), "--keep");
+            drained += gone;
+        }
+    };
     auto step = [&]() {
+        if (want_edit && step_index > 0) edit();
+        ++step_index;
         if (want_record) record_due_frames();
         tm.on_step_started();
         solver->simulation_step(world, tm);
@@ -247,8 +337,9 @@ int main(int argc, char** argv) {
     const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (solver->sync_world(world) != SPHX_OK) return 1;
     // order-independent content check: positions/velocities placed at their persistent particle id
-    std::vector<float> by_id(4 * n, 0.0f);
-    for (size_t i = 0; i < n; ++i) {
+    const size_t n_final = world.particles.positions.size();  // (== n unless --emit / --drain / --keep edited the set; ids < n + emitted)
+    std::vector<float> by_id(4 * (n + emitted), 0.0f);
+    for (size_t i = 0; i < n_final; ++i) {
         const uint32_t id = world.particles.particle_ids[i];
         by_id[4 * id + 0] = world.particles.positions[i].x;
         by_id[4 * id + 1] = world.particles.positions[i].y;
@@ -276,6 +367,11 @@ int main(int argc, char** argv) {
     if (want_record) {
         char buf[96];
         std::snprintf(buf, sizeof(buf), ", \"frames\": %llu, \"last_frame_fnv\": \"%016llx\"", (unsigned long long)frames, (unsigned long long)last_frame_fnv);
+        gauge_json += buf;
+    }
+    if (want_edit) {
+        char buf[128];
+        std::snprintf(buf, sizeof(buf), ", \"emitted\": %llu, \"drained\": %llu, \"final_particles\": %zu", emitted, drained, n_final);
         gauge_json += buf;
     }
     std::printf("{\"solver\": \"%s\", \"viscosity\": \"%s\", \"fluid_viscosity\": %.9g, \"particles\": %zu, \"boundary\": %zu, \"steps\": %ld, \"particle_steps_per_s\": %.6e, \"ms_per_step\": %.6f, "

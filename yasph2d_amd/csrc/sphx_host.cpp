@@ -434,6 +434,48 @@ int HipDfsphSolver::sync_world(FluidParticleWorld& w) {
     return rc;
 }
 
+// ---- sphx_append / sphx_remove behind the solver object ---------------------------------------------------------------------------
+int HipDfsphSolver::edit_ready(const FluidParticleWorld& w) {
+    if (!ctx_) return last_status = SPHX_ERR_NO_DEVICE;
+    if (uploaded_n_ == (size_t)-1 || w.particles.positions.size() != uploaded_n_ || w.fluid_generation != uploaded_generation_) {
+        last_error = uploaded_n_ == (size_t)-1 ? "append / remove before the solver's first step: the device holds no state of this world yet"
+                                                : "the host world was edited since the last step: step (or sync_world) before append / remove";
+        return last_status = SPHX_ERR_NOT_READY;
+    }
+    return SPHX_OK;
+}
+int HipDfsphSolver::edit_done(FluidParticleWorld& w, bool sync, int rc) {
+    if (rc) {
+        last_error = sphx_last_error(ctx_);
+        return last_status = rc;
+    }
+    const size_t n = sphx_num_particles(ctx_);
+    if (sync) {
+        if ((rc = sync_world(w))) {
+            last_error = sphx_last_error(ctx_);
+            return last_status = rc;
+        }
+    } else {
+        // the count follows the device, the contents are behind it (as after a headless step): the next simulation_step does not upload
+        w.particles.positions.resize(n);
+        w.particles.velocities.resize(n, Vector{0, 0});
+        w.particles.densities.resize(n, 0.0f);
+        w.particles.particle_ids.clear();
+        w.stale_prefix = n;
+        uploaded_n_ = n;
+        uploaded_generation_ = w.fluid_generation;
+    }
+    return last_status = SPHX_OK;
+}
+int HipDfsphSolver::append(FluidParticleWorld& w, const float* pos_xy, const float* vel_xy, uint32_t m, bool sync, uint32_t* out_first_id) {
+    if (int rc = edit_ready(w)) return rc;
+    return edit_done(w, sync, sphx_append(ctx_, pos_xy, vel_xy, m, out_first_id));
+}
+int HipDfsphSolver::remove(FluidParticleWorld& w, const sphx_rect* rects, uint32_t n_rects, uint32_t flags, bool sync, uint32_t* out_removed) {
+    if (int rc = edit_ready(w)) return rc;
+    return edit_done(w, sync, sphx_remove(ctx_, rects, n_rects, flags, out_removed));
+}
+
 }  // namespace sph
 
 // =====================================================================================================================
@@ -603,6 +645,14 @@ int sphx_solver_simulation_steps(sphx_solver* s, sphx_world* w, sphx_timer* t, i
     return SPHX_OK;
 }
 int sphx_solver_sync_world(sphx_solver* s, sphx_world* w) { return s->s.sync_world(w->w); }
+int sphx_solver_append(sphx_solver* s, sphx_world* w, const float* pos_xy, const float* vel_xy, uint32_t m, int sync_world, uint32_t* out_first_id) {
+    if (!s || !w) return SPHX_ERR_INVALID_ARGUMENT;
+    return s->s.append(w->w, pos_xy, vel_xy, m, sync_world != 0, out_first_id);
+}
+int sphx_solver_remove(sphx_solver* s, sphx_world* w, const sphx_rect* rects, uint32_t n_rects, uint32_t flags, int sync_world, uint32_t* out_removed) {
+    if (!s || !w) return SPHX_ERR_INVALID_ARGUMENT;
+    return s->s.remove(w->w, rects, n_rects, flags, sync_world != 0, out_removed);
+}
 sphx_ctx* sphx_solver_ctx(sphx_solver* s) { return s->s.ctx(); }
 const char* sphx_solver_last_error(const sphx_solver* s) { return s->s.last_error.c_str(); }
 

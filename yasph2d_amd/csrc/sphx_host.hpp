@@ -132,6 +132,11 @@ class HipDfsphSolver : public Solver {
     void clear_cached_data() override;
     void simulation_step(FluidParticleWorld& fluid_world, TimeManager& time_manager) override;
     virtual int sync_world(FluidParticleWorld& fluid_world);  // download positions/velocities/densities into the host world
+    // sphx_append / sphx_remove on the device state (the contract is in sphx.h): no re-upload follows and ids survive.  The host world
+    // gets the device's count; sync: its arrays are downloaded, else they are marked as behind the device.  SPHX_ERR_NOT_READY before the
+    // first step and when the caller has edited the world's particles since the last one.
+    virtual int append(FluidParticleWorld& fluid_world, const float* pos_xy, const float* vel_xy, uint32_t m, bool sync, uint32_t* out_first_id);
+    virtual int remove(FluidParticleWorld& fluid_world, const sphx_rect* rects, uint32_t n_rects, uint32_t flags, bool sync, uint32_t* out_removed);
 
     bool sync_every_step = true;   // main.rs draws from the host arrays after each step
     bool use_timer_law = true;     // sphx_step_begin_law: the device derives dt itself, the host only verifies it
@@ -158,6 +163,8 @@ class HipDfsphSolver : public Solver {
     explicit HipDfsphSolver(NoContext) {}  // for solvers that hold their device state elsewhere (HipDfsphMultiSolver)
     virtual int device_step(FluidParticleWorld& fluid_world, TimeManager& time_manager);  // the two-phase step on the device
     sphx_ctx* ctx_ = nullptr;
+    int edit_ready(const FluidParticleWorld& fluid_world);             // may the device state be edited behind the world's back?
+    int edit_done(FluidParticleWorld& fluid_world, bool sync, int rc);  // the world follows the device's count
 
    private:
     uint64_t uploaded_generation_ = 0;
@@ -176,9 +183,15 @@ class HipDfsphMultiSolver : public HipDfsphSolver {
     void clear_cached_data() override;
     void simulation_step(FluidParticleWorld& fluid_world, TimeManager& time_manager) override;
     int sync_world(FluidParticleWorld& fluid_world) override;
+    int append(FluidParticleWorld&, const float*, const float*, uint32_t, bool, uint32_t*) override { return no_edit(); }
+    int remove(FluidParticleWorld&, const sphx_rect*, uint32_t, uint32_t, bool, uint32_t*) override { return no_edit(); }
     sphx_multi* multi() { return multi_; }
 
    private:
+    int no_edit() {
+        last_error = "append / remove are not available on the multi-GPU solver";
+        return last_status = SPHX_ERR_INVALID_ARGUMENT;
+    }
     sphx_multi* multi_ = nullptr;
     uint64_t uploaded_generation_ = 0;
     size_t uploaded_n_ = (size_t)-1;

@@ -303,6 +303,12 @@ struct sphx_ctx {
     uint32_t N = 0, capN = 0;  // fluid particles
     uint32_t B = 0, capB = 0;  // boundary particles
     uint32_t cached_n = 0;     // alpha_values.len() of the reference (dfsph.rs:419)
+    // sphx_append / sphx_remove (sphx_edit.inc) changed the particle set: the next sphx_step_begin runs the warm-up block even when the
+    // count has come back to cached_n (the lists belong to another set).  Cleared by that warm-up and by sphx_upload.
+    bool set_changed = false;
+    uint64_t ids_issued = 0;   // particles uploaded or appended since the last sphx_upload: the first id sphx_append hands out
+    uint32_t* edit_buf = nullptr;  // sphx_remove: survivors per workgroup, then their exclusive scan and the total; grown on demand
+    uint32_t edit_cap = 0;         // ... in 4-byte words
     bool uploaded = false, boundary_changed = true, tails_dirty = true, in_step = false;
     uint32_t fast_walk_ok = 0;  // this smoothing length allows the FAST walks (sqrt_dist); K.q_noclamp = fast_walk_ok while the lists are fresh
     // field sampling (sphx_sample_*): 2 = the cell grids and density[] belong to the current positions (a build plus densities), 1 = a

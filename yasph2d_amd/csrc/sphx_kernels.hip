@@ -3222,3 +3222,5 @@ __global__ __launch_bounds__(64) void k_publish(DevScalars* scal, Mailbox* mb, u
 #include "sphx_sample.inc"
 // the particles drawn as discs into an image (kernels + C ABI)
 #include "sphx_render.inc"
+// fluid appended to and removed from the device state between steps (kernels + C ABI)
+#include "sphx_edit.inc"

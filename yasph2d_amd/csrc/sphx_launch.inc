@@ -998,14 +998,18 @@ void launch_density(sphx_ctx* c, bool density, bool alpha) {
         });
 }
 
-int alloc_particles(sphx_ctx* c, uint32_t n) {
+// cap: the capacity to allocate when n does not fit (0: exactly n).  keep_set (sphx_append): positions, velocities and ids of [0, N)
+// survive the reallocation too.
+int alloc_particles(sphx_ctx* c, uint32_t n, uint32_t cap = 0, bool keep_set = false) {
     if (n <= c->capN) return SPHX_OK;
-    const uint32_t cap = n;
+    cap = std::max(cap, n);
     int rc = 0;
-    if ((rc = ensure_nb_arrays(c, cap, c->capB, false))) return rc;
+    if ((rc = ensure_nb_arrays(c, cap, c->capB, keep_set))) return rc;
     // keep the slot-wise warm-start values of the reference's Vec::resize (dfsph.rs:420-422)
     float *old_kappa = c->kappa, *old_stiff = c->stiff, *old_alpha = c->alpha;
     float2* old_accel = c->accel;  // WCSPH: `accellerations` is slot-bound too (Vec::resize, wscsph.rs:129)
+    uint32_t* old_pid = keep_set ? c->pid : nullptr;
+    if (keep_set) c->pid = nullptr;
     const uint32_t keep = std::min(c->cached_n, c->capN);
     const uint32_t keep_accel = std::min(c->wcsph_n, c->capN);
     c->kappa = c->stiff = c->alpha = nullptr;
@@ -1015,6 +1019,7 @@ int alloc_particles(sphx_ctx* c, uint32_t n) {
         dev_free(&old_stiff);
         dev_free(&old_alpha);
         dev_free(&old_accel);
+        dev_free(&old_pid);
         c->cached_n = 0;
         c->wcsph_n = 0;
         c->uploaded = false;
@@ -1038,11 +1043,13 @@ int alloc_particles(sphx_ctx* c, uint32_t n) {
         SPHX_HIP(c, hipMemcpyAsync(c->alpha, old_alpha, (size_t)keep * 4, hipMemcpyDeviceToDevice, c->stream));
     }
     if (keep_accel) SPHX_HIP(c, hipMemcpyAsync(c->accel, old_accel, (size_t)keep_accel * 8, hipMemcpyDeviceToDevice, c->stream));
+    if (old_pid && c->N) SPHX_HIP(c, hipMemcpyAsync(c->pid, old_pid, (size_t)c->N * 4, hipMemcpyDeviceToDevice, c->stream));
     SPHX_HIP(c, hipStreamSynchronize(c->stream));
     dev_free(&old_kappa);
     dev_free(&old_stiff);
     dev_free(&old_alpha);
     dev_free(&old_accel);
+    dev_free(&old_pid);
     c->capN = cap;
     return SPHX_OK;
 }
@@ -1553,7 +1560,7 @@ void sphx_destroy(sphx_ctx* c) {
     dev_free(&c->density); dev_free(&c->alpha); dev_free(&c->alpha2); dev_free(&c->kappa); dev_free(&c->stiff); dev_free(&c->kappa2); dev_free(&c->stiff2);
     dev_free(&c->pid); dev_free(&c->pid2); dev_free(&c->key); dev_free(&c->slot); dev_free(&c->order);
     dev_free(&c->bpos); dev_free(&c->bpos2); dev_free(&c->bid); dev_free(&c->bid2); dev_free(&c->nb_list); dev_free(&c->nb_wave); dev_free(&c->nb_counts); dev_free(&c->nb_remote);
-    dev_free(&c->scan_partials); dev_free(&c->scan_state); dev_free(&c->d_scal); dev_free(&c->tile_blk); dev_free(&c->sample_buf); dev_free(&c->render_buf);
+    dev_free(&c->scan_partials); dev_free(&c->scan_state); dev_free(&c->d_scal); dev_free(&c->tile_blk); dev_free(&c->sample_buf); dev_free(&c->render_buf); dev_free(&c->edit_buf);
     free_grid(c->gdyn);
     free_grid(c->gstat);
     if (c->mbox) hipHostFree((void*)c->mbox);
@@ -1645,6 +1652,8 @@ int sphx_upload(sphx_ctx* c, const float* pos_xy, const float* vel_xy, uint32_t 
     int rc;
     if ((rc = alloc_particles(c, n))) return rc;
     c->N = n;
+    c->ids_issued = n;  // particle_id = index in this upload; sphx_append continues from here
+    c->set_changed = false;
     lists_went_stale(c);
     if (n) {
         SPHX_HIP(c, hipMemcpyAsync(c->posA, pos_xy, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
@@ -1735,7 +1744,8 @@ int sphx_step_begin_law(sphx_ctx* c, float dt_prev, const sphx_timer_law* law, f
     c->law_active = false;
     const uint32_t n = c->N;
     int rc;
-    if (c->cached_n != n) {  // warm-up, dfsph.rs:419-428
+    if (c->cached_n != n || c->set_changed) {  // warm-up, dfsph.rs:419-428 (set_changed: sphx_append / sphx_remove since the last one)
+        c->set_changed = false;
         if (n > c->cached_n) {
             const uint32_t add = n - c->cached_n;
             for (float* a : {c->alpha, c->kappa, c->stiff})
