@@ -18,7 +18,7 @@
  * What is the contract and what is scaffolding (the header has grown beyond the boundary SURVEY.md 8(b) asks for):
  *   STABLE — the drop-in boundary a Rust shim binds:
  *       lifecycle (sphx_default_params, sphx_create, sphx_destroy, sphx_last_error, sphx_abi_version), the particle-array
- *       surface (sphx_set_boundary, sphx_upload, sphx_append, sphx_remove, sphx_download*, sphx_num_*, sphx_view_*, sphx_sample_*, sphx_render*), the Solver trait (sphx_clear_cached,
+ *       surface (sphx_set_boundary, sphx_upload, sphx_append, sphx_remove, sphx_download*, sphx_num_*, sphx_view_*, sphx_sample_*, sphx_render*, sphx_state_*), the Solver trait (sphx_clear_cached,
  *       sphx_step_begin[_law], sphx_step_finish, sphx_wcsph_step_*), the same trait over a device list (sphx_multi_create[_rank],
  *       sphx_multi_destroy, sphx_multi_set_boundary, sphx_multi_upload, sphx_multi_clear_cached, sphx_multi_step_begin/finish,
  *       sphx_multi_simulation_step[s], sphx_multi_download, sphx_multi_num_owned, sphx_multi_last_error, sphx_comm_ops) and
@@ -54,7 +54,9 @@ extern "C" {
                             *    before), SPHX_VISCOSITY_*, sphx_get_viscosity
                             * 5 (additive): sphx_sample_points, sphx_sample_grid, sphx_sample_out, SPHX_SAMPLE_DEVICE_POINTERS
                             * 5 (additive): sphx_render, sphx_render_fit, sphx_render_view, sphx_render_out, SPHX_RENDER_*
-                            * 5 (additive): sphx_append, sphx_remove, sphx_rect, SPHX_REMOVE_*, sphx_solver_append, sphx_solver_remove */
+                            * 5 (additive): sphx_append, sphx_remove, sphx_rect, SPHX_REMOVE_*, sphx_solver_append, sphx_solver_remove
+                            * 5 (additive): sphx_state_size / _save / _load / _digest / _save_file / _load_file, SPHX_STATE_*, sphx_timer_state,
+                            *    sphx_timer_get_state / _set_state, sphx_solver_save / _load */
 
 /* ---- status codes ---- */
 enum {
@@ -319,6 +321,65 @@ typedef struct sphx_rect { float x0, y0, x1, y1; } sphx_rect; /* [x0, x1) x [y0,
 enum { SPHX_REMOVE_OUTSIDE = 1u }; /* remove what is in NO rectangle */
 int sphx_append(sphx_ctx* ctx, const float* pos_xy, const float* vel_xy /* NULL = 0 */, uint32_t m, uint32_t* out_first_id /* may be NULL */);
 int sphx_remove(sphx_ctx* ctx, const sphx_rect* rects, uint32_t n_rects, uint32_t flags, uint32_t* out_removed /* may be NULL */);
+
+/* ---- saving and restoring a context: a run that can be put down and picked up (restart files, roll-back, late-window measurements) --------
+ * sphx_state_save writes everything a later step of this context can read into one self-describing blob; sphx_state_load puts it back, into
+ * this context, a fresh one or one in another process.  The promise: a context that loads a blob and then receives the calls the saving
+ * context received after the save produces the same bits — every sphx_step_stats field, every array and neighbour list, every sample and
+ * render — as long as neither run raises SPHX_FLAG_STRAY_PARTICLES or SPHX_FLAG_DENSE_CELL (the covered region is derived again at load;
+ * the order inside a dense cell was never deterministic).  Save only reads: a run with saves between its steps is bit-identical to one
+ * without (a queued run-ahead pass stays valid).
+ * The blob (little-endian; the byte-exact layout is the comment at the top of csrc/sphx_state_format.hpp, which also holds its validation
+ * as plain host C++): a fixed header — magic, format version, endianness tag, total size —, the sphx_params of the context (device stored
+ * as 0), the scalars N, B, cached_n (dfsph.rs:419), wcsph_n, ids_issued (sphx_append), the two iteration counts behind the warm starts
+ * (dfsph.rs:199 / :354), and the flags "particle set changed" (sphx_append / sphx_remove), tiling-invariant mode, "the neighbour lists belong
+ * to the positions" and "sampling allowed"; a table of {offset, bytes, digest} per section and a digest of the header itself; then the SPHX_STATE_SECTIONS sections, 8-byte
+ * aligned, padding zero: positions, velocities and particle_id of the N particles in device order (sphx_download), density[N], the slot-bound
+ * alpha, kappa and stiffness for the first min(N, cached_n) slots (sphx_download_solver_state), the WCSPH accelerations accel[wcsph_n], and
+ * the boundary in CALLER order (as given to sphx_set_boundary).  No timestamp, no pointer, no capacity: two saves of one state are
+ * byte-identical.  Neighbour lists, cell grids, the covered region and scratch are not stored: they are functions of what is.
+ * Section digest: the section as W 32-bit words w[0 .. W), all arithmetic mod 2^64 with a 64-bit word index i:
+ *     digest = sum_i (uint64)w[i] * ((2 i + 1) * 0x9E3779B97F4A7C15)  +  W * 0xD6E8FEB86659FD93
+ *   position-weighted (swapped words change it) and independent of the order of accumulation, so the device computes it in one streaming
+ *   pass and the host reproduces it exactly.  An INTEGRITY CHECK and a fingerprint — NOT a cryptographic hash: it detects damage and lets
+ *   two runs be compared by 8 bytes per array, it does not resist someone who wants a collision.
+ *   sphx_state_digest: the digests of the LIVE state, out[SPHX_STATE_SEC_*] (72 bytes come back; nothing else is downloaded).  Save stores
+ *   the same numbers in the table; load recomputes them on the device after the copy and compares.
+ * Load validates on the host first — magic, version, endianness, sizes, section bounds and overlaps, every count against every other, and
+ *   the params: every field except device and list_span_limit must equal this context's bit for bit (the message names the first that does
+ *   not); a blob saved in tiling-invariant mode loads only into a context in that mode and the other way round.  A refusal at this stage is
+ *   SPHX_ERR_INVALID_ARGUMENT and leaves the context UNTOUCHED.  Then load allocates as sphx_upload does (an earlier sphx_reserve holds),
+ *   installs the boundary and the arrays in the saved order, zero-fills the slot-bound slots the blob does not hold, sets the scalars and
+ *   drops a queued run-ahead pass.  If the lists were current at save it runs ONE neighbour build — not a step: it raises no flag and
+ *   computes neither density nor alpha, and since a re-grid of an already sorted set is the identity the arrays stay as loaded — so that the
+ *   next sphx_step_begin finds what the saving context had; if sampling was allowed at save it is allowed after load.  A digest that does
+ *   not match after the copy: SPHX_ERR_INVALID_ARGUMENT naming the section; the context then asks for an upload or a load (every step call
+ *   returns SPHX_ERR_NOT_READY), as after a failed step.  A malformed blob never faults: no count is used before it has been checked.
+ *   One deliberate difference: a blob whose lists were NOT current although the next step would have walked them (sphx_upload of the cached
+ *   count without sphx_clear_cached: the reference walks stale lists there, dfsph.rs:419) loads with the "set changed" mark, i.e. the next
+ *   step runs the warm-up block — stale lists are not state anybody can restore.
+ * SPHX_STATE_DEVICE_BUFFER: buf is device memory on the context's device; the sections are copied device-to-device (the header, the
+ *   positions and the boundary also cross to the host: the 392-byte header on save; on load the host derives the covered region from the positions
+ *   and keeps the boundary's caller order).  The call returns when buf is complete (save) or no longer needed (load).
+ * When allowed: save wherever sphx_download is; save and digest return SPHX_ERR_NOT_READY before the first upload or load and after a
+ *   failed step; save, load and digest return SPHX_ERR_NOT_READY between a step_begin and its step_finish (either solver); load is allowed
+ *   on any context outside a step.  A tile context (sphx_tile_*, sphx_multi_tile_ctx): SPHX_ERR_INVALID_ARGUMENT.  A capacity smaller than
+ *   sphx_state_size: SPHX_ERR_CAPACITY with the needed size in *out_bytes (out_bytes may be NULL).  sphx_multi_* has NO counterpart yet: a
+ *   multi-GPU run cannot be saved (sphx_solver_save on the multi-GPU solver object: SPHX_ERR_INVALID_ARGUMENT).
+ * Files: sphx_state_save_file writes exactly the blob (to path + ".tmp", renamed when complete), sphx_state_load_file reads one; an I/O
+ *   failure is SPHX_ERR_INVALID_ARGUMENT with errno's text. */
+#define SPHX_STATE_SECTIONS 9
+enum {
+    SPHX_STATE_SEC_POSITIONS = 0, SPHX_STATE_SEC_VELOCITIES = 1, SPHX_STATE_SEC_PARTICLE_ID = 2, SPHX_STATE_SEC_DENSITY = 3, SPHX_STATE_SEC_ALPHA = 4,
+    SPHX_STATE_SEC_KAPPA = 5, SPHX_STATE_SEC_STIFFNESS = 6, SPHX_STATE_SEC_ACCEL = 7, SPHX_STATE_SEC_BOUNDARY = 8
+};
+enum { SPHX_STATE_DEVICE_BUFFER = 1u };
+int sphx_state_size(sphx_ctx* ctx, uint64_t* out_bytes);
+int sphx_state_save(sphx_ctx* ctx, void* buf, uint64_t capacity, uint32_t flags, uint64_t* out_bytes /* may be NULL */);
+int sphx_state_load(sphx_ctx* ctx, const void* buf, uint64_t bytes, uint32_t flags);
+int sphx_state_digest(sphx_ctx* ctx, uint64_t* out /* [SPHX_STATE_SECTIONS] */);
+int sphx_state_save_file(sphx_ctx* ctx, const char* path);
+int sphx_state_load_file(sphx_ctx* ctx, const char* path);
 
 /* ---- Solver trait (solver/mod.rs:12-18) ---------------------------------------------------------------------- */
 /* Solver::clear_cached_data (dfsph.rs:406-412) */
@@ -633,6 +694,20 @@ uint32_t sphx_timer_num_steps(const sphx_timer* t);
 int sphx_timer_law_of(const sphx_timer* t, float particle_diameter, sphx_timer_law* out); /* fills sphx_timer_law from the mirror */
 void sphx_timer_set_target_frame(sphx_timer* t, uint64_t target_ns); /* AdaptiveTimeStepTarget::TargetFrameLength, timemanager.rs:24-36; 0 = None */
 void sphx_timer_on_step_started(sphx_timer* t);                      /* the clock part of simulation_frame_loop, timemanager.rs:244-247 */
+/* Everything the TimeManager mirror holds (timemanager.rs:72-92, simulation-step part), as one POD: a timer given the state of another
+ * continues exactly as that one would.  sphx_timer_set_state: SPHX_ERR_INVALID_ARGUMENT for NULL, fixed > 1, reserved != 0 or a NaN factor. */
+typedef struct sphx_timer_state {
+    uint32_t fixed;                     /* SimulationStepConfig::Fixed (1) or ::Adaptive (0) */
+    float cfl_factor;
+    uint64_t timestep_max_ns, timestep_min_ns;
+    uint64_t simulation_step_ns;        /* TimeManager::simulation_step() */
+    uint64_t timestep_target_frame_ns;  /* AdaptiveTimeStepTarget::TargetFrameLength; 0 = None */
+    uint64_t total_simulated_ns;
+    uint32_t num_simulation_steps;
+    uint32_t reserved;                  /* 0 */
+} sphx_timer_state;                     /* 56 bytes */
+int sphx_timer_get_state(const sphx_timer* t, sphx_timer_state* out);
+int sphx_timer_set_state(sphx_timer* t, const sphx_timer_state* state);
 
 /* DFSPHSolver::new(XSPHViscosityModel::new(h), h) boxed as dyn Solver (main.rs:93-101).  `params` may be NULL (defaults from the world). */
 int sphx_solver_create_dfsph(const sphx_world* w, const sphx_params* params, sphx_solver** out);
@@ -659,6 +734,16 @@ int sphx_solver_sync_world(sphx_solver* s, sphx_world* w); /* explicit download 
  * SPHX_ERR_INVALID_ARGUMENT on the multi-GPU solver. */
 int sphx_solver_append(sphx_solver* s, sphx_world* w, const float* pos_xy, const float* vel_xy, uint32_t m, int sync_world, uint32_t* out_first_id);
 int sphx_solver_remove(sphx_solver* s, sphx_world* w, const sphx_rect* rects, uint32_t n_rects, uint32_t flags, int sync_world, uint32_t* out_removed);
+/* A run behind the solver object, put down and picked up: ONE file holding an 80-byte header ("SPHXSOLV", version, endianness tag, the
+ * blob's size, the sphx_timer_state of t) and the context's blob (sphx_state_save).  sphx_solver_save: SPHX_ERR_NOT_READY before the
+ * solver's first step and when the caller has edited the world's particles since the last step (the device does not hold that world yet).
+ * sphx_solver_load: the file is validated as a whole before anything changes (sphx_state_load's rules; the timer state too); afterwards t
+ * holds the saved timer state, the host world the saved boundary (caller order) and the device's particle count; its particle arrays are
+ * marked as behind the device (as after a step with sync_world = 0: sphx_solver_sync_world fetches them) and the next
+ * sphx_solver_simulation_step uploads nothing.  The world's fluid properties are not in the file: load into a world created like the saved
+ * one (the params check refuses a context that differs).  SPHX_ERR_INVALID_ARGUMENT on the multi-GPU solver and for I/O failures. */
+int sphx_solver_save(sphx_solver* s, sphx_world* w, sphx_timer* t, const char* path);
+int sphx_solver_load(sphx_solver* s, sphx_world* w, sphx_timer* t, const char* path);
 sphx_ctx* sphx_solver_ctx(sphx_solver* s);
 const char* sphx_solver_last_error(const sphx_solver* s);
 

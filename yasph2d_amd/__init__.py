@@ -477,6 +477,66 @@ class SphxContext:
         self._chk(self.L.sphx_render(self.h, C.byref(view), 0, C.byref(o)))
         return own if not rgba else ((img, own) if owner else img)
 
+    def state_size(self):
+        """sphx_state_size: bytes of the blob save_state() would write now."""
+        n = C.c_uint64()
+        self._chk(self.L.sphx_state_size(self.h, C.byref(n)))
+        return n.value
+
+    def save_state(self, device=False):
+        """sphx_state_save: everything a later step can read, as one blob (the contract is in include/sphx.h).
+
+        -> a numpy uint8 array; with device=True a torch uint8 tensor on the context's device (the sections are copied device to
+        device).  Like sample() and render(), the device path synchronises torch's current stream before the call; the library waits
+        for its own stream before it returns, so the tensor is complete."""
+        size = self.state_size()
+        done = C.c_uint64()
+        if device:
+            import torch
+
+            dev = torch.device("cuda", self.params.device if self.params is not None else torch.cuda.current_device())
+            blob = torch.empty(size, dtype=torch.uint8, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            self._chk(self.L.sphx_state_save(self.h, C.c_void_p(blob.data_ptr()), size, _lib.STATE_DEVICE_BUFFER, C.byref(done)))
+        else:
+            blob = np.empty(size, np.uint8)
+            self._chk(self.L.sphx_state_save(self.h, _p(blob), size, 0, C.byref(done)))
+        assert done.value == size
+        return blob
+
+    def load_state(self, blob):
+        """sphx_state_load: blob = bytes / bytearray / memoryview, a numpy uint8 array, or a torch uint8 tensor (a cuda tensor on the
+        context's device takes the device path: torch's current stream is synchronised first, and the library is done with the tensor
+        when the call returns)."""
+        if _is_torch(blob):
+            import torch
+
+            if blob.dtype != torch.uint8 or blob.dim() != 1:
+                raise ValueError("blob must be a 1-D uint8 tensor")
+            if blob.device.type == "cuda":
+                if self.params is not None and blob.device.index not in (None, self.params.device):
+                    raise ValueError("blob is on %s, the context on device %d" % (blob.device, self.params.device))
+                t = blob.contiguous()
+                torch.cuda.current_stream(t.device).synchronize()
+                self._chk(self.L.sphx_state_load(self.h, C.c_void_p(t.data_ptr() or 1), t.numel(), _lib.STATE_DEVICE_BUFFER))
+                return
+            blob = blob.numpy()
+        a = np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else np.ascontiguousarray(blob, np.uint8).reshape(-1)
+        self._chk(self.L.sphx_state_load(self.h, C.c_void_p(a.ctypes.data or 1), a.size, 0))
+
+    def state_digest(self):
+        """sphx_state_digest: {section name: 64-bit digest} of the live state (_lib.STATE_SECTIONS); 72 bytes come back from the device.
+        An integrity check and a fingerprint for comparing two contexts or runs, not a cryptographic hash."""
+        out = (C.c_uint64 * len(_lib.STATE_SECTIONS))()
+        self._chk(self.L.sphx_state_digest(self.h, out))
+        return {name: int(out[k]) for k, name in enumerate(_lib.STATE_SECTIONS)}
+
+    def save_state_file(self, path):
+        self._chk(self.L.sphx_state_save_file(self.h, str(path).encode()))
+
+    def load_state_file(self, path):
+        self._chk(self.L.sphx_state_load_file(self.h, str(path).encode()))
+
     def profile_enable(self, on=True):
         self._chk(self.L.sphx_profile_enable(self.h, int(on)))
 
@@ -639,6 +699,21 @@ class TimeManager:
             raise SphxError(rc, "sphx_timer_law_of")
         return out
 
+    def get_state(self):
+        """sphx_timer_get_state: everything the timer holds, as a _lib.SphxTimerState."""
+        st = _lib.SphxTimerState()
+        rc = self.L.sphx_timer_get_state(self.h, C.byref(st))
+        if rc:
+            raise SphxError(rc, "sphx_timer_get_state")
+        return st
+
+    def set_state(self, state):
+        """sphx_timer_set_state: continue exactly as the timer that get_state() was taken from."""
+        rc = self.L.sphx_timer_set_state(self.h, C.byref(state))
+        if rc:
+            raise SphxError(rc, "sphx_timer_set_state: not a state a TimeManager can hold")
+        self.timestep_max_ns, self.timestep_min_ns, self.cfl_factor = state.timestep_max_ns, state.timestep_min_ns, state.cfl_factor
+
     @property
     def total_simulated_ns(self):
         return self.L.sphx_timer_total_simulated_ns(self.h)
@@ -710,6 +785,21 @@ class DFSPHSolver:
         if rc:
             raise SphxError(rc, self.L.sphx_solver_last_error(self.h).decode())
         return removed.value
+
+    def save(self, world, time_manager, path):
+        """sphx_solver_save: one file holding the context's blob and the timer's state."""
+        rc = self.L.sphx_solver_save(self.h, world.h, time_manager.h, str(path).encode())
+        if rc:
+            raise SphxError(rc, self.L.sphx_solver_last_error(self.h).decode())
+
+    def load(self, world, time_manager, path, sync_world=False):
+        """sphx_solver_load: continue the run of the file; the timer gets the saved state, the world the saved boundary and the device's
+        particle count (sync_world=True also downloads its arrays)."""
+        rc = self.L.sphx_solver_load(self.h, world.h, time_manager.h, str(path).encode())
+        if rc:
+            raise SphxError(rc, self.L.sphx_solver_last_error(self.h).decode())
+        if sync_world:
+            self.sync_world(world)
 
     def context(self):
         """Borrowed SphxContext view (for inspection: neighbours, cells, solver state, profiling)."""

@@ -111,6 +111,16 @@ class SphxRect(C.Structure):
     _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("x1", C.c_float), ("y1", C.c_float)]
 
 
+STATE_DEVICE_BUFFER = 1  # sphx_state_save / sphx_state_load flags
+STATE_SECTIONS = ("positions", "velocities", "particle_id", "density", "alpha", "kappa", "stiffness", "accel", "boundary")  # SPHX_STATE_SEC_*
+
+
+class SphxTimerState(C.Structure):
+    _fields_ = [("fixed", C.c_uint32), ("cfl_factor", C.c_float), ("timestep_max_ns", C.c_uint64), ("timestep_min_ns", C.c_uint64),
+                ("simulation_step_ns", C.c_uint64), ("timestep_target_frame_ns", C.c_uint64), ("total_simulated_ns", C.c_uint64),
+                ("num_simulation_steps", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class SphxMultiOptions(C.Structure):
     _fields_ = [("halo_cells", C.c_uint32), ("fixed_halo", C.c_uint32), ("rebalance_every", C.c_uint32), ("layout", C.c_uint32),
                 ("cap_records", C.c_uint32), ("overlap_exchange", C.c_uint32), ("reserved", C.c_uint32 * 2)]
@@ -149,6 +159,12 @@ SIGNATURES = {
     "sphx_upload": (_i, [_vp, _vp, _vp, _u32]),
     "sphx_append": (_i, [_vp, _vp, _vp, _u32, C.POINTER(_u32)]),
     "sphx_remove": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32, C.POINTER(_u32)]),
+    "sphx_state_size": (_i, [_vp, C.POINTER(_u64)]),
+    "sphx_state_save": (_i, [_vp, _vp, _u64, _u32, C.POINTER(_u64)]),
+    "sphx_state_load": (_i, [_vp, _vp, _u64, _u32]),
+    "sphx_state_digest": (_i, [_vp, C.POINTER(_u64)]),
+    "sphx_state_save_file": (_i, [_vp, C.c_char_p]),
+    "sphx_state_load_file": (_i, [_vp, C.c_char_p]),
     "sphx_download": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "sphx_download_boundary": (_i, [_vp, _vp, _vp]),
     "sphx_num_particles": (_u32, [_vp]),
@@ -263,6 +279,10 @@ SIGNATURES = {
     "sphx_timer_update_simulation_step": (_u64, [_vp, _f, _f]),
     "sphx_timer_total_simulated_ns": (_u64, [_vp]),
     "sphx_timer_num_steps": (_u32, [_vp]),
+    "sphx_timer_get_state": (_i, [_vp, C.POINTER(SphxTimerState)]),
+    "sphx_timer_set_state": (_i, [_vp, C.POINTER(SphxTimerState)]),
+    "sphx_solver_save": (_i, [_vp, _vp, _vp, C.c_char_p]),
+    "sphx_solver_load": (_i, [_vp, _vp, _vp, C.c_char_p]),
     "sphx_solver_create_dfsph": (_i, [_vp, C.POINTER(SphxParams), C.POINTER(_vp)]),
     "sphx_solver_create_wcsph": (_i, [_vp, C.POINTER(SphxParams), C.POINTER(_vp)]),
     "sphx_solver_create_dfsph_multi": (_i, [_vp, C.POINTER(SphxParams), C.POINTER(C.c_int), _i, C.POINTER(SphxMultiOptions), C.POINTER(_vp)]),

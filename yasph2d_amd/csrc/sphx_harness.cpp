@@ -5,6 +5,13 @@
 //                [--gauges x1,x2,... [--gauge-range lo:hi:dy]]
 //                [--record DIR [--record-fps F] [--record-size WxH] [--record-min-pixel-radius P]]
 //                [--emit x,y,w,h[:every=K][:until=S][:vel=vx,vy]] [--drain x0,y0,x1,y1]... [--keep x0,y0,x1,y1]...
+//                [--load-state FILE] [--save-state FILE[:at=STEP]] [--help]
+//
+// --load-state / --save-state: the run picked up from and put down into a solver state file (sphx_solver_load / sphx_solver_save: the
+// context's blob and the timer's state).  --load-state FILE starts from the file instead of the scene (solver kind, viscosity and scale
+// must be those of the run that saved it: the params check refuses anything else); steps are then counted from 0 again.  --save-state FILE
+// writes the file after the last step, --save-state FILE:at=STEP after STEP steps of this run (warm-up and timed steps counted together).
+// A run of K steps, and a run of J < K steps that saves followed by a run that loads and does K - J steps, end in the same bits.
 //
 // --emit / --drain / --keep: fluid added and removed on the device between the steps (sphx_append / sphx_remove through the solver
 // object).  Steps are counted from 0 over warm-up and timed steps together; the edits come before a step, from step 1 on (step 0 uploads
@@ -85,6 +92,16 @@ static bool gauge_elevation(sph::HipDfsphSolver& solver, double x, double lo, do
 }
 
 // `count` comma-separated numbers; a rectangle bound may be infinite, never NaN
+static const char* const USAGE =
+    "sphx_harness [--solver dfsph|wcsph] [--viscosity xsph|physical[:mu]] [--scale S | --particles N] [--steps K] [--warmup W] [--no-law] [--sync]\n"
+    "             [--gauges x1,x2,... [--gauge-range lo:hi:dy]]\n"
+    "             [--record DIR [--record-fps F] [--record-size WxH] [--record-min-pixel-radius P]]\n"
+    "             [--emit x,y,w,h[:every=K][:until=S][:vel=vx,vy]] [--drain x0,y0,x1,y1]... [--keep x0,y0,x1,y1]...\n"
+    "             [--load-state FILE] [--save-state FILE[:at=STEP]] [--help]\n"
+    "  --load-state FILE            start from a solver state file (sphx_solver_load) instead of the scene\n"
+    "  --save-state FILE[:at=STEP]  write a solver state file (sphx_solver_save) after STEP steps of this run; default: after the last step\n"
+    "Prints one JSON line with the throughput, the timer's final step and a checksum of the final state.\n";
+
 static bool parse_list(const std::string& s, size_t count, bool allow_inf, double* out) {
     size_t p = 0;
     for (size_t k = 0; k < count; ++k) {
@@ -112,6 +129,9 @@ int main(int argc, char** argv) {
     std::string emit_arg;
     bool want_emit = false;
     std::vector<sphx_rect> drain_rects, keep_rects;
+    std::string load_state, save_state;
+    bool want_load = false, want_save = false;
+    long save_at = -1;  // (-1: after the last step)
     auto add_rect = [&](std::vector<sphx_rect>& to, const char* opt, const std::string& arg) {
         double v[4];
         if (!parse_list(arg, 4, true, v) || drain_rects.size() + keep_rects.size() >= SPHX_REMOVE_MAX_RECTS) {
@@ -141,10 +161,34 @@ int main(int argc, char** argv) {
         else if (s == "--emit") emit_arg = next(), want_emit = true;
         else if (s == "--drain") add_rect(drain_rects, "--drain", next());
         else if (s == "--keep") add_rect(keep_rects, "--keep", next());
+        else if (s == "--load-state") load_state = a + 1 < argc ? argv[++a] : "", want_load = true;
+        else if (s == "--save-state") save_state = a + 1 < argc ? argv[++a] : "", want_save = true;
+        else if (s == "--help" || s == "-h") {
+            std::fputs(USAGE, stdout);
+            return 0;
+        }
         else {
             std::fprintf(stderr, "unknown argument %s\n", s.c_str());
             return 2;
         }
+    }
+    if (want_save) {
+        const size_t at = save_state.rfind(":at=");
+        bool ok = true;
+        if (at != std::string::npos) {
+            double num;
+            ok = parse_double(save_state.substr(at + 4), &num) && num >= 0.0 && num == std::floor(num) && num < 1e15;
+            save_at = ok ? (long)num : -1;
+            save_state.erase(at);
+        }
+        if (!ok || save_state.empty()) {
+            std::fprintf(stderr, "invalid --save-state (FILE[:at=STEP], STEP a whole number >= 0)\n");
+            return 2;
+        }
+    }
+    if (want_load && load_state.empty()) {
+        std::fprintf(stderr, "invalid --load-state (FILE)\n");
+        return 2;
     }
     const bool wcsph = solver_kind == "wcsph";
     sph::FluidParticleWorld world(2.0f, 10000.0f, 100.0f);  // main.rs:85-89
@@ -250,6 +294,10 @@ int main(int argc, char** argv) {
     solver->use_timer_law = law;
     sph::TimeManager tm = sph::TimeManager::adaptive(sph::Duration::from_secs_f32(1.0f / 120.0f / 3.0f), sph::Duration::from_secs_f32(1.0f / 60.0f / 400.0f),
                                                      wcsph ? 0.2f : 1.5f);  // main.rs:115-127
+    if (want_load && solver->load(world, tm, load_state.c_str()) != SPHX_OK) {
+        std::fprintf(stderr, "--load-state %s failed: %s (status %d)\n", load_state.c_str(), solver->last_error.c_str(), solver->last_status);
+        return 1;
+    }
     const size_t n = world.particles.positions.size();
     // recording mode
     sph::Camera camera = sph::Camera::center_around_world_rect(record_w, record_h, -0.1f * scale, -0.1f * scale, 2.1f * scale, 1.6f * scale);  // main.rs:137
@@ -259,6 +307,7 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> image;
     if (want_record) {
         tm.timestep_target_frame = sph::Duration{frame_ns};  // main.rs:323-326
+        frames = tm.total_simulated_time.ns / frame_ns;      // (0 unless --load-state: the frames before the save were drawn by that run)
         mkdir(record_dir.c_str(), 0777);
         image.resize((size_t)record_w * record_h * 4);
     }
@@ -313,6 +362,13 @@ int main(int argc, char** argv) {
             drained += gone;
         }
     };
+    auto save = [&]() {
+        if (solver->save(world, tm, save_state.c_str()) != SPHX_OK) {
+            std::fprintf(stderr, "--save-state %s failed: %s (status %d)\n", save_state.c_str(), solver->last_error.c_str(), solver->last_status);
+            std::exit(1);
+        }
+    };
+    if (want_save && save_at == 0) save();  // (only a loaded run holds a state before its first step)
     auto step = [&]() {
         if (want_edit && step_index > 0) edit();
         ++step_index;
@@ -323,6 +379,7 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "step failed: %s (status %d)\n", solver->last_error.c_str(), solver->last_status);
             std::exit(1);
         }
+        if (want_save && step_index == save_at) save();
     };
     for (long i = 0; i < warmup; ++i) step();
     sphx_synchronize(solver->ctx());
@@ -335,10 +392,14 @@ int main(int argc, char** argv) {
     }
     sphx_synchronize(solver->ctx());
     const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (want_save && save_at < 0) save();
     if (solver->sync_world(world) != SPHX_OK) return 1;
     // order-independent content check: positions/velocities placed at their persistent particle id
     const size_t n_final = world.particles.positions.size();  // (== n unless --emit / --drain / --keep edited the set; ids < n + emitted)
-    std::vector<float> by_id(4 * (n + emitted), 0.0f);
+    size_t id_span = n + emitted;
+    if (want_load)  // (a loaded set may hold ids of particles that were appended and removed before the save)
+        for (size_t i = 0; i < n_final; ++i) id_span = std::max<size_t>(id_span, (size_t)world.particles.particle_ids[i] + 1);
+    std::vector<float> by_id(4 * id_span, 0.0f);
     for (size_t i = 0; i < n_final; ++i) {
         const uint32_t id = world.particles.particle_ids[i];
         by_id[4 * id + 0] = world.particles.positions[i].x;

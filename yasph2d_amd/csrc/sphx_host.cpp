@@ -1,6 +1,8 @@
 // sphx_host.cpp — implementation of the host-side mirror (sphx_host.hpp) and its C exports (include/sphx.h, bottom half).
 #include "sphx_host.hpp"
 
+#include "sphx_state_format.hpp"
+
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -8,6 +10,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -223,6 +226,31 @@ void timer_law_of(const TimeManager& tm, Real particle_diameter, sphx_timer_law*
 void TimeManager::on_step_started() {
     num_simulation_steps += 1;
     total_simulated_time.ns += simulation_step_.ns;
+}
+sphx_timer_state TimeManager::get_state() const {
+    sphx_timer_state s;
+    std::memset(&s, 0, sizeof(s));
+    s.fixed = fixed ? 1u : 0u;
+    s.cfl_factor = cfl_factor;
+    s.timestep_max_ns = timestep_max.ns;
+    s.timestep_min_ns = timestep_min.ns;
+    s.simulation_step_ns = simulation_step_.ns;
+    s.timestep_target_frame_ns = timestep_target_frame.ns;
+    s.total_simulated_ns = total_simulated_time.ns;
+    s.num_simulation_steps = num_simulation_steps;
+    return s;
+}
+bool TimeManager::set_state(const sphx_timer_state& s) {
+    if (!sphx_state::timer_state_valid(s)) return false;
+    fixed = s.fixed != 0;
+    cfl_factor = s.cfl_factor;
+    timestep_max.ns = s.timestep_max_ns;
+    timestep_min.ns = s.timestep_min_ns;
+    simulation_step_.ns = s.simulation_step_ns;
+    timestep_target_frame.ns = s.timestep_target_frame_ns;
+    total_simulated_time.ns = s.total_simulated_ns;
+    num_simulation_steps = s.num_simulation_steps;
+    return true;
 }
 
 // ---- HipDfsphSolver -----------------------------------------------------------------------------------------------------
@@ -476,6 +504,88 @@ int HipDfsphSolver::remove(FluidParticleWorld& w, const sphx_rect* rects, uint32
     return edit_done(w, sync, sphx_remove(ctx_, rects, n_rects, flags, out_removed));
 }
 
+
+// ---- the run in one file: {SolverFileHeader with the timer's state, the context's blob} -------------------------------------------------
+int HipDfsphSolver::save(const FluidParticleWorld& w, const TimeManager& tm, const char* path) {
+    if (!path) {
+        last_error = "save: path is NULL";
+        return last_status = SPHX_ERR_INVALID_ARGUMENT;
+    }
+    if (int rc = edit_ready(w)) {
+        if (rc == SPHX_ERR_NOT_READY) last_error = "save: the device does not hold this world yet (step first)";
+        return rc;
+    }
+    auto fail = [&](int rc, const std::string& what) {
+        last_error = what;
+        return last_status = rc;
+    };
+    uint64_t bytes = 0;
+    int rc;
+    if ((rc = sphx_state_size(ctx_, &bytes))) return fail(rc, sphx_last_error(ctx_));
+    std::vector<unsigned char> file(sizeof(sphx_state::SolverFileHeader) + bytes);
+    if ((rc = sphx_state_save(ctx_, file.data() + sizeof(sphx_state::SolverFileHeader), bytes, 0u, nullptr))) return fail(rc, sphx_last_error(ctx_));
+    sphx_state::SolverFileHeader fh;
+    std::memset(&fh, 0, sizeof(fh));
+    std::memcpy(fh.magic, sphx_state::SOLVER_MAGIC, 8);
+    fh.version = sphx_state::VERSION;
+    fh.endian_tag = sphx_state::ENDIAN_TAG;
+    fh.blob_bytes = bytes;
+    fh.timer = tm.get_state();
+    std::memcpy(file.data(), &fh, sizeof(fh));
+    const std::string tmp = std::string(path) + ".tmp";
+    FILE* f = std::fopen(tmp.c_str(), "wb");
+    bool ok = f != nullptr;
+    if (ok) {
+        ok = std::fwrite(file.data(), 1, file.size(), f) == file.size();
+        ok = std::fclose(f) == 0 && ok;
+    }
+    if (ok) ok = std::rename(tmp.c_str(), path) == 0;
+    if (!ok) {
+        const std::string e = std::strerror(errno);
+        std::remove(tmp.c_str());
+        return fail(SPHX_ERR_INVALID_ARGUMENT, "save: cannot write " + std::string(path) + ": " + e);
+    }
+    return last_status = SPHX_OK;
+}
+
+int HipDfsphSolver::load(FluidParticleWorld& w, TimeManager& tm, const char* path) {
+    auto fail = [&](int rc, const std::string& what) {
+        last_error = what;
+        return last_status = rc;
+    };
+    if (!ctx_) return last_status = SPHX_ERR_NO_DEVICE;
+    if (!path) return fail(SPHX_ERR_INVALID_ARGUMENT, "load: path is NULL");
+    FILE* f = std::fopen(path, "rb");
+    if (!f) return fail(SPHX_ERR_INVALID_ARGUMENT, "load: cannot open " + std::string(path) + ": " + std::strerror(errno));
+    std::vector<unsigned char> file;
+    unsigned char chunk[1 << 16];
+    size_t got;
+    while ((got = std::fread(chunk, 1, sizeof(chunk), f)) > 0) file.insert(file.end(), chunk, chunk + got);
+    const bool bad = std::ferror(f) != 0;
+    std::fclose(f);
+    if (bad) return fail(SPHX_ERR_INVALID_ARGUMENT, "load: cannot read " + std::string(path));
+    sphx_state::SolverFileHeader fh;
+    std::string why;
+    if (!sphx_state::validate_solver_file(file.data(), file.size(), &fh, &why)) return fail(SPHX_ERR_INVALID_ARGUMENT, "load: " + why);
+    const unsigned char* blob = file.data() + sizeof(fh);
+    sphx_state::Header h;
+    if (!sphx_state::validate(blob, fh.blob_bytes, &h, &why)) return fail(SPHX_ERR_INVALID_ARGUMENT, "load: " + why);
+    // (sphx_state_load validates again, and against this context; a refusal there has changed nothing either)
+    if (int rc = sphx_state_load(ctx_, blob, fh.blob_bytes, 0u)) {
+        const std::string e = sphx_last_error(ctx_);
+        // refused before anything changed: the device still holds the world; broken half way (a digest): the next step uploads the world
+        uint64_t unused;
+        if (sphx_state_size(ctx_, &unused) == SPHX_ERR_NOT_READY) uploaded_n_ = (size_t)-1;
+        return fail(rc, e);
+    }
+    tm.set_state(fh.timer);  // (validated above)
+    const sphx_state::Section& sb = h.sec[SPHX_STATE_SEC_BOUNDARY];
+    w.particles.boundary_particles.resize(h.s.b);
+    if (sb.bytes) std::memcpy(&w.particles.boundary_particles[0].x, blob + sb.offset, sb.bytes);
+    w.boundary_changed = false;  // the device holds exactly this boundary
+    return edit_done(w, false, SPHX_OK);
+}
+
 }  // namespace sph
 
 // =====================================================================================================================
@@ -563,6 +673,15 @@ uint64_t sphx_timer_total_simulated_ns(const sphx_timer* t) { return t->t.total_
 uint32_t sphx_timer_num_steps(const sphx_timer* t) { return t->t.num_simulation_steps; }
 void sphx_timer_set_target_frame(sphx_timer* t, uint64_t target_ns) { t->t.timestep_target_frame.ns = target_ns; }
 void sphx_timer_on_step_started(sphx_timer* t) { t->t.on_step_started(); }
+int sphx_timer_get_state(const sphx_timer* t, sphx_timer_state* out) {
+    if (!t || !out) return SPHX_ERR_INVALID_ARGUMENT;
+    *out = t->t.get_state();
+    return SPHX_OK;
+}
+int sphx_timer_set_state(sphx_timer* t, const sphx_timer_state* state) {
+    if (!t || !state) return SPHX_ERR_INVALID_ARGUMENT;
+    return t->t.set_state(*state) ? SPHX_OK : SPHX_ERR_INVALID_ARGUMENT;
+}
 // Camera::center_around_world_rect (camera.rs:21-35) over the screen (0, 0, width, height), plus the app's drawing defaults
 int sphx_render_fit(uint32_t width, uint32_t height, float x, float y, float w, float h, sphx_render_view* out) {
     if (!out || !std::isfinite(x) || !std::isfinite(y) || !std::isfinite(w) || !std::isfinite(h) || !(w > 0.0f) || !(h > 0.0f))
@@ -652,6 +771,14 @@ int sphx_solver_append(sphx_solver* s, sphx_world* w, const float* pos_xy, const
 int sphx_solver_remove(sphx_solver* s, sphx_world* w, const sphx_rect* rects, uint32_t n_rects, uint32_t flags, int sync_world, uint32_t* out_removed) {
     if (!s || !w) return SPHX_ERR_INVALID_ARGUMENT;
     return s->s.remove(w->w, rects, n_rects, flags, sync_world != 0, out_removed);
+}
+int sphx_solver_save(sphx_solver* s, sphx_world* w, sphx_timer* t, const char* path) {
+    if (!s || !w || !t || !path) return SPHX_ERR_INVALID_ARGUMENT;
+    return s->s.save(w->w, t->t, path);
+}
+int sphx_solver_load(sphx_solver* s, sphx_world* w, sphx_timer* t, const char* path) {
+    if (!s || !w || !t || !path) return SPHX_ERR_INVALID_ARGUMENT;
+    return s->s.load(w->w, t->t, path);
 }
 sphx_ctx* sphx_solver_ctx(sphx_solver* s) { return s->s.ctx(); }
 const char* sphx_solver_last_error(const sphx_solver* s) { return s->s.last_error.c_str(); }

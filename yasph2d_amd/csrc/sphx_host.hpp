@@ -95,6 +95,9 @@ struct TimeManager {
     Duration update_simulation_step(Real particle_diameter, Real max_velocity);   // :252-279
     Duration lower_bound() const;                                                 // :268-274, known before the update
     void on_step_started();  // the clock part of simulation_frame_loop (:244-247)
+    // everything above as one POD (sphx_timer_state): a timer given another's state continues exactly as that one would
+    sphx_timer_state get_state() const;
+    bool set_state(const sphx_timer_state& s);  // false (and unchanged) for a state no TimeManager can hold
 };
 
 // what sphx_step_begin_law needs to know about the timer (its public config + current step)
@@ -137,6 +140,12 @@ class HipDfsphSolver : public Solver {
     // first step and when the caller has edited the world's particles since the last one.
     virtual int append(FluidParticleWorld& fluid_world, const float* pos_xy, const float* vel_xy, uint32_t m, bool sync, uint32_t* out_first_id);
     virtual int remove(FluidParticleWorld& fluid_world, const sphx_rect* rects, uint32_t n_rects, uint32_t flags, bool sync, uint32_t* out_removed);
+    // The run put down into one file and picked up from it (sphx_solver_save / sphx_solver_load in sphx.h): the context's blob
+    // (sphx_state_save) behind a header with the timer's state.  save: SPHX_ERR_NOT_READY while the device does not hold this world
+    // (before the first step, or the caller edited the particles since).  load: the whole file is validated before anything changes;
+    // then the timer has the saved state, the world the saved boundary and the device's count (arrays behind the device: sync_world).
+    virtual int save(const FluidParticleWorld& fluid_world, const TimeManager& time_manager, const char* path);
+    virtual int load(FluidParticleWorld& fluid_world, TimeManager& time_manager, const char* path);
 
     bool sync_every_step = true;   // main.rs draws from the host arrays after each step
     bool use_timer_law = true;     // sphx_step_begin_law: the device derives dt itself, the host only verifies it
@@ -185,11 +194,13 @@ class HipDfsphMultiSolver : public HipDfsphSolver {
     int sync_world(FluidParticleWorld& fluid_world) override;
     int append(FluidParticleWorld&, const float*, const float*, uint32_t, bool, uint32_t*) override { return no_edit(); }
     int remove(FluidParticleWorld&, const sphx_rect*, uint32_t, uint32_t, bool, uint32_t*) override { return no_edit(); }
+    int save(const FluidParticleWorld&, const TimeManager&, const char*) override { return no_edit("save / load"); }
+    int load(FluidParticleWorld&, TimeManager&, const char*) override { return no_edit("save / load"); }
     sphx_multi* multi() { return multi_; }
 
    private:
-    int no_edit() {
-        last_error = "append / remove are not available on the multi-GPU solver";
+    int no_edit(const char* what = "append / remove") {
+        last_error = std::string(what) + " are not available on the multi-GPU solver";
         return last_status = SPHX_ERR_INVALID_ARGUMENT;
     }
     sphx_multi* multi_ = nullptr;

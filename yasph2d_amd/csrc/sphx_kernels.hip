@@ -3224,3 +3224,5 @@ __global__ __launch_bounds__(64) void k_publish(DevScalars* scal, Mailbox* mb, u
 #include "sphx_render.inc"
 // fluid appended to and removed from the device state between steps (kernels + C ABI)
 #include "sphx_edit.inc"
+// a context saved into and restored from one blob (the section digest kernel + C ABI)
+#include "sphx_state.inc"

@@ -712,6 +712,7 @@ static inline void sample_after_step(sphx_ctx* c) {
 // that are right for any distance (sqrt_dist in sphx_kernels.hip) until the next build.
 static inline void lists_went_stale(sphx_ctx* c) {
     c->K.q_noclamp = 0u;
+    c->lists_current = false;
     // (a caller that has already dropped the sampling state keeps its own, more specific message)
     if (c->sample_ready) sample_went_stale(c, "the positions changed since the last neighbour build: run a step, or sphx_update_neighborhood + sphx_update_densities");
 }
@@ -838,6 +839,7 @@ int recover_directory(sphx_ctx* c, float advect_dt, uint32_t advect_below = 0xFF
 int update_neighborhood(sphx_ctx* c, bool extra_alpha, float advect_dt, bool fuse, bool fuse_div = false, bool fuse_warm = false) {
     int rc;
     drop_class_count(c);
+    c->lists_current = false;
     sample_went_stale(c, "the last neighbour build did not complete: upload the state again");
     if (c->boundary_changed) {
         if ((rc = build_static(c))) return rc;
@@ -969,6 +971,7 @@ int update_neighborhood(sphx_ctx* c, bool extra_alpha, float advect_dt, bool fus
         if ((rc = wait_mailbox(c, tile_n))) return rc;  // tile_n carries the sequence number of the publish inside build_grid
         c->N = std::min(c->mbox->sort_total, c->N);
     }
+    c->lists_current = true;
     c->sample_ready = 1u;  // (the callers that also complete the densities of this build raise it to 2)
     c->sample_missing = "the densities of the last neighbour build are missing: call sphx_update_densities";
     return SPHX_OK;
@@ -1560,7 +1563,7 @@ void sphx_destroy(sphx_ctx* c) {
     dev_free(&c->density); dev_free(&c->alpha); dev_free(&c->alpha2); dev_free(&c->kappa); dev_free(&c->stiff); dev_free(&c->kappa2); dev_free(&c->stiff2);
     dev_free(&c->pid); dev_free(&c->pid2); dev_free(&c->key); dev_free(&c->slot); dev_free(&c->order);
     dev_free(&c->bpos); dev_free(&c->bpos2); dev_free(&c->bid); dev_free(&c->bid2); dev_free(&c->nb_list); dev_free(&c->nb_wave); dev_free(&c->nb_counts); dev_free(&c->nb_remote);
-    dev_free(&c->scan_partials); dev_free(&c->scan_state); dev_free(&c->d_scal); dev_free(&c->tile_blk); dev_free(&c->sample_buf); dev_free(&c->render_buf); dev_free(&c->edit_buf);
+    dev_free(&c->scan_partials); dev_free(&c->scan_state); dev_free(&c->d_scal); dev_free(&c->tile_blk); dev_free(&c->sample_buf); dev_free(&c->render_buf); dev_free(&c->edit_buf); dev_free(&c->state_dig);
     free_grid(c->gdyn);
     free_grid(c->gstat);
     if (c->mbox) hipHostFree((void*)c->mbox);
