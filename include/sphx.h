@@ -18,7 +18,7 @@
  * What is the contract and what is scaffolding (the header has grown beyond the boundary SURVEY.md 8(b) asks for):
  *   STABLE — the drop-in boundary a Rust shim binds:
  *       lifecycle (sphx_default_params, sphx_create, sphx_destroy, sphx_last_error, sphx_abi_version), the particle-array
- *       surface (sphx_set_boundary, sphx_upload, sphx_append, sphx_remove, sphx_download*, sphx_num_*, sphx_view_*, sphx_sample_*, sphx_render*, sphx_state_*), the Solver trait (sphx_clear_cached,
+ *       surface (sphx_set_boundary, sphx_upload, sphx_append, sphx_remove, sphx_download*, sphx_num_*, sphx_view_*, sphx_sample_*, sphx_render*, sphx_state_*, sphx_track_*, sphx_download_by_id), the Solver trait (sphx_clear_cached,
  *       sphx_step_begin[_law], sphx_step_finish, sphx_wcsph_step_*), the same trait over a device list (sphx_multi_create[_rank],
  *       sphx_multi_destroy, sphx_multi_set_boundary, sphx_multi_upload, sphx_multi_clear_cached, sphx_multi_step_begin/finish,
  *       sphx_multi_simulation_step[s], sphx_multi_download, sphx_multi_num_owned, sphx_multi_last_error, sphx_comm_ops) and
@@ -56,7 +56,9 @@ extern "C" {
                             * 5 (additive): sphx_render, sphx_render_fit, sphx_render_view, sphx_render_out, SPHX_RENDER_*
                             * 5 (additive): sphx_append, sphx_remove, sphx_rect, SPHX_REMOVE_*, sphx_solver_append, sphx_solver_remove
                             * 5 (additive): sphx_state_size / _save / _load / _digest / _save_file / _load_file, SPHX_STATE_*, sphx_timer_state,
-                            *    sphx_timer_get_state / _set_state, sphx_solver_save / _load */
+                            *    sphx_timer_get_state / _set_state, sphx_solver_save / _load
+                            * 5 (additive): sphx_track_set / _fetch / _record / _get_status / _read, sphx_download_by_id, sphx_track_out,
+                            *    sphx_track_status, SPHX_TRACK_* */
 
 /* ---- status codes ---- */
 enum {
@@ -380,6 +382,62 @@ int sphx_state_load(sphx_ctx* ctx, const void* buf, uint64_t bytes, uint32_t fla
 int sphx_state_digest(sphx_ctx* ctx, uint64_t* out /* [SPHX_STATE_SECTIONS] */);
 int sphx_state_save_file(sphx_ctx* ctx, const char* path);
 int sphx_state_load_file(sphx_ctx* ctx, const char* path);
+
+/* ---- following particles by id: look-up, id-ordered download, trajectories (csrc/sphx_track.inc) -----------------------------------------
+ * The device re-sorts its particles on every step; particle_id[] travels with them.  These calls answer "where is particle id now" on the
+ * device — 4 bytes per particle scanned — instead of a full sphx_download and an argsort on the host.  (sphx_view_* cannot stand in: it
+ * packs every stride-th SLOT, and a slot holds another particle after each re-grid.)
+ * Slot of an id: slot_of(id) = the HIGHEST device index j < N with particle_id[j] == id, or SPHX_TRACK_ABSENT if there is none; "device
+ *   index" is the order of sphx_download.  Ids are unique in a context filled by sphx_upload / sphx_append; a context that loaded a blob
+ *   with repeated ids (sphx_state_load does not refuse one) gets the same answer on every call (an integer maximum of slot + 1, no race).
+ * Fetch: sphx_track_set hands over m ids (host memory, copied; any order, duplicates allowed and answered alike; m == 0 clears the set).
+ *   sphx_track_fetch then gives, for the k-th id in the caller's order: slot[k] = slot_of(ids[k]); pos, vel and density = the exact bits
+ *   sphx_download returns at that slot.  For an absent id every float is the word 0x7FC00000 and the slot is SPHX_TRACK_ABSENT.  An empty
+ *   set is a successful no-op.
+ * sphx_download_by_id: the same rule for the ids first_id + k, k < count; *out_present = the number of ids found.  first_id + count may
+ *   reach 2^32 and no more (SPHX_ERR_INVALID_ARGUMENT beyond); count == 0 is a successful no-op (*out_present = 0).  With first_id = 0 and
+ *   count = n after an unedited sphx_upload of n particles the result is the particles in upload order, whatever the steps since.
+ * SPHX_TRACK_DEVICE_POINTERS (fetch, read, download_by_id): every output — out_present too — is a device pointer on the context's device;
+ *   the call is enqueued on the context's stream and returns without waiting.  Without it: host pointers; the call returns when they are
+ *   written (through a device scratch the library grows on demand and frees in sphx_destroy).
+ * Recording: after sphx_track_record(max_frames, every) every every-th SUCCESSFULLY finished step (either solver, counted from the call;
+ *   so also each step inside sphx_solver_simulation_steps) enqueues one frame behind its own kernels: {x, y, vx, vy} per tracked id in the
+ *   caller's order, 16 bytes each, four 0x7FC00000 words for an absent id.  Nothing comes back to the host and nothing is synchronised.
+ *   A failed step takes no frame and does not count.  Once max_frames frames are stored, later frames are counted in `dropped` and not
+ *   stored.  The buffer is max_frames * m * 16 bytes on the device; more than 1 GiB is SPHX_ERR_CAPACITY.  sphx_track_read copies the
+ *   frames [first_frame, first_frame + n_frames) to out[n_frames][m][4]; a range beyond `frames` is SPHX_ERR_INVALID_ARGUMENT; the host
+ *   path waits for the stream.  sphx_track_set and sphx_track_record discard an earlier recording; max_frames == 0 stops and frees;
+ *   every == 0 is SPHX_ERR_INVALID_ARGUMENT; recording with an empty set is SPHX_ERR_NOT_READY.
+ * Lifetime: the set and the recording belong to the CONTEXT, not to the particle state.  sphx_append / sphx_remove leave them alone (a
+ *   removed id becomes absent, an appended id that is in the set is found).  sphx_upload renumbers the particles: the set keeps its numbers
+ *   and now means the new particles.  sphx_state_save does not store them; sphx_state_load leaves them as they are.
+ * No side effects: all of this only reads the particle state.  A run with a tracked set, fetches, by-id downloads and a recording is
+ *   bit-identical to the same run without them — every sphx_state_digest word, every sphx_step_stats field, sphx_last_flags — and a queued
+ *   run-ahead pass stays valid, as for sphx_sample_*.
+ * When allowed: fetch and sphx_download_by_id wherever sphx_download is, and before any upload (N = 0: everything is absent).  Fetch, read,
+ *   sphx_download_by_id, set and record return SPHX_ERR_NOT_READY between a step_begin and its step_finish (either solver).  A tile context
+ *   (sphx_tile_*, sphx_multi_tile_ctx) is refused with SPHX_ERR_INVALID_ARGUMENT: it holds ghosts and its ids need not be unique.
+ *   sphx_multi_* has NO counterpart: a multi-GPU run is followed through sphx_multi_download.
+ * Argument errors (SPHX_ERR_INVALID_ARGUMENT, the message names the argument): ctx, out or status NULL, every output NULL, ids NULL with
+ *   m > 0, m > SPHX_TRACK_MAX_IDS, unknown flag bits.
+ * Cost: the look-up streams particle_id[] once (4 bytes per particle; a bit filter in LDS keeps all but ~6 % of the other particles away
+ *   from the binary search of the sorted id table), then 28 bytes per id found; a frame entry is 16 bytes ("Following particles"). */
+#define SPHX_TRACK_MAX_IDS 16384
+#define SPHX_TRACK_ABSENT  0xFFFFFFFFu
+enum { SPHX_TRACK_DEVICE_POINTERS = 1u };
+typedef struct sphx_track_out {
+    uint32_t* slot;   /* [m] or NULL */
+    float* pos;       /* [2m] interleaved xy, or NULL */
+    float* vel;       /* [2m] interleaved xy, or NULL */
+    float* density;   /* [m] or NULL */
+} sphx_track_out;     /* not all NULL */
+typedef struct sphx_track_status { uint32_t m, recording, max_frames, every, frames, dropped, reserved[2]; } sphx_track_status;
+int sphx_track_set(sphx_ctx* ctx, const uint32_t* ids /* host */, uint32_t m);
+int sphx_track_fetch(sphx_ctx* ctx, uint32_t flags, const sphx_track_out* out);
+int sphx_track_record(sphx_ctx* ctx, uint32_t max_frames, uint32_t every);
+int sphx_track_get_status(const sphx_ctx* ctx, sphx_track_status* out);
+int sphx_track_read(sphx_ctx* ctx, uint32_t first_frame, uint32_t n_frames, uint32_t flags, float* out /* [n_frames][m][4] = x, y, vx, vy */);
+int sphx_download_by_id(sphx_ctx* ctx, uint32_t first_id, uint32_t count, uint32_t flags, const sphx_track_out* out, uint32_t* out_present /* may be NULL */);
 
 /* ---- Solver trait (solver/mod.rs:12-18) ---------------------------------------------------------------------- */
 /* Solver::clear_cached_data (dfsph.rs:406-412) */

@@ -16,7 +16,7 @@ from ._lib import (FLAG_DENSITY_ITER_CAP, FLAG_DIVERGENCE_ITER_CAP, FLAG_DENSE_C
 
 __all__ = ["SphxContext", "FluidParticleWorld", "TimeManager", "DFSPHSolver", "DFSPHMultiSolver", "default_params", "duration_from_secs_f32",
            "duration_as_secs_f32", "SphxError", "WCSPHSolver", "VISCOSITY_XSPH", "VISCOSITY_PHYSICAL", "SAMPLE_FIELDS", "gauge_elevation",
-           "render_fit", "write_png", "SCENE_RECT"]
+           "render_fit", "write_png", "SCENE_RECT", "TRACK_FIELDS"]
 
 
 def _p(a):
@@ -87,6 +87,24 @@ def _out_struct(outs, ptr):
     o = _lib.SphxSampleOut()
     for f, a in outs.items():
         setattr(o, f, ptr(a) or 1)  # (an empty tensor has no storage: a non-NULL dummy still names the field; nothing is written)
+    return o
+
+
+TRACK_FIELDS = ("slot", "pos", "vel", "density")
+
+
+def _track_outputs(fields, m):
+    fields = (fields,) if isinstance(fields, str) else tuple(fields)
+    bad = [f for f in fields if f not in TRACK_FIELDS]
+    if bad or not fields:
+        raise ValueError("fields must be a non-empty subset of %s, not %r" % (TRACK_FIELDS, fields))
+    return {f: np.zeros((m, 2) if f in ("pos", "vel") else (m,), np.uint32 if f == "slot" else np.float32) for f in fields}
+
+
+def _track_struct(outs):
+    o = _lib.SphxTrackOut()
+    for f, a in outs.items():
+        setattr(o, f, a.ctypes.data or 1)  # (an empty array: a non-NULL dummy still names the field; nothing is written)
     return o
 
 
@@ -326,6 +344,83 @@ class SphxContext:
         self._chk(self.L.sphx_download(self.h, _p(a_pos), _p(a_vel), _p(a_den), _p(a_ids)))
         out.update(pos=a_pos, vel=a_vel, density=a_den, ids=a_ids)
         return out
+
+    # ---- following particles by id (the contract is in include/sphx.h, "following particles by id") ----
+    def track(self, ids):
+        """sphx_track_set: the ids to follow (any order, duplicates allowed, at most _lib.TRACK_MAX_IDS; an empty sequence clears the
+        set).  Discards a recording."""
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        self._chk(self.L.sphx_track_set(self.h, _p(ids) if len(ids) else None, len(ids)))
+
+    def track_status(self):
+        """sphx_track_get_status -> dict(m, recording, max_frames, every, frames, dropped)."""
+        st = _lib.SphxTrackStatus()
+        self._chk(self.L.sphx_track_get_status(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_ if k != "reserved"}
+
+    def track_fetch(self, out=None, fields=TRACK_FIELDS):
+        """sphx_track_fetch: where the tracked particles are now, in the order of track(ids), without a download of the arrays.
+
+        out=None: returns {"slot": uint32 [m], "pos": float32 [m, 2], "vel": float32 [m, 2], "density": float32 [m]} (the requested
+        `fields`) as numpy arrays.  An id no particle carries has slot _lib.TRACK_ABSENT and NaN records (the word 0x7FC00000).
+        out={field: torch tensor on the context's device} (contiguous; slot int32, the others float32; the sizes above) selects the
+        device path: the library writes into the tensors on its own stream; torch's current stream is synchronised before the call
+        and the context's stream after it, as in sample().  Returns out."""
+        m = self.track_status()["m"]
+        if out is not None:
+            import torch
+
+            o = _lib.SphxTrackOut()
+            for f, t in out.items():
+                want = m * (2 if f in ("pos", "vel") else 1)
+                if f not in TRACK_FIELDS or not _is_torch(t) or t.device.type != "cuda" or not t.is_contiguous() or t.numel() != want or \
+                        t.dtype != (torch.int32 if f == "slot" else torch.float32):
+                    raise ValueError("out[%r] must be a contiguous %s cuda tensor of %d elements" % (f, "int32" if f == "slot" else "float32", want))
+                setattr(o, f, t.data_ptr() or 1)
+            torch.cuda.current_stream().synchronize()
+            self._chk(self.L.sphx_track_fetch(self.h, _lib.TRACK_DEVICE_POINTERS, C.byref(o)))
+            self.synchronize()
+            return out
+        outs = _track_outputs(fields, m)
+        self._chk(self.L.sphx_track_fetch(self.h, 0, C.byref(_track_struct(outs))))
+        return outs
+
+    def track_record(self, max_frames, every=1):
+        """sphx_track_record: from now on every `every`-th finished step stores {x, y, vx, vy} of the tracked ids on the device, up to
+        max_frames frames (later ones are counted in track_status()["dropped"]); max_frames=0 stops and frees.  Works inside
+        DFSPHSolver.simulation_steps(k) too: the frames are taken behind each step's kernels, nothing is synchronised."""
+        self._chk(self.L.sphx_track_record(self.h, max_frames, every))
+
+    def track_frames(self, first=0, count=None):
+        """sphx_track_read -> float32 [count, m, 4] = x, y, vx, vy of the recorded frames [first, first + count) (count=None: all from
+        `first`).  Waits for the context's stream."""
+        st = self.track_status()
+        if count is None:
+            count = max(st["frames"] - first, 0)
+        out = np.zeros((count, st["m"], 4), np.float32)
+        self._chk(self.L.sphx_track_read(self.h, first, count, 0, _p(out) if out.size else None))
+        return out
+
+    def ids_issued(self):
+        """The number of ids handed out since the last upload (the id the next append() would start from); 0 before any upload."""
+        first = C.c_uint32()
+        rc = self.L.sphx_append(self.h, None, None, 0, C.byref(first))  # (m == 0: a no-op that reports the next id)
+        if rc == _lib.ERR_NOT_READY:
+            return 0
+        self._chk(rc)
+        return first.value
+
+    def download_by_id(self, first=0, count=None, fields=TRACK_FIELDS):
+        """sphx_download_by_id: the particles with the ids first .. first + count - 1 in id order (count=None: up to the ids issued so
+        far) -> the dict of track_fetch() plus "present", the number of ids found.  After an unedited upload download_by_id() is the
+        particles in upload order, whatever the steps since."""
+        if count is None:
+            count = max(self.ids_issued() - first, 0)
+        outs = _track_outputs(fields, count)
+        present = C.c_uint32()
+        self._chk(self.L.sphx_download_by_id(self.h, first, count, 0, C.byref(_track_struct(outs)), C.byref(present)))
+        outs["present"] = present.value
+        return outs
 
     def download_boundary(self):
         xy = np.zeros((self.nb, 2), np.float32)
@@ -802,7 +897,15 @@ class DFSPHSolver:
             self.sync_world(world)
 
     def context(self):
-        """Borrowed SphxContext view (for inspection: neighbours, cells, solver state, profiling)."""
+        """Borrowed SphxContext view (for inspection: neighbours, cells, solver state, profiling — and for following particles: the
+        tracked set and the recorder live on the context, and the recorder fires behind every step of simulation_steps(k)):
+
+            ctx = solver.context()
+            ctx.track([0, 17, 4049])
+            ctx.track_record(max_frames=100)
+            solver.simulation_steps(world, timer, 100, sync_world=False)
+            paths = ctx.track_frames()  # [100, 3, 4] = x, y, vx, vy after each step
+        """
         ctx = SphxContext.__new__(SphxContext)
         ctx.L = self.L
         ctx.params = None

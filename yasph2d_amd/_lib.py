@@ -115,6 +115,21 @@ STATE_DEVICE_BUFFER = 1  # sphx_state_save / sphx_state_load flags
 STATE_SECTIONS = ("positions", "velocities", "particle_id", "density", "alpha", "kappa", "stiffness", "accel", "boundary")  # SPHX_STATE_SEC_*
 
 
+TRACK_DEVICE_POINTERS = 1  # sphx_track_fetch / sphx_track_read / sphx_download_by_id flags
+TRACK_MAX_IDS = 16384
+TRACK_ABSENT = 0xFFFFFFFF      # slot of an id no particle carries
+TRACK_ABSENT_WORD = 0x7FC00000  # ... and every float of its record
+
+
+class SphxTrackOut(C.Structure):
+    _fields_ = [("slot", C.c_void_p), ("pos", C.c_void_p), ("vel", C.c_void_p), ("density", C.c_void_p)]
+
+
+class SphxTrackStatus(C.Structure):
+    _fields_ = [("m", C.c_uint32), ("recording", C.c_uint32), ("max_frames", C.c_uint32), ("every", C.c_uint32), ("frames", C.c_uint32),
+                ("dropped", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 class SphxTimerState(C.Structure):
     _fields_ = [("fixed", C.c_uint32), ("cfl_factor", C.c_float), ("timestep_max_ns", C.c_uint64), ("timestep_min_ns", C.c_uint64),
                 ("simulation_step_ns", C.c_uint64), ("timestep_target_frame_ns", C.c_uint64), ("total_simulated_ns", C.c_uint64),
@@ -165,6 +180,12 @@ SIGNATURES = {
     "sphx_state_digest": (_i, [_vp, C.POINTER(_u64)]),
     "sphx_state_save_file": (_i, [_vp, C.c_char_p]),
     "sphx_state_load_file": (_i, [_vp, C.c_char_p]),
+    "sphx_track_set": (_i, [_vp, _vp, _u32]),
+    "sphx_track_fetch": (_i, [_vp, _u32, C.POINTER(SphxTrackOut)]),
+    "sphx_track_record": (_i, [_vp, _u32, _u32]),
+    "sphx_track_get_status": (_i, [_vp, C.POINTER(SphxTrackStatus)]),
+    "sphx_track_read": (_i, [_vp, _u32, _u32, _u32, _vp]),
+    "sphx_download_by_id": (_i, [_vp, _u32, _u32, _u32, C.POINTER(SphxTrackOut), C.POINTER(_u32)]),
     "sphx_download": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "sphx_download_boundary": (_i, [_vp, _vp, _vp]),
     "sphx_num_particles": (_u32, [_vp]),

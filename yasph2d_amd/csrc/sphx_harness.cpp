@@ -5,7 +5,12 @@
 //                [--gauges x1,x2,... [--gauge-range lo:hi:dy]]
 //                [--record DIR [--record-fps F] [--record-size WxH] [--record-min-pixel-radius P]]
 //                [--emit x,y,w,h[:every=K][:until=S][:vel=vx,vy]] [--drain x0,y0,x1,y1]... [--keep x0,y0,x1,y1]...
-//                [--load-state FILE] [--save-state FILE[:at=STEP]] [--help]
+//                [--load-state FILE] [--save-state FILE[:at=STEP]] [--track ID[,ID...] [--track-every E] --track-out FILE] [--help]
+//
+// --track: the particles with these ids (at most SPHX_TRACK_MAX_IDS) are followed on the device (sphx_track_set + sphx_track_record): a
+// frame {x, y, vx, vy} per id behind every E-th step (default 1; warm-up and timed steps counted together), nothing downloaded during the
+// run.  After the run --track-out FILE receives the CSV "frame,id,x,y,vx,vy" (one line per frame and id, in the order given; %.9g, which
+// round-trips fp32; "nan" for an id no particle carries at that time).  The JSON line gains "track_frames".
 //
 // --load-state / --save-state: the run picked up from and put down into a solver state file (sphx_solver_load / sphx_solver_save: the
 // context's blob and the timer's state).  --load-state FILE starts from the file instead of the scene (solver kind, viscosity and scale
@@ -97,9 +102,12 @@ static const char* const USAGE =
     "             [--gauges x1,x2,... [--gauge-range lo:hi:dy]]\n"
     "             [--record DIR [--record-fps F] [--record-size WxH] [--record-min-pixel-radius P]]\n"
     "             [--emit x,y,w,h[:every=K][:until=S][:vel=vx,vy]] [--drain x0,y0,x1,y1]... [--keep x0,y0,x1,y1]...\n"
-    "             [--load-state FILE] [--save-state FILE[:at=STEP]] [--help]\n"
+    "             [--load-state FILE] [--save-state FILE[:at=STEP]] [--track ID[,ID...] [--track-every E] --track-out FILE] [--help]\n"
     "  --load-state FILE            start from a solver state file (sphx_solver_load) instead of the scene\n"
     "  --save-state FILE[:at=STEP]  write a solver state file (sphx_solver_save) after STEP steps of this run; default: after the last step\n"
+    "  --track ID[,ID...]           follow these particle ids on the device (sphx_track_set + sphx_track_record), a frame behind every step\n"
+    "  --track-every E              ... behind every E-th step only (default 1)\n"
+    "  --track-out FILE             write the frames after the run as CSV: frame,id,x,y,vx,vy\n"
     "Prints one JSON line with the throughput, the timer's final step and a checksum of the final state.\n";
 
 static bool parse_list(const std::string& s, size_t count, bool allow_inf, double* out) {
@@ -132,6 +140,8 @@ int main(int argc, char** argv) {
     std::string load_state, save_state;
     bool want_load = false, want_save = false;
     long save_at = -1;  // (-1: after the last step)
+    std::string track_arg, track_every_arg, track_out;
+    bool want_track = false, want_track_every = false, want_track_out = false;
     auto add_rect = [&](std::vector<sphx_rect>& to, const char* opt, const std::string& arg) {
         double v[4];
         if (!parse_list(arg, 4, true, v) || drain_rects.size() + keep_rects.size() >= SPHX_REMOVE_MAX_RECTS) {
@@ -163,6 +173,9 @@ int main(int argc, char** argv) {
         else if (s == "--keep") add_rect(keep_rects, "--keep", next());
         else if (s == "--load-state") load_state = a + 1 < argc ? argv[++a] : "", want_load = true;
         else if (s == "--save-state") save_state = a + 1 < argc ? argv[++a] : "", want_save = true;
+        else if (s == "--track") track_arg = a + 1 < argc ? argv[++a] : "", want_track = true;
+        else if (s == "--track-every") track_every_arg = next(), want_track_every = true;
+        else if (s == "--track-out") track_out = a + 1 < argc ? argv[++a] : "", want_track_out = true;
         else if (s == "--help" || s == "-h") {
             std::fputs(USAGE, stdout);
             return 0;
@@ -189,6 +202,26 @@ int main(int argc, char** argv) {
     if (want_load && load_state.empty()) {
         std::fprintf(stderr, "invalid --load-state (FILE)\n");
         return 2;
+    }
+    std::vector<uint32_t> track_ids;
+    uint32_t track_every = 1;
+    if (want_track || want_track_every || want_track_out) {
+        bool ok = want_track && want_track_out && !track_arg.empty() && !track_out.empty();
+        for (size_t p = 0; ok && p <= track_arg.size();) {
+            const size_t q = std::min(track_arg.find(',', p), track_arg.size());
+            double v;
+            ok = parse_double(track_arg.substr(p, q - p), &v) && v >= 0.0 && v <= 4294967295.0 && v == std::floor(v) && track_ids.size() < SPHX_TRACK_MAX_IDS;
+            track_ids.push_back(ok ? (uint32_t)v : 0u);
+            p = q + 1;
+        }
+        double e = 1.0;
+        if (ok && want_track_every) ok = parse_double(track_every_arg, &e) && e >= 1.0 && e == std::floor(e) && e <= 4294967295.0;
+        track_every = (uint32_t)e;
+        if (!ok) {
+            std::fprintf(stderr, "invalid --track options (--track ID[,ID...] with at most %d whole numbers < 2^32, [--track-every E >= 1], --track-out FILE)\n",
+                         SPHX_TRACK_MAX_IDS);
+            return 2;
+        }
     }
     const bool wcsph = solver_kind == "wcsph";
     sph::FluidParticleWorld world(2.0f, 10000.0f, 100.0f);  // main.rs:85-89
@@ -299,6 +332,16 @@ int main(int argc, char** argv) {
         return 1;
     }
     const size_t n = world.particles.positions.size();
+    // the trajectory recorder: set and recording belong to the context, the upload of step 0 leaves them alone
+    const uint64_t track_max_frames = want_track ? (uint64_t)std::max(warmup + steps, 0l) / track_every : 0;
+    if (track_max_frames) {
+        int rc = track_max_frames > 0xFFFFFFFFull ? SPHX_ERR_CAPACITY : sphx_track_set(solver->ctx(), track_ids.data(), (uint32_t)track_ids.size());
+        if (rc == SPHX_OK) rc = sphx_track_record(solver->ctx(), (uint32_t)track_max_frames, track_every);
+        if (rc != SPHX_OK) {
+            std::fprintf(stderr, "--track failed: %s (status %d)\n", sphx_last_error(solver->ctx()), rc);
+            return 1;
+        }
+    }
     // recording mode
     sph::Camera camera = sph::Camera::center_around_world_rect(record_w, record_h, -0.1f * scale, -0.1f * scale, 2.1f * scale, 1.6f * scale);  // main.rs:137
     camera.view.min_pixel_radius = (float)record_mpr;
@@ -428,6 +471,32 @@ int main(int argc, char** argv) {
     if (want_record) {
         char buf[96];
         std::snprintf(buf, sizeof(buf), ", \"frames\": %llu, \"last_frame_fnv\": \"%016llx\"", (unsigned long long)frames, (unsigned long long)last_frame_fnv);
+        gauge_json += buf;
+    }
+    if (want_track) {
+        sphx_track_status ts{};
+        std::vector<float> fr;
+        int rc = sphx_track_get_status(solver->ctx(), &ts);
+        if (rc == SPHX_OK && ts.frames) {
+            fr.resize((size_t)ts.frames * ts.m * 4);
+            rc = sphx_track_read(solver->ctx(), 0u, ts.frames, 0u, fr.data());
+        }
+        if (rc != SPHX_OK) {
+            std::fprintf(stderr, "--track-out: %s (status %d)\n", sphx_last_error(solver->ctx()), rc);
+            return 1;
+        }
+        FILE* f = std::fopen(track_out.c_str(), "w");
+        bool ok = f != nullptr && std::fputs("frame,id,x,y,vx,vy\n", f) >= 0;
+        for (size_t k = 0; ok && k < (size_t)ts.frames * ts.m; ++k)
+            ok = std::fprintf(f, "%zu,%u,%.9g,%.9g,%.9g,%.9g\n", k / ts.m, track_ids[k % ts.m], (double)fr[4 * k], (double)fr[4 * k + 1], (double)fr[4 * k + 2],
+                              (double)fr[4 * k + 3]) > 0;
+        if (f) ok = std::fclose(f) == 0 && ok;
+        if (!ok) {
+            std::fprintf(stderr, "cannot write %s\n", track_out.c_str());
+            return 1;
+        }
+        char buf[64];
+        std::snprintf(buf, sizeof(buf), ", \"track_frames\": %u", ts.frames);
         gauge_json += buf;
     }
     if (want_edit) {

@@ -309,6 +309,16 @@ struct sphx_ctx {
     uint64_t ids_issued = 0;   // particles uploaded or appended since the last sphx_upload: the first id sphx_append hands out
     uint32_t* edit_buf = nullptr;  // sphx_remove: survivors per workgroup, then their exclusive scan and the total; grown on demand
     uint32_t edit_cap = 0;         // ... in 4-byte words
+    // particle tracking (sphx_track_*, sphx_download_by_id: sphx_track.inc).  Belongs to the context, not to the particle state.
+    struct Track {
+        uint32_t m = 0, unique = 0, log2_bits = 0;  // caller ids, distinct ids, log2 of the filter's bits
+        uint32_t* set_buf = nullptr;  // device: table[unique] | map[m] | filter[2^log2_bits / 32] | found[unique]
+        uint32_t *table = nullptr, *map = nullptr, *filter = nullptr, *found = nullptr;  // ... the pieces of set_buf
+        float* rec = nullptr;         // recording: max_frames frames of m {x, y, vx, vy}
+        uint32_t recording = 0, max_frames = 0, every = 0, frames = 0, dropped = 0, steps = 0;  // steps: finished since sphx_track_record
+        uint32_t* scratch = nullptr;  // window index of sphx_download_by_id + the outputs' device copies on the host-pointer paths
+        size_t scratch_cap = 0;       // ... in 4-byte words
+    } track;
     bool uploaded = false, boundary_changed = true, tails_dirty = true, in_step = false;
     bool lists_current = false;  // the neighbour lists were built from the positions the arrays hold (raised by a completed build, dropped with q_noclamp)
     unsigned long long* state_dig = nullptr;  // sphx_state_*: one digest per section (device), allocated on first use

@@ -3226,3 +3226,5 @@ __global__ __launch_bounds__(64) void k_publish(DevScalars* scal, Mailbox* mb, u
 #include "sphx_edit.inc"
 // a context saved into and restored from one blob (the section digest kernel + C ABI)
 #include "sphx_state.inc"
+// particles followed by id: look-up, id-ordered download, the trajectory recorder (kernels + C ABI)
+#include "sphx_track.inc"

@@ -708,6 +708,12 @@ static inline void sample_after_step(sphx_ctx* c) {
         sample_went_stale(c, "no neighbour build has run since the particles or the boundary changed (a step over zero fluid particles runs "
                              "none): call sphx_update_neighborhood + sphx_update_densities");
 }
+// The recorder of sphx_track_record (sphx_track.inc): a finished step tests one flag; with a recording on, a frame of the tracked set is
+// queued behind the step's kernels.
+void track_take_frame(sphx_ctx* c);
+static inline void track_after_step(sphx_ctx* c) {
+    if (c->track.recording) track_take_frame(c);
+}
 // Positions are about to change (or have changed) without the neighbour lists being rebuilt first: the walks go back to the forms
 // that are right for any distance (sqrt_dist in sphx_kernels.hip) until the next build.
 static inline void lists_went_stale(sphx_ctx* c) {
@@ -1564,6 +1570,7 @@ void sphx_destroy(sphx_ctx* c) {
     dev_free(&c->pid); dev_free(&c->pid2); dev_free(&c->key); dev_free(&c->slot); dev_free(&c->order);
     dev_free(&c->bpos); dev_free(&c->bpos2); dev_free(&c->bid); dev_free(&c->bid2); dev_free(&c->nb_list); dev_free(&c->nb_wave); dev_free(&c->nb_counts); dev_free(&c->nb_remote);
     dev_free(&c->scan_partials); dev_free(&c->scan_state); dev_free(&c->d_scal); dev_free(&c->tile_blk); dev_free(&c->sample_buf); dev_free(&c->render_buf); dev_free(&c->edit_buf); dev_free(&c->state_dig);
+    dev_free(&c->track.set_buf); dev_free(&c->track.rec); dev_free(&c->track.scratch);
     free_grid(c->gdyn);
     free_grid(c->gstat);
     if (c->mbox) hipHostFree((void*)c->mbox);
@@ -1906,6 +1913,7 @@ int sphx_step_finish(sphx_ctx* c, float dt, sphx_step_stats* out) {
     s.flags = c->step_flags;
     if (out) *out = s;
     sample_after_step(c);  // re-grid, densities (fused into the build) and the divergence loop, which moves no particle
+    track_after_step(c);
     return SPHX_OK;
 }
 
@@ -1985,6 +1993,7 @@ int sphx_wcsph_step_finish(sphx_ctx* c, float dt, sphx_step_stats* out) {
     s.flags = c->step_flags;
     if (out) *out = s;
     sample_after_step(c);  // phase A re-gridded the leap-frogged positions and took their Poly6 densities; leap frog 2 moves none
+    track_after_step(c);
     return SPHX_OK;
 }
 
