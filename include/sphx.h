@@ -439,6 +439,13 @@ int sphx_track_get_status(const sphx_ctx* ctx, sphx_track_status* out);
 int sphx_track_read(sphx_ctx* ctx, uint32_t first_frame, uint32_t n_frames, uint32_t flags, float* out /* [n_frames][m][4] = x, y, vx, vy */);
 int sphx_download_by_id(sphx_ctx* ctx, uint32_t first_id, uint32_t count, uint32_t flags, const sphx_track_out* out, uint32_t* out_present /* may be NULL */);
 
+/* Test aid for the zero-correction skip: cumulative numbers of correction workgroups that skipped their walk
+ * (out[0]), that a flag inside their window stopped (out[1]) and that a flag behind an out-of-window table line stopped (out[2]; a workgroup
+ * with a wavefront in the wide list format never looks further and is counted here too).
+ * Collected only by a context created with SPHX_ZERO_SKIP_COUNT=1 in the environment (all zero otherwise); the skip itself is on by
+ * default in a context of 4 M particles or more; SPHX_ZERO_SKIP=0 turns it off, =1 on at every size.  Waits for the stream. */
+int sphx_debug_correction_counts(sphx_ctx* ctx, uint64_t out[3]);
+
 /* ---- Solver trait (solver/mod.rs:12-18) ---------------------------------------------------------------------- */
 /* Solver::clear_cached_data (dfsph.rs:406-412) */
 int sphx_clear_cached(sphx_ctx* ctx);

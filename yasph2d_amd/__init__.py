@@ -457,6 +457,13 @@ class SphxContext:
     def last_flags(self):
         return self.L.sphx_last_flags(self.h)
 
+    def correction_counts(self):
+        """sphx_debug_correction_counts -> (skipped, stopped by a window flag, stopped by a remote entry): cumulative correction
+        workgroups of a context created with SPHX_ZERO_SKIP_COUNT=1 in the environment (all zero otherwise)."""
+        out = (C.c_uint64 * 3)()
+        self._chk(self.L.sphx_debug_correction_counts(self.h, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
     def grid_info(self, which=0):
         """Cell table behind the grid: covered blocks, table entries, directory extent (sphx_grid_info)."""
         out = (C.c_uint32 * 4)()

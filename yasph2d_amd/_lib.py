@@ -185,6 +185,7 @@ SIGNATURES = {
     "sphx_track_record": (_i, [_vp, _u32, _u32]),
     "sphx_track_get_status": (_i, [_vp, C.POINTER(SphxTrackStatus)]),
     "sphx_track_read": (_i, [_vp, _u32, _u32, _u32, _vp]),
+    "sphx_debug_correction_counts": (_i, [_vp, _vp]),
     "sphx_download_by_id": (_i, [_vp, _u32, _u32, _u32, C.POINTER(SphxTrackOut), C.POINTER(_u32)]),
     "sphx_download": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "sphx_download_boundary": (_i, [_vp, _vp, _vp]),

@@ -174,8 +174,13 @@ struct alignas(128) Stripe {
     // clears slot v + 2).
     unsigned long long res_hi, res_lo;
     uint32_t ticket;                // first-level arrival counter of the last-block reduction (two-pass scan only)
-    uint32_t pad[21];
+    uint32_t pad0;
+    // zero-correction skip (k_correct), cumulative, collected only with SPHX_ZERO_SKIP_COUNT=1: workgroups that skipped
+    // their walk / that a flag of their window stopped / that a flag behind an out-of-window table line stopped
+    unsigned long long zs_skipped, zs_window, zs_remote;
+    uint32_t pad[14];
 };
+static_assert(sizeof(Stripe) == 128, "one stripe, one cache line");
 // The max-velocity ring lives on cache lines of its own: the first density iteration READS it (velocity prediction folded into
 // compute_density_error) while workgroups of the same launch that have finished ADD their residual to Stripe — with both on one
 // line every one of those atomics sent the readers of that line back to the fabric (19.5 -> 31.7 us per launch at 1M particles
@@ -342,6 +347,15 @@ struct sphx_ctx {
     float2 *vel = nullptr, *vel2 = nullptr;    // [N|B] velocities (boundary tail: 0); after predict = the predicted velocities (dfsph.rs:484-492)
     sphx::PVr pv() const { return sphx::PVr{posA, vel}; }
     float* kbuf = nullptr;                     // [N] k = err * alpha of the running solver iteration: written by compute_error, staged by correct
+    // [N / 64] one word per wavefront of kbuf: some live lane's k is not +-0 (scratch, not state).  Written with kbuf by the single
+    // context's iterations; a correction whose whole reach is flag-free skips its walk (k_correct; SPHX_ZERO_SKIP=0 turns it off)
+    uint32_t* knz = nullptr;
+    bool div_knz_fused = false;                // the neighbour build that left kbuf (div_error_fused) left the flags too
+    // SPHX_ZERO_SKIP=0/1; -1: by size, on from 4 M particles.  (Measured: at 16 M the skipped walks are 4.7 % of the lattice step; at
+    // 1 M they are 2 %, and a step in which nothing can be skipped runs 3.6 % slower with the flags on — profiles/zero_skip/.)
+    int zero_skip = -1;
+    bool zero_skip_on() const { return zero_skip < 0 ? N >= 4000000u : zero_skip != 0; }
+    int zero_skip_count = 0;                   // SPHX_ZERO_SKIP_COUNT=1 (test aid: the three counters of Stripe)
     float2* accel = nullptr;                   // [N]
     float *density = nullptr, *alpha = nullptr, *alpha2 = nullptr, *kappa = nullptr, *stiff = nullptr;  // [N]
     float *kappa2 = nullptr, *stiff2 = nullptr;  // gather targets (tile mode only)

@@ -1380,8 +1380,16 @@ struct DivArgs {
     float2* velw;       // MODE 3: the own particle's velocity is corrected in place (nobody reads velocities in this launch)
     const float* warm;  // MODE 3: warm-start stiffness, slot-bound (dfsph.rs:316-344)
     float lim;          // MODE 3: -0.5 rho0^2, dfsph.rs:356-358
+    uint32_t* knz;      // MODE 2: per-wavefront "some k is not +-0" word, like k_compute_error (nullptr: not wanted)
 };
 __device__ __forceinline__ void block_residual_add(float e, DevScalars* __restrict__ scal);
+// The producers of kbuf[] also leave one word per wavefront: 1 when some live lane's k has a bit pattern other than +-0 (a NaN
+// counts), else 0.  A correction whose whole reach is free of flags has nothing to add to any velocity (k_correct).  Called by
+// every lane of the wavefront; dead lanes pass +0.  One ballot, one plain store by one lane.
+__device__ __forceinline__ void knz_store(uint32_t* __restrict__ knz, uint32_t i, uint32_t k_bits) {
+    const unsigned long long nz = __ballot((k_bits << 1) != 0u);
+    if ((threadIdx.x & 63u) == 0u) knz[i >> 6] = nz ? 1u : 0u;
+}
 // LDS byte address of a __shared__ object / a 32-bit store to one: the candidate scan keeps the ADDRESS of its next list row in a
 // register and moves it by one row per accepted candidate (one add instead of a clamp, a shift-add and an index add per candidate)
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
@@ -1624,6 +1632,7 @@ __device__ __forceinline__ void nb_tail(const float2* __restrict__ posA, uint32_
     }
     SPHX_STAMP(4)
     float div_err = 0.0f;
+    uint32_t k_bits = 0u;  // DIV: the bits of the k this lane stored (dead lanes: +0)
     if (FUSE && live) {
         const float gsx = gs2.x, gsy = gs2.y, wsx = ws.x, wsy = ws.y;
         const uint32_t i4 = i * 4u;  // (scalar base + 32-bit lane offset: contexts hold < 2^28 slots)
@@ -1635,10 +1644,15 @@ __device__ __forceinline__ void nb_tail(const float2* __restrict__ posA, uint32_
         store_cold((float*)((char*)alpha + i4), alpha_i, K.nt_cold);
         if (DIV) {
             const float e = ct < 9u ? 0.0f : fmaxf(delta * K.mass, 0.0f);  // dfsph.rs:261, :277-278
-            *(float*)((char*)dv.kbuf + i4) = e * alpha_i;  // (the warm-start stiffness is not zeroed here: the loop's first correction starts it from zero)
+            const float kv = e * alpha_i;
+            *(float*)((char*)dv.kbuf + i4) = kv;  // (the warm-start stiffness is not zeroed here: the loop's first correction starts it from zero)
+            k_bits = __float_as_uint(kv);
             div_err = tile_owns(K, pi.x, pi.y) ? e : 0.0f;
         }
         if (WARM) *(float2*)((char*)dv.velw + 2u * i4) = make_float2(vi.x - wsx * K.mass, vi.y - wsy * K.mass);  // dfsph.rs:342
+    }
+    if constexpr (DIV) {
+        if (dv.knz) knz_store(dv.knz, i, k_bits);
     }
     // ---- list rows ----------------------------------------------------------------------------------------------------------------
     uint32_t spill_rem = 0, spill_before = 0;
@@ -2755,12 +2769,13 @@ struct PredArgs {
     VmaxArgs va;
     TimerLaw law;
 };
-template <bool DIVERGENCE, bool PREDICT = false>
+template <bool DIVERGENCE, bool PREDICT = false, bool KNZ = false>
 __global__ TRAV_BOUNDS void k_compute_error(PVr PV, const float* __restrict__ density,
                                                         const float* __restrict__ alpha, uint32_t n, uint32_t soff, Consts K, float dt,
                                                         NbView nb, float* __restrict__ kbuf, float* __restrict__ warm_zero,
                                                         DevScalars* __restrict__ scal, const float* __restrict__ dt_dev, LoopArgs la,
-                                                        uint32_t* __restrict__ clear_hist, uint32_t clear_len, PredArgs pa) {
+                                                        uint32_t* __restrict__ clear_hist, uint32_t clear_len, PredArgs pa,
+                                                        uint32_t* __restrict__ knz) {
     // device-run loop: an iteration queued behind the one that met the residual test has nothing to do
     if (la.enabled && la.iter > 1u && scal->loop_done != 0u) return;
     if (dt_dev) dt = *dt_dev;
@@ -2820,6 +2835,7 @@ __global__ TRAV_BOUNDS void k_compute_error(PVr PV, const float* __restrict__ de
     }
     __syncthreads();
     float e = 0.0f, e_owned = 0.0f;
+    uint32_t k_bits = 0u;
     if (i < n) {
         const uint32_t ct = h.ct;
         float4 pvi = h.wide ? ldpv(PV, i) : take((i - h.lw0) * 4u);
@@ -2847,13 +2863,16 @@ __global__ TRAV_BOUNDS void k_compute_error(PVr PV, const float* __restrict__ de
                 e = fmaxf(K.rho0, e) - K.rho0;         // dfsph.rs:124
             }
         }
-        kbuf[i] = e * alpha_i;  // k = err * alpha: all the correction needs of a neighbour besides its position
+        const float kv = e * alpha_i;
+        kbuf[i] = kv;  // k = err * alpha: all the correction needs of a neighbour besides its position
+        k_bits = __float_as_uint(kv);
         // the predicted velocity of the own particle (staged with the window).  Stored HERE, behind the walk: a store in front of it
         // sits in the same counter as the walk's entry loads, and every wait for one of those waited for the store's acknowledge too
         if (PREDICT) pa.vel_out[i] = make_float2(pvi.z, pvi.w);
         if (warm_zero) warm_zero[i] = 0.0f;  // dfsph.rs:206-208 / 361-363 (callers whose first correction does not start from zero itself)
         e_owned = tile_owns(K, pvi.x, pvi.y) ? e : 0.0f;
     }
+    if constexpr (KNZ) knz_store(knz, i, k_bits);  // (the grid is rounded up to whole workgroups, and so is knz[])
     block_residual_add(e_owned, scal);  // read by the correction queued behind this launch (ResArgs)
 }
 
@@ -2868,12 +2887,29 @@ __global__ TRAV_BOUNDS void k_compute_error(PVr PV, const float* __restrict__ de
 // correction counts, and the host clears the histogram again when another iteration follows — unless the loop is run by the device
 // (LoopArgs): then the correction derives the verdict from the residual itself and only the last one counts.
 // hist == nullptr: plain correction.
-template <bool WARM, bool INV_DT, bool TILE = false>
+//
+// Zero-correction skip (knz != nullptr; WARM = false, TILE = false only).  When every k in a workgroup's reach is +-0
+// the walk computes an exact identity on the velocity: s = k_i + k_j = +-0, s grad W = +-0 (grad W is finite: the host passes knz
+// only with K.q_noclamp, lists built from these positions), the sums start from +0 and stay +0, (inv_dt 0) m = +0 for a positive
+// finite inv_dt and mass, and v - (+0) = v to the bit, v = -0 included.  The reach of a workgroup is its window — covered by the
+// flag words of the <= 9 wavefronts that overlap it — and the fluid records behind the lines of its out-of-window tables (boundary
+// records carry k = 0).  A workgroup whose reach is flag-free stages nothing, reads no list and stores no velocity: it adds k_i to
+// the warm-start sum and, in the density correction, advects its own particles for the cell count — the same operations on the
+// same values.  The flag words are requested in front of nb_head's loads and looked at behind them: a workgroup that finds a flag in
+// its window has paid nine scalar loads that ride with the head's own scalar load, and one scalar branch.
+struct ZeroSkipArgs {
+    const uint32_t* knz;  // nullptr: no workgroup skips
+    uint32_t count;       // SPHX_ZERO_SKIP_COUNT=1: add to Stripe::zs_* (test aid)
+};
+// ZS: the instantiation with the zero-correction skip's decision in it; a launch without flags runs the one without (the code from
+// before the skip, to the instruction).
+template <bool WARM, bool INV_DT, bool TILE = false, bool ZS = false>
 __global__ TRAV_BOUNDS void k_correct(float2* __restrict__ vel, const float2* __restrict__ posA, const float* __restrict__ kbuf,
                                                   float* __restrict__ warm, uint32_t n,
                                                   uint32_t soff, Consts K, float inv_dt, float lim, NbView nb,
                                                   const float* __restrict__ dt_dev, CountArgs ca, DevScalars* __restrict__ scal, LoopArgs la, ResArgs ra,
-                                                  uint32_t first, TileClassArgs tc) {
+                                                  uint32_t first, TileClassArgs tc, ZeroSkipArgs zs) {
+    static_assert(!ZS || (!WARM && !TILE), "the skip belongs to the plain corrections");
     float dt = WARM ? ca.dt : (la.enabled ? la.dt : ca.dt);
     if (dt_dev) {
         dt = *dt_dev;
@@ -2947,7 +2983,10 @@ __global__ TRAV_BOUNDS void k_correct(float2* __restrict__ vel, const float2* __
         NbStaged<StageRec> st;
         DirAhead ahead;
     };
-    auto load_block = [&](uint32_t blk) {
+    // (two parts: the head — list words, table lines, the own particle's words — and the staging loads.  Between them sits the
+    // zero-correction skip's decision: its flag words are requested in front of the head and looked at behind it, so a workgroup that
+    // walks has lost no round trip to them, and the table lines a clear window's second look needs are the head's)
+    auto load_head = [&](uint32_t blk) {
         Loaded L;
         L.blk = blk;
         L.i = blk * 256 + threadIdx.x;
@@ -2965,10 +3004,17 @@ __global__ TRAV_BOUNDS void k_correct(float2* __restrict__ vel, const float2* __
 #endif
         // first: the first correction of its loop — the accumulated warm-start value starts from zero (dfsph.rs:206-208 / :361-363):
         // nothing is read, and nobody had to write that zero either
-        L.warm_i = (L.i < n && !first) ? warm[L.i] : 0.0f;
+        // (clamped, not predicated on i < n: behind that branch the compiler also selects the count word — and waits for it there)
+        if constexpr (ZS)
+            L.warm_i = first ? 0.0f : warm[min(L.i, n ? n - 1u : 0u)];
+        else  // (the kernels without the skip's decision keep the predicated form they were tuned with)
+            L.warm_i = (L.i < n && !first) ? warm[L.i] : 0.0f;
         // (TILE — TileClassArgs in use: clamped, not predicated; behind a branch the compiler tests the owner bit inside it and waits there)
         L.id_i = TILE ? tc.pid[min(L.i, n - 1u)] : 0u;
-        L.st = nb_stage_load(L.h, nb, blk, L.i, n, load_rec, load_rec2);
+        return L;
+    };
+    auto load_stage = [&](Loaded& L) {
+        L.st = nb_stage_load(L.h, nb, L.blk, L.i, n, load_rec, load_rec2);
         L.ahead = DirAhead{0xFFFFFFFFu, EMPTY};
 #ifdef SPHX_CORRECT_POS_GLOBAL
         if (!WARM && INV_DT && ca.hist) {
@@ -2983,10 +3029,8 @@ __global__ TRAV_BOUNDS void k_correct(float2* __restrict__ vel, const float2* __
                 L.ahead = dir_ahead(ca.g, cx0, cy0);
             }
         }
-        return L;
     };
-    const Loaded LA = load_block(xcd_bid(K.rev, K.xcd_shift));
-    if (LA.h.lwlen) nb_stage_store(LA.h, LA.st, store_rec);
+    auto verdict = [&] {
     if (judge) {
         constexpr bool DIVERGENCE = !INV_DT;
         residual_wave_reduce(hi, lo);
@@ -3024,6 +3068,74 @@ __global__ TRAV_BOUNDS void k_correct(float2* __restrict__ vel, const float2* __
             publish_common(scal, ra.mb, ra.seq);
         }
     }
+    };
+    const uint32_t blk0 = xcd_bid(K.rev, K.xcd_shift);
+    // zero-correction skip, 1: the flag words of the wavefronts that overlap the window [lw0, lw0 + lwlen) of nb_head — contiguous, at
+    // most nine — requested here (scalar loads), looked at behind the head's loads
+    bool zs_try = false;
+    uint32_t zf[9] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    if constexpr (ZS) {
+        const uint32_t b0 = blk0 * 256u;
+        // (scalar conditions; inv_dt may have come from device memory: the host cannot vouch for it)
+        if (zs.knz && b0 < n && (!INV_DT || (inv_dt > 0.0f && inv_dt <= 3.402823466e38f))) {
+            zs_try = true;
+            const uint32_t lw0 = b0 > LIST_HALO ? b0 - LIST_HALO : 0u, lwend = min(b0 + 256u + LIST_HALO, n);
+            const uint32_t f0 = lw0 >> 6, f1 = (lwend - 1u) >> 6;
+            static_assert((LIST_WIN + 62u) / 64u + 1u <= 9u, "flag words of a window");
+#pragma unroll
+            for (uint32_t u = 0; u < 9u; ++u) zf[u] = zs.knz[min(f0 + u, f1)];
+        }
+    }
+    Loaded LA = load_head(blk0);
+    if constexpr (ZS) {
+        if (zs_try) {
+            if (zf[0] | zf[1] | zf[2] | zf[3] | zf[4] | zf[5] | zf[6] | zf[7] | zf[8]) {
+                if (zs.count && threadIdx.x == 0) atomicAdd(&scal->stripe[blockIdx.x % STRIPES].zs_window, 1ull);
+            } else {
+                // 2. a wavefront in the wide format gathers from anywhere: today's path.  3. the fluid records behind the lines of the
+                // out-of-window tables (every line in use belongs to some list entry of its wavefront; boundary records carry k = 0).
+                // The lines and the wavefront's word are the head's; what the skip needs of the own particle rides with the flags.
+                const NbHead& h = LA.h;
+                const uint32_t lane = threadIdx.x & 63u;
+                const uint32_t i = LA.i, ic = min(i, n - 1u);
+                const float ki = kbuf[ic];
+                const float2 pi = INV_DT ? gat(posA, ic) : make_float2(0.0f, 0.0f);
+                static_assert(WAVE_REMOTE == 128, "two halves of 64 lines");
+                uint32_t g1 = h.g[1];
+                if (nb.lazy_hi && h.R > 64u) g1 = h.rtab[lane + 64u];  // (nb_head leaves the upper half to nb_head_late)
+                uint32_t veto = h.wide ? 1u : 0u;
+                if (lane < h.R && h.g[0] < soff) veto |= zs.knz[h.g[0] >> 6];
+                if (lane + 64u < h.R && g1 < soff) veto |= zs.knz[g1 >> 6];
+                if (__syncthreads_or((int)veto)) {
+                    if (zs.count && threadIdx.x == 0) atomicAdd(&scal->stripe[blockIdx.x % STRIPES].zs_remote, 1ull);
+                } else {
+                    // 4. skip: no staging, no walk, no velocity store
+                    if (zs.count && threadIdx.x == 0) atomicAdd(&scal->stripe[blockIdx.x % STRIPES].zs_skipped, 1ull);
+                    verdict();
+                    float2 pnew = make_float2(0.0f, 0.0f);
+                    DirAhead ahead{0xFFFFFFFFu, EMPTY};
+                    if (i < n) {
+                        if (INV_DT) {
+                            if (ca.hist) {
+                                uint32_t cx0, cy0;
+                                cell_of(K, pi, cx0, cy0);
+                                ahead = dir_ahead(ca.g, cx0, cy0);
+                            }
+                            // dfsph.rs:499-510 on the velocity the walk would have stored back
+                            pnew = make_float2(pi.x + LA.pvi.z * dt, pi.y + LA.pvi.w * dt);
+                        }
+                        store_cold(&warm[i], LA.warm_i + ki, K.nt_cold);  // dfsph.rs:142 / :296
+                    }
+                    if (INV_DT)
+                        if (ca.hist) count_cell(K, ca.g, i < n, i, pnew, ca.hist, ca.cidx, ca.slot, 1u, scal, ahead);
+                    return;
+                }
+            }
+        }
+    }
+    load_stage(LA);
+    if (LA.h.lwlen) nb_stage_store(LA.h, LA.st, store_rec);
+    verdict();
     auto process = [&](const Loaded& L) {
     const uint32_t i = L.i, blk = L.blk;
     const NbHead& h = L.h;

@@ -833,6 +833,10 @@ int recover_directory(sphx_ctx* c, float advect_dt, uint32_t advect_below = 0xFF
     return cover_dynamic(c, xy.data(), (uint32_t)m, false);
 }
 
+// The per-wavefront "some k is not +-0" words for the producers of kbuf (k_compute_error, k_neighbor_build<2>): single context only,
+// nullptr with SPHX_ZERO_SKIP=0, and by default in a context of fewer than 4 M particles.
+inline uint32_t* zero_skip_flags(const sphx_ctx* c) { return c->zero_skip_on() && !c->tile_mode ? c->knz : nullptr; }
+
 // FluidParticleWorld::update_neighborhood_datastructure (fluidparticleworld.rs:235-261).
 // extra_alpha: also permute alpha_values (warm-up, dfsph.rs:425).  Velocities (vel[] — the predicted velocities inside a
 // step, dfsph.rs:512) and ids always follow.  advect_dt > 0: fuse the advection (dfsph.rs:499-510) into the re-grid.
@@ -943,6 +947,7 @@ int update_neighborhood(sphx_ctx* c, bool extra_alpha, float advect_dt, bool fus
         const uint32_t n = c->N;
         c->div_error_fused = false;
         c->div_warm_fused = false;
+        c->div_knz_fused = false;
         if (fuse && fuse_warm) {
             DivArgs dv{};
             dv.velw = c->vel;
@@ -957,6 +962,8 @@ int update_neighborhood(sphx_ctx* c, bool extra_alpha, float advect_dt, bool fus
             DivArgs dv{};
             dv.vel = (const float2*)c->vel;
             dv.kbuf = c->kbuf;
+            dv.knz = zero_skip_flags(c);
+            c->div_knz_fused = dv.knz != nullptr;
             launch(c, "neighbor_build+density_alpha+density_change", (8.0 + list_bytes(c) + 8.0 + 8.0 + 4.0) * n, [&] {
                 hipLaunchKernelGGL(k_neighbor_build<2>, dim3(nblocks(n)), dim3(256), 0, st, (const float2*)c->posA, n, c->soff(), c->K, c->gdyn.nview(),
                                    c->gstat.nview(), c->nb_list, c->nb_counts, c->nb_wave, c->nb_remote, c->density, c->alpha, c->d_scal, n_dev, dv);
@@ -1038,6 +1045,7 @@ int alloc_particles(sphx_ctx* c, uint32_t n, uint32_t cap = 0, bool keep_set = f
     if ((rc = dev_alloc(c, &c->p, cap))) return give_up(rc);
     A(accel) A(density) A(alpha) A(alpha2) A(kappa) A(stiff) A(kappa2) A(stiff2) A(pid) A(pid2) A(nb_counts) A(kbuf)
 #undef A
+    if ((rc = dev_alloc(c, &c->knz, (size_t)(nblocks(cap) + 8) * 4))) return give_up(rc);  // (one word per wavefront of the rounded-up grid, like nb_wave)
     if ((rc = dev_alloc(c, &c->nb_remote, (size_t)(nblocks(cap) + 8) * REMOTE_CAP))) return give_up(rc);
     if ((rc = dev_alloc(c, &c->nb_wave, (size_t)(nblocks(cap) + 8) * 4))) return give_up(rc);
     const size_t slices = ((size_t)cap + 63) / 64;
@@ -1079,52 +1087,76 @@ void launch_predict(sphx_ctx* c, const char* label, float dt, const VmaxArgs& va
 // prediction on the way, from accel[] into vel2[].  clear_hist: the cell count the previous iteration's correction left, wiped on the
 // way.  (No warm_zero array: the zeroing of dfsph.rs:206-208 / :361-363 is implicit, the first correction starts the sum from zero.)
 void launch_compute_error(sphx_ctx* c, bool divergence, float dt, const float* dt_dev, const LoopArgs& la, uint32_t* clear_hist, uint32_t clear_len,
-                          const PredArgs* pred) {
+                          const PredArgs* pred, uint32_t* knz) {
     const uint32_t n = c->N;
     hipStream_t st = c->stream;
     const dim3 g(nblocks(n)), b(256);
     const double lb = list_bytes(c);
     if (divergence) {
         launch(c, "compute_density_change", (16 + 4 + 4 + lb) * n, [&] {
-            hipLaunchKernelGGL((k_compute_error<true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt, c->nbv(),
-                               c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{});
+            if (knz)
+                hipLaunchKernelGGL((k_compute_error<true, false, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt, c->nbv(),
+                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz);
+            else
+                hipLaunchKernelGGL((k_compute_error<true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt, c->nbv(),
+                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz);
         });
     } else if (pred) {
         PredArgs pa = *pred;
         pa.accel = c->accel;
         pa.vel_out = c->vel2;
         launch(c, "velocity_prediction+compute_density_error", (16 + 8 + 8 + 4 + 4 + 4 + lb) * n, [&] {
-            hipLaunchKernelGGL((k_compute_error<false, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt,
-                               c->nbv(), c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, pa);
+            if (knz)
+                hipLaunchKernelGGL((k_compute_error<false, true, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt,
+                                   c->nbv(), c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, pa, knz);
+            else
+                hipLaunchKernelGGL((k_compute_error<false, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt,
+                                   c->nbv(), c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, pa, knz);
         });
     } else {
         launch(c, "compute_density_error", (16 + 4 + 4 + 4 + lb) * n + (clear_hist ? 4.0 * clear_len : 0.0), [&] {
-            hipLaunchKernelGGL((k_compute_error<false>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt, c->nbv(),
-                               c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{});
+            if (knz)
+                hipLaunchKernelGGL((k_compute_error<false, false, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt, c->nbv(),
+                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz);
+            else
+                hipLaunchKernelGGL((k_compute_error<false>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt, c->nbv(),
+                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz);
         });
     }
 }
 
 // correct_velocity_with_{density,divergence}_error (dfsph.rs:218 / :373).  ca.hist: the density correction also makes the next build's
 // cell count (+8 B per particle); tc.pid: and the tile's send classification (+4 B).
+// knz: the flags this iteration's producer wrote (nullptr: none) — handed to the kernel only where a skipped walk is an exact identity.
 void launch_correct(sphx_ctx* c, bool divergence, float dt, const float* dt_dev, const CountArgs& ca, const LoopArgs& la, const ResArgs& ra, bool first,
-                    const TileClassArgs& tc) {
+                    const TileClassArgs& tc, const uint32_t* knz) {
     const uint32_t n = c->N, f = first ? 1u : 0u;
     hipStream_t st = c->stream;
     const dim3 g(nblocks(n)), b(256);
     const float inv_dt = 1.0f / dt, lim = -0.5f * c->K.rho0 * c->K.rho0;
     float* warm = divergence ? c->stiff : c->kappa;
+    // (q_noclamp: the lists were built from these positions, every grad W is finite; a dt the device derives is tested by the kernel)
+    const bool skip_ok = knz && c->K.q_noclamp && !tc.pid && std::isfinite(c->K.mass) && c->K.mass > 0.0f &&
+                         (dt_dev || divergence || (inv_dt > 0.0f && std::isfinite(inv_dt)));
+    const ZeroSkipArgs zs{skip_ok ? knz : nullptr, c->zero_skip_count ? 1u : 0u};
     launch(c, divergence ? "correct_velocity_with_divergence_error" : "correct_velocity_with_density_error",
            (16 + 8 + 12 + 8 + list_bytes(c) + (ca.hist ? (tc.pid ? 8 + 4 : 8) : 0)) * n, [&] {
-               if (divergence)
+               // (a launch without flags runs the instantiation without the skip's decision: the code from before it)
+               if (divergence && zs.knz)
+                   hipLaunchKernelGGL((k_correct<false, false, false, true>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K,
+                                      inv_dt, lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, f, tc, zs);
+               else if (divergence)
                    hipLaunchKernelGGL((k_correct<false, false>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K, inv_dt,
-                                      lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, f, tc);
+                                      lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, f, tc, zs);
                else if (tc.pid)
                    hipLaunchKernelGGL((k_correct<false, true, true>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K,
-                                      inv_dt, lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, f, tc);
+                                      inv_dt, lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, f, tc, ZeroSkipArgs{});
+               else if (zs.knz)
+                   hipLaunchKernelGGL((k_correct<false, true, false, true>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K,
+                                      inv_dt, lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, f, tc, zs);
                else
                    hipLaunchKernelGGL((k_correct<false, true>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K, inv_dt,
-                                      lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, f, tc);
+                                      lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, f, tc, zs);
            });
 }
 
@@ -1137,10 +1169,10 @@ void launch_warmstart(sphx_ctx* c, bool divergence, float dt, const float* dt_de
     auto go = [&] {
         if (divergence)
             hipLaunchKernelGGL((k_correct<true, false>), g, b, 0, c->stream, c->vel, (const float2*)c->posA, (const float*)c->kbuf, c->stiff, n, c->soff(), c->K,
-                               inv_dt, lim, c->nbv(), dt_dev, CountArgs{}, c->d_scal, LoopArgs{}, ResArgs{}, 0u, TileClassArgs{});
+                               inv_dt, lim, c->nbv(), dt_dev, CountArgs{}, c->d_scal, LoopArgs{}, ResArgs{}, 0u, TileClassArgs{}, ZeroSkipArgs{});
         else
             hipLaunchKernelGGL((k_correct<true, true>), g, b, 0, c->stream, c->vel, (const float2*)c->posA, (const float*)c->kbuf, c->kappa, n, c->soff(), c->K,
-                               inv_dt, lim, c->nbv(), dt_dev, CountArgs{}, c->d_scal, LoopArgs{}, ResArgs{}, 0u, TileClassArgs{});
+                               inv_dt, lim, c->nbv(), dt_dev, CountArgs{}, c->d_scal, LoopArgs{}, ResArgs{}, 0u, TileClassArgs{}, ZeroSkipArgs{});
     };
     if (!labelled) return go();
     // own position + velocity read, velocity written, staged positions, warm-start values
@@ -1178,17 +1210,20 @@ uint32_t enqueue_iteration(sphx_ctx* c, const IterSpec& s) {
     }
     const uint32_t seq = ++c->seq;
     const ResArgs ra{1u, ++c->res_seq, c->mbox_dev, seq};  // the correction reads (and publishes) the residual its compute_error leaves
-    if (s.divergence && s.first && c->div_error_fused)  // the neighbour build has left this iteration's errors, residual and zeroed warm-start values
+    // the flags the correction may trust: the ones the producer of THIS iteration's kbuf wrote
+    uint32_t* knz = s.tc.pid ? nullptr : zero_skip_flags(c);
+    if (s.divergence && s.first && c->div_error_fused) {  // the neighbour build has left this iteration's errors, residual and zeroed warm-start values
         c->div_error_fused = false;
-    else
-        launch_compute_error(c, s.divergence, s.dt, s.dt_dev, s.la, s.clear_hist, s.clear_len, s.pred);
+        if (!c->div_knz_fused) knz = nullptr;
+    } else
+        launch_compute_error(c, s.divergence, s.dt, s.dt_dev, s.la, s.clear_hist, s.clear_len, s.pred, knz);
     if (s.pred) std::swap(c->vel, c->vel2);  // the predicted velocities are the velocities from here on (the boundary tail is zero in both)
     if (s.drop_count) drop_fused_count(c);
     if (s.ca.hist) {
         c->count_done = true;
         c->count_n = c->N;
     }
-    launch_correct(c, s.divergence, s.dt, s.dt_dev, s.ca, s.la, ra, s.first, s.tc);
+    launch_correct(c, s.divergence, s.dt, s.dt_dev, s.ca, s.la, ra, s.first, s.tc, knz);
     return seq;
 }
 
@@ -1425,6 +1460,21 @@ int sphx_default_params(float smoothing_factor, float particle_density, float fl
 
 const char* sphx_last_error(const sphx_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
+int sphx_debug_correction_counts(sphx_ctx* c, uint64_t out[3]) {
+    if (!c || !out) return SPHX_ERR_INVALID_ARGUMENT;
+    SPHX_HIP(c, hipSetDevice(c->device));
+    SPHX_HIP(c, hipStreamSynchronize(c->stream));
+    std::vector<Stripe> st(STRIPES);
+    SPHX_HIP(c, hipMemcpy(st.data(), c->d_scal->stripe, sizeof(Stripe) * STRIPES, hipMemcpyDeviceToHost));
+    out[0] = out[1] = out[2] = 0;
+    for (const Stripe& s : st) {
+        out[0] += s.zs_skipped;
+        out[1] += s.zs_window;
+        out[2] += s.zs_remote;
+    }
+    return SPHX_OK;
+}
+
 int sphx_create(const sphx_params* params, sphx_ctx** out) {
     if (!params || !out) return SPHX_ERR_INVALID_ARGUMENT;
     *out = nullptr;
@@ -1459,6 +1509,8 @@ int sphx_create(const sphx_params* params, sphx_ctx** out) {
     if (const char* e = std::getenv("SPHX_FUSE_DIV")) c->fuse_div = e[0] != '0';
     if (const char* e = std::getenv("SPHX_XCD_CHUNK")) c->xcd_chunk = (int)xcd_shift_clamp(std::atoi(e));  // log2(blocks per chunk); 0: contiguous eighths
     if (const char* e = std::getenv("SPHX_ALTERNATE_SWEEP")) c->alternate_sweep = e[0] == '2' ? 2 : (e[0] != '0');  // (0: every launch bottom-up; 2: the scatter toggles too — A/B forms)
+    if (const char* e = std::getenv("SPHX_ZERO_SKIP")) c->zero_skip = e[0] != '0';  // (0: no correction skips its walk, no flags are written; 1: also below 4 M particles)
+    if (const char* e = std::getenv("SPHX_ZERO_SKIP_COUNT")) c->zero_skip_count = e[0] == '1';  // (test aid: sphx_debug_correction_counts)
     if (const char* e = std::getenv("SPHX_FUSE_WARM")) c->fuse_warm = e[0] != '0';  // (A/B: the divergence warm start as a walk of its own behind k_neighbor_build<1>)
     c->P = *params;
     c->device = params->device;
@@ -1565,7 +1617,7 @@ void sphx_destroy(sphx_ctx* c) {
         hipEventDestroy(p.b);
     }
     for (auto e : c->ev_pool) hipEventDestroy(e);
-    dev_free(&c->posA); dev_free(&c->posA2); dev_free(&c->vel); dev_free(&c->vel2); dev_free(&c->kbuf); dev_free(&c->accel);
+    dev_free(&c->posA); dev_free(&c->posA2); dev_free(&c->vel); dev_free(&c->vel2); dev_free(&c->kbuf); dev_free(&c->knz); dev_free(&c->accel);
     dev_free(&c->density); dev_free(&c->alpha); dev_free(&c->alpha2); dev_free(&c->kappa); dev_free(&c->stiff); dev_free(&c->kappa2); dev_free(&c->stiff2);
     dev_free(&c->pid); dev_free(&c->pid2); dev_free(&c->key); dev_free(&c->slot); dev_free(&c->order);
     dev_free(&c->bpos); dev_free(&c->bpos2); dev_free(&c->bid); dev_free(&c->bid2); dev_free(&c->nb_list); dev_free(&c->nb_wave); dev_free(&c->nb_counts); dev_free(&c->nb_remote);
