@@ -18,7 +18,7 @@
  * What is the contract and what is scaffolding (the header has grown beyond the boundary SURVEY.md 8(b) asks for):
  *   STABLE — the drop-in boundary a Rust shim binds:
  *       lifecycle (sphx_default_params, sphx_create, sphx_destroy, sphx_last_error, sphx_abi_version), the particle-array
- *       surface (sphx_set_boundary, sphx_upload, sphx_append, sphx_remove, sphx_download*, sphx_num_*, sphx_view_*, sphx_sample_*, sphx_render*, sphx_state_*, sphx_track_*, sphx_download_by_id), the Solver trait (sphx_clear_cached,
+ *       surface (sphx_set_boundary, sphx_upload, sphx_append, sphx_remove, sphx_download*, sphx_num_*, sphx_view_*, sphx_sample_*, sphx_render*, sphx_state_*, sphx_track_*, sphx_download_by_id, sphx_particle_fields), the Solver trait (sphx_clear_cached,
  *       sphx_step_begin[_law], sphx_step_finish, sphx_wcsph_step_*), the same trait over a device list (sphx_multi_create[_rank],
  *       sphx_multi_destroy, sphx_multi_set_boundary, sphx_multi_upload, sphx_multi_clear_cached, sphx_multi_step_begin/finish,
  *       sphx_multi_simulation_step[s], sphx_multi_download, sphx_multi_num_owned, sphx_multi_last_error, sphx_comm_ops) and
@@ -58,7 +58,8 @@ extern "C" {
                             * 5 (additive): sphx_state_size / _save / _load / _digest / _save_file / _load_file, SPHX_STATE_*, sphx_timer_state,
                             *    sphx_timer_get_state / _set_state, sphx_solver_save / _load
                             * 5 (additive): sphx_track_set / _fetch / _record / _get_status / _read, sphx_download_by_id, sphx_track_out,
-                            *    sphx_track_status, SPHX_TRACK_* */
+                            *    sphx_track_status, SPHX_TRACK_*
+                            * 5 (additive): sphx_particle_fields, sphx_fields_out, SPHX_FIELDS_DEVICE_POINTERS */
 
 /* ---- status codes ---- */
 enum {
@@ -438,6 +439,48 @@ int sphx_track_record(sphx_ctx* ctx, uint32_t max_frames, uint32_t every);
 int sphx_track_get_status(const sphx_ctx* ctx, sphx_track_status* out);
 int sphx_track_read(sphx_ctx* ctx, uint32_t first_frame, uint32_t n_frames, uint32_t flags, float* out /* [n_frames][m][4] = x, y, vx, vy */);
 int sphx_download_by_id(sphx_ctx* ctx, uint32_t first_id, uint32_t count, uint32_t flags, const sphx_track_out* out, uint32_t* out_present /* may be NULL */);
+
+/* ---- per-particle flow fields: velocity gradient, divergence, vorticity and the colour-field gradient (csrc/sphx_fields.inc) ---------------
+ * What people derive from an SPH velocity field AT THE PARTICLES — vortex visualisation, what the divergence solver left behind, free-surface
+ * detection and surface normals — from one more traversal of the solver's own neighbour lists, run on request: 32 bytes per particle come
+ * out instead of sphx_download + sphx_download_neighbors and a host loop.  (sphx_sample_* cannot stand in: it interpolates at query points
+ * from cell scans and knows nothing of differences v_j - v_i over the solver's neighbour set.)
+ * The contract, for particle i (device order: the order of sphx_download, n = sphx_num_particles): walk the entries 0 .. count_total - 1 of
+ *   its neighbour list in list order — dynamic entries first, then static ones: exactly what sphx_download_neighbors returns; a list the
+ *   build capped at 64 entries (SPHX_FLAG_NEIGHBOR_CAP) stays capped, the fields see what the solver sees.  All arithmetic fp32 and unfused,
+ *   every sum starts at 0.0f and takes one rounding per operation:
+ *     dx = x_j.x - x_i.x, dy = x_j.y - x_i.y, d2 = dx*dx + dy*dy, r = sqrtf(d2) (correctly rounded), q = min(r * w_hinv, 1), omq = 1 - q,
+ *     s = ((w_ngrad*omq)*omq)*omq, gx = s*dx, gy = s*dy       (Kernel::gradient_from_positions(x_i, x_j), kernel.rs:23-28 with
+ *                                                              wendland_quintic_c2.rs:42-46; w_hinv, w_ngrad = sphx_get_constants out[0], out[2])
+ *     vol = m / rho_j for a fluid neighbour (rho_j = the density sphx_download returns), vol = m / rho0 and v_j = (0, 0) for a boundary one
+ *     ax = vol*gx, ay = vol*gy, dvx = v_j.x - v_i.x, dvy = v_j.y - v_i.y          (v = sphx_download's velocity)
+ *     Lxx = Lxx + dvx*ax, Lxy = Lxy + dvx*ay, Lyx = Lyx + dvy*ax, Lyy = Lyy + dvy*ay, cx = cx + ax, cy = cy + ay
+ *   and after the walk  vel_grad = {Lxx, Lxy, Lyx, Lyy} (d(vx)/dx, d(vx)/dy, d(vy)/dx, d(vy)/dy), divergence = Lxx + Lyy,
+ *   vorticity = Lyx - Lxy, color_grad = {cx, cy}.  color_grad is the gradient of the colour field: ~0 in the bulk and next to a wall, pointing
+ *   INTO the fluid at a free surface (|color_grad| * h of order 1 there; no threshold is built in).  A particle with an empty list gets zeros.
+ *   Any subset of the outputs gives the same bits as the full set.
+ * When the call is allowed: as for sphx_sample_* — the neighbour lists and density[] must belong to the current positions: after a finished
+ *   step of either solver that ran a neighbour build (not one over zero fluid particles), after sphx_update_neighborhood followed by
+ *   sphx_update_densities, and after a sphx_state_load of such a state.  After sphx_upload, sphx_set_boundary, sphx_append / sphx_remove (that
+ *   changed something), between a step_begin and its step_finish and after a failed step: SPHX_ERR_NOT_READY, with the messages of sampling.
+ *   A tile context (sphx_tile_*, sphx_multi_tile_ctx) is refused with SPHX_ERR_INVALID_ARGUMENT; sphx_multi_* has no counterpart.
+ * Argument errors (SPHX_ERR_INVALID_ARGUMENT, the message names the argument): ctx or out NULL, every output NULL, unknown flag bits.
+ *   n == 0 in a ready context is a successful no-op.
+ * No side effects: the call only reads (it restores the sweep direction a launch toggles and leaves a queued run-ahead pass valid); a run
+ *   with calls between its steps is bit-identical to one without — every sphx_state_digest word, every sphx_step_stats field, sphx_last_flags.
+ * SPHX_FIELDS_DEVICE_POINTERS: the outputs are device pointers on the context's device (4-byte alignment suffices); the call is enqueued
+ *   on the context's stream and does not wait.
+ *   Without it: host pointers; the call goes through a device scratch the library grows on demand for the requested outputs only and frees
+ *   in sphx_destroy, and returns when the outputs are written.
+ * Cost: the staged record of the non-pressure pass (position, velocity, one scalar), walked over count_total entries; DESIGN.md section 4h. */
+typedef struct sphx_fields_out {
+    float* vel_grad;    /* [4n]: d(vx)/dx, d(vx)/dy, d(vy)/dx, d(vy)/dy per particle, or NULL */
+    float* divergence;  /* [n] or NULL */
+    float* vorticity;   /* [n] or NULL */
+    float* color_grad;  /* [2n] interleaved xy, or NULL */
+} sphx_fields_out;      /* not all NULL */
+enum { SPHX_FIELDS_DEVICE_POINTERS = 1u };
+int sphx_particle_fields(sphx_ctx* ctx, uint32_t flags, const sphx_fields_out* out);
 
 /* Test aid for the zero-correction skip: cumulative numbers of correction workgroups that skipped their walk
  * (out[0]), that a flag inside their window stopped (out[1]) and that a flag behind an out-of-window table line stopped (out[2]; a workgroup

@@ -16,7 +16,7 @@ from ._lib import (FLAG_DENSITY_ITER_CAP, FLAG_DIVERGENCE_ITER_CAP, FLAG_DENSE_C
 
 __all__ = ["SphxContext", "FluidParticleWorld", "TimeManager", "DFSPHSolver", "DFSPHMultiSolver", "default_params", "duration_from_secs_f32",
            "duration_as_secs_f32", "SphxError", "WCSPHSolver", "VISCOSITY_XSPH", "VISCOSITY_PHYSICAL", "SAMPLE_FIELDS", "gauge_elevation",
-           "render_fit", "write_png", "SCENE_RECT", "TRACK_FIELDS"]
+           "render_fit", "write_png", "SCENE_RECT", "TRACK_FIELDS", "FIELD_NAMES"]
 
 
 def _p(a):
@@ -106,6 +106,19 @@ def _track_struct(outs):
     for f, a in outs.items():
         setattr(o, f, a.ctypes.data or 1)  # (an empty array: a non-NULL dummy still names the field; nothing is written)
     return o
+
+
+FIELD_NAMES = ("vel_grad", "divergence", "vorticity", "color_grad")
+_FIELD_WIDTH = dict(vel_grad=4, divergence=1, vorticity=1, color_grad=2)  # floats per particle
+_FIELD_SHAPE = dict(vel_grad=(2, 2), divergence=(), vorticity=(), color_grad=(2,))
+
+
+def _field_names(fields):
+    fields = (fields,) if isinstance(fields, str) else tuple(fields)
+    bad = [f for f in fields if f not in FIELD_NAMES]
+    if bad or not fields:
+        raise ValueError("fields must be a non-empty subset of %s, not %r" % (FIELD_NAMES, fields))
+    return fields
 
 
 SCENE_RECT = (-0.1, -0.1, 2.1, 1.6)  # the world rectangle the reference app's camera is fitted to (main.rs:137), at scale 1
@@ -383,6 +396,39 @@ class SphxContext:
             return out
         outs = _track_outputs(fields, m)
         self._chk(self.L.sphx_track_fetch(self.h, 0, C.byref(_track_struct(outs))))
+        return outs
+
+    def fields(self, fields=FIELD_NAMES, out=None):
+        """sphx_particle_fields: the velocity gradient, its divergence and vorticity, and the colour-field gradient at every particle, from
+        the solver's own neighbour lists (the contract is in include/sphx.h).  Device order: row i belongs to row i of download().
+
+        out=None: returns {name: numpy float32 array} for the requested `fields` — "vel_grad" [n, 2, 2] (d v_a / d x_b at [a, b]),
+        "divergence" [n], "vorticity" [n], "color_grad" [n, 2].  color_grad is ~0 in the bulk and points into the fluid at a free
+        surface (|color_grad| * h of order 1 there): a free-surface indicator and, negated and normalised, the surface normal.
+        out={name: torch tensor on the context's device} (contiguous float32, the sizes above) selects the device path: the library
+        writes into the tensors on its own stream; torch's current stream is synchronised before the call and the context's stream
+        after it, as in track_fetch().  Returns out.
+        Allowed where sample() is: after a finished step, or update_neighborhood() + update_densities()."""
+        n = self.n
+        if out is not None:
+            import torch
+
+            o = _lib.SphxFieldsOut()
+            for f, t in out.items():
+                want = n * _FIELD_WIDTH.get(f, 0)
+                if f not in FIELD_NAMES or not _is_torch(t) or t.device.type != "cuda" or not t.is_contiguous() or t.numel() != want or \
+                        t.dtype != torch.float32:
+                    raise ValueError("out[%r] must be a contiguous float32 cuda tensor of %d elements" % (f, want))
+                setattr(o, f, t.data_ptr() or 1)  # (an empty tensor has no storage: a non-NULL dummy still names the field; nothing is written)
+            torch.cuda.current_stream().synchronize()
+            self._chk(self.L.sphx_particle_fields(self.h, _lib.FIELDS_DEVICE_POINTERS, C.byref(o)))
+            self.synchronize()
+            return out
+        outs = {f: np.zeros((n,) + _FIELD_SHAPE[f], np.float32) for f in _field_names(fields)}
+        o = _lib.SphxFieldsOut()
+        for f, a in outs.items():
+            setattr(o, f, a.ctypes.data or 1)
+        self._chk(self.L.sphx_particle_fields(self.h, 0, C.byref(o)))
         return outs
 
     def track_record(self, max_frames, every=1):

@@ -130,6 +130,13 @@ class SphxTrackStatus(C.Structure):
                 ("dropped", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+FIELDS_DEVICE_POINTERS = 1  # sphx_particle_fields flags
+
+
+class SphxFieldsOut(C.Structure):
+    _fields_ = [("vel_grad", C.c_void_p), ("divergence", C.c_void_p), ("vorticity", C.c_void_p), ("color_grad", C.c_void_p)]
+
+
 class SphxTimerState(C.Structure):
     _fields_ = [("fixed", C.c_uint32), ("cfl_factor", C.c_float), ("timestep_max_ns", C.c_uint64), ("timestep_min_ns", C.c_uint64),
                 ("simulation_step_ns", C.c_uint64), ("timestep_target_frame_ns", C.c_uint64), ("total_simulated_ns", C.c_uint64),
@@ -185,6 +192,7 @@ SIGNATURES = {
     "sphx_track_record": (_i, [_vp, _u32, _u32]),
     "sphx_track_get_status": (_i, [_vp, C.POINTER(SphxTrackStatus)]),
     "sphx_track_read": (_i, [_vp, _u32, _u32, _u32, _vp]),
+    "sphx_particle_fields": (_i, [_vp, _u32, C.POINTER(SphxFieldsOut)]),
     "sphx_debug_correction_counts": (_i, [_vp, _vp]),
     "sphx_download_by_id": (_i, [_vp, _u32, _u32, _u32, C.POINTER(SphxTrackOut), C.POINTER(_u32)]),
     "sphx_download": (_i, [_vp, _vp, _vp, _vp, _vp]),

@@ -5,7 +5,12 @@
 //                [--gauges x1,x2,... [--gauge-range lo:hi:dy]]
 //                [--record DIR [--record-fps F] [--record-size WxH] [--record-min-pixel-radius P]]
 //                [--emit x,y,w,h[:every=K][:until=S][:vel=vx,vy]] [--drain x0,y0,x1,y1]... [--keep x0,y0,x1,y1]...
-//                [--load-state FILE] [--save-state FILE[:at=STEP]] [--track ID[,ID...] [--track-every E] --track-out FILE] [--help]
+//                [--load-state FILE] [--save-state FILE[:at=STEP]] [--track ID[,ID...] [--track-every E] --track-out FILE] [--fields-out FILE]
+//                [--help]
+//
+// --fields-out: after the last step, the per-particle flow fields of the final state (sphx_particle_fields: velocity divergence, vorticity
+// and the colour-field gradient, from the solver's own neighbour lists) as the CSV "id,x,y,divergence,vorticity,cx,cy", one line per
+// particle in device order (%.9g, which round-trips fp32).  The JSON line gains "fields_particles".
 //
 // --track: the particles with these ids (at most SPHX_TRACK_MAX_IDS) are followed on the device (sphx_track_set + sphx_track_record): a
 // frame {x, y, vx, vy} per id behind every E-th step (default 1; warm-up and timed steps counted together), nothing downloaded during the
@@ -102,12 +107,14 @@ static const char* const USAGE =
     "             [--gauges x1,x2,... [--gauge-range lo:hi:dy]]\n"
     "             [--record DIR [--record-fps F] [--record-size WxH] [--record-min-pixel-radius P]]\n"
     "             [--emit x,y,w,h[:every=K][:until=S][:vel=vx,vy]] [--drain x0,y0,x1,y1]... [--keep x0,y0,x1,y1]...\n"
-    "             [--load-state FILE] [--save-state FILE[:at=STEP]] [--track ID[,ID...] [--track-every E] --track-out FILE] [--help]\n"
+    "             [--load-state FILE] [--save-state FILE[:at=STEP]] [--track ID[,ID...] [--track-every E] --track-out FILE] [--fields-out FILE]\n"
+    "             [--help]\n"
     "  --load-state FILE            start from a solver state file (sphx_solver_load) instead of the scene\n"
     "  --save-state FILE[:at=STEP]  write a solver state file (sphx_solver_save) after STEP steps of this run; default: after the last step\n"
     "  --track ID[,ID...]           follow these particle ids on the device (sphx_track_set + sphx_track_record), a frame behind every step\n"
     "  --track-every E              ... behind every E-th step only (default 1)\n"
     "  --track-out FILE             write the frames after the run as CSV: frame,id,x,y,vx,vy\n"
+    "  --fields-out FILE            write the final state's flow fields (sphx_particle_fields) as CSV: id,x,y,divergence,vorticity,cx,cy\n"
     "Prints one JSON line with the throughput, the timer's final step and a checksum of the final state.\n";
 
 static bool parse_list(const std::string& s, size_t count, bool allow_inf, double* out) {
@@ -142,6 +149,8 @@ int main(int argc, char** argv) {
     long save_at = -1;  // (-1: after the last step)
     std::string track_arg, track_every_arg, track_out;
     bool want_track = false, want_track_every = false, want_track_out = false;
+    std::string fields_out;
+    bool want_fields = false;
     auto add_rect = [&](std::vector<sphx_rect>& to, const char* opt, const std::string& arg) {
         double v[4];
         if (!parse_list(arg, 4, true, v) || drain_rects.size() + keep_rects.size() >= SPHX_REMOVE_MAX_RECTS) {
@@ -176,6 +185,7 @@ int main(int argc, char** argv) {
         else if (s == "--track") track_arg = a + 1 < argc ? argv[++a] : "", want_track = true;
         else if (s == "--track-every") track_every_arg = next(), want_track_every = true;
         else if (s == "--track-out") track_out = a + 1 < argc ? argv[++a] : "", want_track_out = true;
+        else if (s == "--fields-out") fields_out = a + 1 < argc ? argv[++a] : "", want_fields = true;
         else if (s == "--help" || s == "-h") {
             std::fputs(USAGE, stdout);
             return 0;
@@ -201,6 +211,10 @@ int main(int argc, char** argv) {
     }
     if (want_load && load_state.empty()) {
         std::fprintf(stderr, "invalid --load-state (FILE)\n");
+        return 2;
+    }
+    if (want_fields && fields_out.empty()) {
+        std::fprintf(stderr, "invalid --fields-out (FILE)\n");
         return 2;
     }
     std::vector<uint32_t> track_ids;
@@ -497,6 +511,31 @@ int main(int argc, char** argv) {
         }
         char buf[64];
         std::snprintf(buf, sizeof(buf), ", \"track_frames\": %u", ts.frames);
+        gauge_json += buf;
+    }
+    if (want_fields) {
+        std::vector<float> div(n_final), vort(n_final), cg(2 * n_final);
+        sphx_fields_out fo{};
+        fo.divergence = div.data();
+        fo.vorticity = vort.data();
+        fo.color_grad = cg.data();
+        const int rc = sphx_particle_fields(solver->ctx(), 0u, &fo);
+        if (rc != SPHX_OK) {
+            std::fprintf(stderr, "--fields-out: %s (status %d)\n", sphx_last_error(solver->ctx()), rc);
+            return 1;
+        }
+        FILE* f = std::fopen(fields_out.c_str(), "w");
+        bool ok = f != nullptr && std::fputs("id,x,y,divergence,vorticity,cx,cy\n", f) >= 0;
+        for (size_t i = 0; ok && i < n_final; ++i)
+            ok = std::fprintf(f, "%u,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g\n", world.particles.particle_ids[i], (double)world.particles.positions[i].x,
+                              (double)world.particles.positions[i].y, (double)div[i], (double)vort[i], (double)cg[2 * i], (double)cg[2 * i + 1]) > 0;
+        if (f) ok = std::fclose(f) == 0 && ok;
+        if (!ok) {
+            std::fprintf(stderr, "cannot write %s\n", fields_out.c_str());
+            return 1;
+        }
+        char buf[64];
+        std::snprintf(buf, sizeof(buf), ", \"fields_particles\": %zu", n_final);
         gauge_json += buf;
     }
     if (want_edit) {

@@ -336,6 +336,8 @@ struct sphx_ctx {
     size_t sample_cap = 0;        // ... in 4-byte words
     uint32_t* render_buf = nullptr;  // sphx_render: one owner code per pixel (+ the outputs' device copies on the host-pointer path), grown on demand
     size_t render_cap = 0;           // ... in 4-byte words
+    float* fields_buf = nullptr;  // sphx_particle_fields: the requested outputs' device copies on the host-pointer path, grown on demand
+    size_t fields_cap = 0;        // ... in 4-byte words
     uint32_t num_density_iters = 1, num_divergence_iters = 0;  // dfsph.rs:51,55
     float step_dt_prev = 0, step_vmax = 0;
     uint32_t step_flags = 0;

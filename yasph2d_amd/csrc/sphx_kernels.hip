@@ -3340,3 +3340,5 @@ __global__ __launch_bounds__(64) void k_publish(DevScalars* scal, Mailbox* mb, u
 #include "sphx_state.inc"
 // particles followed by id: look-up, id-ordered download, the trajectory recorder (kernels + C ABI)
 #include "sphx_track.inc"
+// per-particle flow fields from the neighbour lists: velocity gradient, divergence, vorticity, colour gradient (kernel + C ABI)
+#include "sphx_fields.inc"
