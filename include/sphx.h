@@ -18,7 +18,7 @@
  * What is the contract and what is scaffolding (the header has grown beyond the boundary SURVEY.md 8(b) asks for):
  *   STABLE — the drop-in boundary a Rust shim binds:
  *       lifecycle (sphx_default_params, sphx_create, sphx_destroy, sphx_last_error, sphx_abi_version), the particle-array
- *       surface (sphx_set_boundary, sphx_upload, sphx_append, sphx_remove, sphx_download*, sphx_num_*, sphx_view_*, sphx_sample_*, sphx_render*, sphx_state_*, sphx_track_*, sphx_download_by_id, sphx_particle_fields), the Solver trait (sphx_clear_cached,
+ *       surface (sphx_set_boundary, sphx_upload, sphx_append, sphx_remove, sphx_download*, sphx_num_*, sphx_view_*, sphx_sample_*, sphx_render*, sphx_state_*, sphx_track_*, sphx_download_by_id, sphx_particle_fields, sphx_fluid_stats, sphx_stats_*), the Solver trait (sphx_clear_cached,
  *       sphx_step_begin[_law], sphx_step_finish, sphx_wcsph_step_*), the same trait over a device list (sphx_multi_create[_rank],
  *       sphx_multi_destroy, sphx_multi_set_boundary, sphx_multi_upload, sphx_multi_clear_cached, sphx_multi_step_begin/finish,
  *       sphx_multi_simulation_step[s], sphx_multi_download, sphx_multi_num_owned, sphx_multi_last_error, sphx_comm_ops) and
@@ -59,7 +59,9 @@ extern "C" {
                             *    sphx_timer_get_state / _set_state, sphx_solver_save / _load
                             * 5 (additive): sphx_track_set / _fetch / _record / _get_status / _read, sphx_download_by_id, sphx_track_out,
                             *    sphx_track_status, SPHX_TRACK_*
-                            * 5 (additive): sphx_particle_fields, sphx_fields_out, SPHX_FIELDS_DEVICE_POINTERS */
+                            * 5 (additive): sphx_particle_fields, sphx_fields_out, SPHX_FIELDS_DEVICE_POINTERS
+                            * 5 (additive): sphx_fluid_stats, sphx_stats_record / _get_status / _read, sphx_stats_rec, sphx_stats_frame,
+                            *    sphx_stats_status, SPHX_STATS_* */
 
 /* ---- status codes ---- */
 enum {
@@ -481,6 +483,80 @@ typedef struct sphx_fields_out {
 } sphx_fields_out;      /* not all NULL */
 enum { SPHX_FIELDS_DEVICE_POINTERS = 1u };
 int sphx_particle_fields(sphx_ctx* ctx, uint32_t flags, const sphx_fields_out* out);
+
+/* ---- fluid statistics: counts, sums, extremes, probe rectangles, time series (csrc/sphx_stats.inc) -----------------------------------------
+ * What an SPH user checks first — is the run healthy: total momentum and kinetic energy, where the fluid is (bounds, centre of mass), how
+ * compressed it is (density spread), whether anything has gone non-finite — from one streaming pass on the device, 20 bytes per particle,
+ * instead of a sphx_download and a host loop; and as a time series with nothing coming back to the host per step.  It also gives
+ * sphx_render_fit its world rectangle and tells how full a box is before sphx_remove drains it.
+ * Records: a call fills 1 + n_rects records.  Record 0 covers all N fluid particles (device order, the values sphx_download returns).
+ *   Record 1 + k covers the particles whose position is in rects[k] by sphx_remove's predicate
+ *     in(r, p) = p.x >= r.x0 && p.x < r.x1 && p.y >= r.y0 && p.y < r.y1
+ *   (IEEE comparisons, half-open: a NaN coordinate is in no rectangle, infinite bounds are allowed, x0 > x1 is an empty rectangle).
+ *   Rectangles may overlap; each record is independent of the others.  A particle with a non-finite x, y, vx or vy enters no sum and no
+ *   extreme: it is counted in `nonfinite` (of a rectangle record when its position passes the predicate).  Of the `count` finite particles
+ *   those with a finite density enter the density members and `density_count` — only while density[] belongs to the positions
+ *   (density_valid == 1: the state in which sphx_sample_* succeeds); otherwise density[] is not read, density_count = 0, the density sums
+ *   are 0 and the density extremes those of an empty record.
+ * Arithmetic: every term is formed in float64 from the float32 values exactly as the member comments say; a product of two converted
+ *   floats is exact in float64, so each term takes at most one rounding and fused and unfused evaluation give the same bits.  The ORDER
+ *   of a summation is not part of the contract; each sum S of n terms t satisfies |S - exact| <= n * 2^-52 * sum|t| (any-order recursive
+ *   summation errs by at most (n-1)u / (1 - (n-1)u) * sum|t|, u = 2^-53: less than half of that).  Counts, minima, maxima and max_speed_sq
+ *   are exact; among zeros of either sign a minimum is -0 if one is present and a maximum +0 if one is present.
+ * Determinism: two calls on the same state return identical bytes, on the host path and on the device-pointer path alike (no atomics:
+ *   the grid and every order of addition are functions of N alone); a recorded frame equals the call made at that moment.
+ * Physical quantities are the caller's: momentum = m * sum_vel, E_kin = m/2 * sum_speed_sq, E_pot = -m * (g . sum_pos), centre of mass
+ *   = sum_pos / count, angular momentum about c = m * (sum_angular - (c.x * sum_vel[1] - c.y * sum_vel[0])), density variance =
+ *   sum_density_sq / density_count - (sum_density / density_count)^2.
+ * When allowed: sphx_fluid_stats wherever sphx_download is (a pending advection is applied first, as in sphx_render) and before any upload
+ *   (N = 0: empty records); SPHX_ERR_NOT_READY between a step_begin and its step_finish (either solver).  Densities never make the call
+ *   fail.  A tile context (sphx_tile_*, sphx_multi_tile_ctx) is refused with SPHX_ERR_INVALID_ARGUMENT; sphx_multi_* has no counterpart.
+ * Argument errors (SPHX_ERR_INVALID_ARGUMENT, the message names the argument): ctx, out or status NULL, rects NULL with n_rects > 0,
+ *   n_rects > SPHX_STATS_MAX_RECTS, a NaN bound, unknown flag bits, a device `out` that is not 8-byte aligned.
+ * SPHX_STATS_DEVICE_POINTERS: `out` is device memory on the context's device, 8-byte aligned; the call is enqueued on the context's
+ *   stream and does not wait.  Without it: host memory; the call goes through a small device scratch (allocated on first use, freed in
+ *   sphx_destroy) and returns when the records are written.  `rects` is host memory either way (copied).
+ * Recording: after sphx_stats_record(rects, n_rects, max_frames, every) every every-th SUCCESSFULLY finished step (either solver, counted
+ *   from the call; so also each step inside sphx_solver_simulation_steps) enqueues one frame of 1 + n_rects records behind its own
+ *   kernels.  Nothing comes back to the host and nothing is synchronised.  The library keeps one sphx_stats_frame per frame on the host:
+ *   step = finished steps since the call (1-based), dt = the dt given to that step_finish, n = the particle count at that moment.  A
+ *   failed step takes no frame and does not count.  Once max_frames frames are stored, later frames are counted in `dropped`.
+ *   max_frames == 0 stops and frees; every == 0 is SPHX_ERR_INVALID_ARGUMENT; a buffer (max_frames * (1 + n_rects) * 128 bytes) above
+ *   64 MiB is SPHX_ERR_CAPACITY; a new sphx_stats_record discards the old recording.  sphx_stats_read copies the frames [first_frame,
+ *   first_frame + n_frames) and waits for the stream; a range beyond `frames` is SPHX_ERR_INVALID_ARGUMENT.  Record, read: SPHX_ERR_NOT_READY
+ *   inside an open step, a tile context is refused.
+ * Lifetime: the recording belongs to the CONTEXT: sphx_upload, sphx_append, sphx_remove and sphx_state_load leave it alone (frames simply
+ *   see the new particle set); sphx_state_save does not store it.
+ * No side effects: all of this only reads the particle state.  A run with stats calls and a recording between its steps is bit-identical
+ *   to the same run without them — every sphx_state_digest word, every sphx_step_stats field, sphx_last_flags — and a queued run-ahead
+ *   pass stays valid.
+ * Cost: two launches; pos, vel and (while valid) density are streamed once, rectangles are decided per wavefront (the particles are
+ *   cell-sorted, so a wavefront that lies outside a rectangle skips it); DESIGN.md section 4i. */
+#define SPHX_STATS_MAX_RECTS 8
+enum { SPHX_STATS_DEVICE_POINTERS = 1u };
+typedef struct sphx_stats_rec {      /* 128 bytes, every member naturally aligned */
+    uint64_t count;                  /*   0: finite particles of this record */
+    uint64_t nonfinite;              /*   8: particles with a non-finite x, y, vx or vy (in no sum, no extreme) */
+    uint64_t density_count;          /*  16: of `count`, those whose density is finite (0 when !density_valid) */
+    uint32_t density_valid;          /*  24: 1 iff density[] belonged to the positions (the state in which sphx_sample_* succeeds) */
+    uint32_t reserved;               /*  28: 0 */
+    double sum_pos[2];               /*  32: sum (double)x, sum (double)y */
+    double sum_vel[2];               /*  48 */
+    double sum_speed_sq;             /*  64: sum of t = (double)vx*(double)vx + (double)vy*(double)vy */
+    double sum_angular;              /*  72: sum of (double)x*(double)vy - (double)y*(double)vx  (about the origin) */
+    double sum_density;              /*  80 */
+    double sum_density_sq;           /*  88: sum of (double)rho*(double)rho */
+    double max_speed_sq;             /*  96: max of t; 0 for an empty record */
+    float min_pos[2], max_pos[2];    /* 104, 112: +INFINITY / -INFINITY for an empty record */
+    float min_density, max_density;  /* 120, 124: likewise */
+} sphx_stats_rec;
+typedef struct sphx_stats_frame { uint64_t step; float dt; uint32_t n; } sphx_stats_frame;   /* 16 bytes */
+typedef struct sphx_stats_status { uint32_t n_rects, recording, max_frames, every, frames, dropped, reserved[2]; } sphx_stats_status;
+int sphx_fluid_stats(sphx_ctx* ctx, const sphx_rect* rects /* host */, uint32_t n_rects, uint32_t flags, sphx_stats_rec* out /* [1 + n_rects] */);
+int sphx_stats_record(sphx_ctx* ctx, const sphx_rect* rects /* host */, uint32_t n_rects, uint32_t max_frames, uint32_t every);
+int sphx_stats_get_status(const sphx_ctx* ctx, sphx_stats_status* out);
+int sphx_stats_read(sphx_ctx* ctx, uint32_t first_frame, uint32_t n_frames, sphx_stats_rec* out /* host, [n_frames][1 + n_rects] */,
+                    sphx_stats_frame* info /* host, [n_frames], may be NULL */);
 
 /* Test aid for the zero-correction skip: cumulative numbers of correction workgroups that skipped their walk
  * (out[0]), that a flag inside their window stopped (out[1]) and that a flag behind an out-of-window table line stopped (out[2]; a workgroup

@@ -16,7 +16,7 @@ from ._lib import (FLAG_DENSITY_ITER_CAP, FLAG_DIVERGENCE_ITER_CAP, FLAG_DENSE_C
 
 __all__ = ["SphxContext", "FluidParticleWorld", "TimeManager", "DFSPHSolver", "DFSPHMultiSolver", "default_params", "duration_from_secs_f32",
            "duration_as_secs_f32", "SphxError", "WCSPHSolver", "VISCOSITY_XSPH", "VISCOSITY_PHYSICAL", "SAMPLE_FIELDS", "gauge_elevation",
-           "render_fit", "write_png", "SCENE_RECT", "TRACK_FIELDS", "FIELD_NAMES"]
+           "render_fit", "write_png", "SCENE_RECT", "TRACK_FIELDS", "FIELD_NAMES", "STATS_DTYPE", "STATS_FRAME_DTYPE"]
 
 
 def _p(a):
@@ -119,6 +119,14 @@ def _field_names(fields):
     if bad or not fields:
         raise ValueError("fields must be a non-empty subset of %s, not %r" % (FIELD_NAMES, fields))
     return fields
+
+
+# one record of sphx_fluid_stats (sphx_stats_rec, 128 bytes) and one frame entry of the recorder (sphx_stats_frame, 16 bytes)
+STATS_DTYPE = np.dtype([("count", "<u8"), ("nonfinite", "<u8"), ("density_count", "<u8"), ("density_valid", "<u4"), ("reserved", "<u4"),
+                        ("sum_pos", "<f8", (2,)), ("sum_vel", "<f8", (2,)), ("sum_speed_sq", "<f8"), ("sum_angular", "<f8"),
+                        ("sum_density", "<f8"), ("sum_density_sq", "<f8"), ("max_speed_sq", "<f8"), ("min_pos", "<f4", (2,)),
+                        ("max_pos", "<f4", (2,)), ("min_density", "<f4"), ("max_density", "<f4")])
+STATS_FRAME_DTYPE = np.dtype([("step", "<u8"), ("dt", "<f4"), ("n", "<u4")])
 
 
 SCENE_RECT = (-0.1, -0.1, 2.1, 1.6)  # the world rectangle the reference app's camera is fitted to (main.rs:137), at scale 1
@@ -430,6 +438,55 @@ class SphxContext:
             setattr(o, f, a.ctypes.data or 1)
         self._chk(self.L.sphx_particle_fields(self.h, 0, C.byref(o)))
         return outs
+
+    # ---- fluid statistics (the contract is in include/sphx.h, "fluid statistics") ----
+    def stats(self, rects=(), out=None):
+        """sphx_fluid_stats: counts, float64 sums and exact extremes of the whole fluid (record 0) and of the particles inside each of up
+        to _lib.STATS_MAX_RECTS rectangles (record 1 + k; (x0, y0, x1, y1) tuples, half-open, bounds may be infinite), from one
+        streaming pass on the device.
+
+        out=None: returns a numpy structured array [1 + len(rects)] of STATS_DTYPE.
+        out=a contiguous torch uint8 tensor of (1 + len(rects)) * 128 bytes on the context's device selects the device path: the
+        library writes the records into it on its own stream; torch's current stream is synchronised before the call and the
+        context's stream after it, as in track_fetch().  Returns out (out.cpu().numpy().view(STATS_DTYPE) reads it).
+        Momentum = m * sum_vel, E_kin = m / 2 * sum_speed_sq, E_pot = -m * (g . sum_pos)."""
+        arr, k = _rect_array(rects)
+        if out is not None:
+            import torch
+
+            if not _is_torch(out) or out.device.type != "cuda" or not out.is_contiguous() or out.dtype != torch.uint8 or \
+                    out.numel() != (1 + k) * STATS_DTYPE.itemsize:
+                raise ValueError("out must be a contiguous uint8 cuda tensor of %d bytes" % ((1 + k) * STATS_DTYPE.itemsize))
+            torch.cuda.current_stream().synchronize()
+            self._chk(self.L.sphx_fluid_stats(self.h, arr, k, _lib.STATS_DEVICE_POINTERS, out.data_ptr()))
+            self.synchronize()
+            return out
+        rec = np.zeros(1 + k, STATS_DTYPE)
+        self._chk(self.L.sphx_fluid_stats(self.h, arr, k, 0, _p(rec)))
+        return rec
+
+    def stats_record(self, rects, max_frames, every=1):
+        """sphx_stats_record: from now on every `every`-th finished step stores one frame of stats(rects) on the device, up to max_frames
+        frames (later ones are counted in stats_status()["dropped"]); max_frames=0 stops and frees.  Nothing is synchronised."""
+        arr, k = _rect_array(rects)
+        self._chk(self.L.sphx_stats_record(self.h, arr, k, max_frames, every))
+
+    def stats_status(self):
+        """sphx_stats_get_status -> dict(n_rects, recording, max_frames, every, frames, dropped)."""
+        st = _lib.SphxStatsStatus()
+        self._chk(self.L.sphx_stats_get_status(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_ if k != "reserved"}
+
+    def stats_frames(self, first=0, count=None):
+        """sphx_stats_read -> (records [count, 1 + n_rects] of STATS_DTYPE, info [count] of STATS_FRAME_DTYPE: step, dt, n) for the
+        recorded frames [first, first + count) (count=None: all from `first`).  Waits for the context's stream."""
+        st = self.stats_status()
+        if count is None:
+            count = max(st["frames"] - first, 0)
+        rec = np.zeros((count, 1 + st["n_rects"]), STATS_DTYPE)
+        info = np.zeros(count, STATS_FRAME_DTYPE)
+        self._chk(self.L.sphx_stats_read(self.h, first, count, _p(rec) if count else None, _p(info) if count else None))
+        return rec, info
 
     def track_record(self, max_frames, every=1):
         """sphx_track_record: from now on every `every`-th finished step stores {x, y, vx, vy} of the tracked ids on the device, up to

@@ -137,6 +137,26 @@ class SphxFieldsOut(C.Structure):
     _fields_ = [("vel_grad", C.c_void_p), ("divergence", C.c_void_p), ("vorticity", C.c_void_p), ("color_grad", C.c_void_p)]
 
 
+STATS_DEVICE_POINTERS = 1  # sphx_fluid_stats flags
+STATS_MAX_RECTS = 8
+
+
+class SphxStatsRec(C.Structure):  # 128 bytes
+    _fields_ = [("count", C.c_uint64), ("nonfinite", C.c_uint64), ("density_count", C.c_uint64), ("density_valid", C.c_uint32),
+                ("reserved", C.c_uint32), ("sum_pos", C.c_double * 2), ("sum_vel", C.c_double * 2), ("sum_speed_sq", C.c_double),
+                ("sum_angular", C.c_double), ("sum_density", C.c_double), ("sum_density_sq", C.c_double), ("max_speed_sq", C.c_double),
+                ("min_pos", C.c_float * 2), ("max_pos", C.c_float * 2), ("min_density", C.c_float), ("max_density", C.c_float)]
+
+
+class SphxStatsFrame(C.Structure):  # 16 bytes
+    _fields_ = [("step", C.c_uint64), ("dt", C.c_float), ("n", C.c_uint32)]
+
+
+class SphxStatsStatus(C.Structure):
+    _fields_ = [("n_rects", C.c_uint32), ("recording", C.c_uint32), ("max_frames", C.c_uint32), ("every", C.c_uint32), ("frames", C.c_uint32),
+                ("dropped", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 class SphxTimerState(C.Structure):
     _fields_ = [("fixed", C.c_uint32), ("cfl_factor", C.c_float), ("timestep_max_ns", C.c_uint64), ("timestep_min_ns", C.c_uint64),
                 ("simulation_step_ns", C.c_uint64), ("timestep_target_frame_ns", C.c_uint64), ("total_simulated_ns", C.c_uint64),
@@ -193,6 +213,10 @@ SIGNATURES = {
     "sphx_track_get_status": (_i, [_vp, C.POINTER(SphxTrackStatus)]),
     "sphx_track_read": (_i, [_vp, _u32, _u32, _u32, _vp]),
     "sphx_particle_fields": (_i, [_vp, _u32, C.POINTER(SphxFieldsOut)]),
+    "sphx_fluid_stats": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32, _vp]),
+    "sphx_stats_record": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32, _u32]),
+    "sphx_stats_get_status": (_i, [_vp, C.POINTER(SphxStatsStatus)]),
+    "sphx_stats_read": (_i, [_vp, _u32, _u32, _vp, _vp]),
     "sphx_debug_correction_counts": (_i, [_vp, _vp]),
     "sphx_download_by_id": (_i, [_vp, _u32, _u32, _u32, C.POINTER(SphxTrackOut), C.POINTER(_u32)]),
     "sphx_download": (_i, [_vp, _vp, _vp, _vp, _vp]),

@@ -6,7 +6,13 @@
 //                [--record DIR [--record-fps F] [--record-size WxH] [--record-min-pixel-radius P]]
 //                [--emit x,y,w,h[:every=K][:until=S][:vel=vx,vy]] [--drain x0,y0,x1,y1]... [--keep x0,y0,x1,y1]...
 //                [--load-state FILE] [--save-state FILE[:at=STEP]] [--track ID[,ID...] [--track-every E] --track-out FILE] [--fields-out FILE]
+//                [--stats-out FILE [--stats-every K]]
 //                [--help]
+//
+// --stats-out: the statistics of the whole fluid (sphx_fluid_stats, record 0) are recorded on the device behind every K-th step of the
+// run (sphx_stats_record; --stats-every K, default 1; warm-up and timed steps counted together) and written after the run, one JSON
+// object per line and frame: step, dt, n and the members of sphx_stats_rec (%.17g, which round-trips float64).  The JSON line of the
+// run gains "stats_frames".
 //
 // --fields-out: after the last step, the per-particle flow fields of the final state (sphx_particle_fields: velocity divergence, vorticity
 // and the colour-field gradient, from the solver's own neighbour lists) as the CSV "id,x,y,divergence,vorticity,cx,cy", one line per
@@ -108,12 +114,15 @@ static const char* const USAGE =
     "             [--record DIR [--record-fps F] [--record-size WxH] [--record-min-pixel-radius P]]\n"
     "             [--emit x,y,w,h[:every=K][:until=S][:vel=vx,vy]] [--drain x0,y0,x1,y1]... [--keep x0,y0,x1,y1]...\n"
     "             [--load-state FILE] [--save-state FILE[:at=STEP]] [--track ID[,ID...] [--track-every E] --track-out FILE] [--fields-out FILE]\n"
+    "             [--stats-out FILE [--stats-every K]]\n"
     "             [--help]\n"
     "  --load-state FILE            start from a solver state file (sphx_solver_load) instead of the scene\n"
     "  --save-state FILE[:at=STEP]  write a solver state file (sphx_solver_save) after STEP steps of this run; default: after the last step\n"
     "  --track ID[,ID...]           follow these particle ids on the device (sphx_track_set + sphx_track_record), a frame behind every step\n"
     "  --track-every E              ... behind every E-th step only (default 1)\n"
     "  --track-out FILE             write the frames after the run as CSV: frame,id,x,y,vx,vy\n"
+    "  --stats-out FILE             record the whole fluid's statistics (sphx_stats_record) behind every step, write one JSON line per frame\n"
+    "  --stats-every K              ... behind every K-th step only (default 1)\n"
     "  --fields-out FILE            write the final state's flow fields (sphx_particle_fields) as CSV: id,x,y,divergence,vorticity,cx,cy\n"
     "Prints one JSON line with the throughput, the timer's final step and a checksum of the final state.\n";
 
@@ -149,6 +158,8 @@ int main(int argc, char** argv) {
     long save_at = -1;  // (-1: after the last step)
     std::string track_arg, track_every_arg, track_out;
     bool want_track = false, want_track_every = false, want_track_out = false;
+    std::string stats_out, stats_every_arg;
+    bool want_stats = false, want_stats_every = false;
     std::string fields_out;
     bool want_fields = false;
     auto add_rect = [&](std::vector<sphx_rect>& to, const char* opt, const std::string& arg) {
@@ -185,6 +196,8 @@ int main(int argc, char** argv) {
         else if (s == "--track") track_arg = a + 1 < argc ? argv[++a] : "", want_track = true;
         else if (s == "--track-every") track_every_arg = next(), want_track_every = true;
         else if (s == "--track-out") track_out = a + 1 < argc ? argv[++a] : "", want_track_out = true;
+        else if (s == "--stats-out") stats_out = a + 1 < argc ? argv[++a] : "", want_stats = true;
+        else if (s == "--stats-every") stats_every_arg = next(), want_stats_every = true;
         else if (s == "--fields-out") fields_out = a + 1 < argc ? argv[++a] : "", want_fields = true;
         else if (s == "--help" || s == "-h") {
             std::fputs(USAGE, stdout);
@@ -216,6 +229,16 @@ int main(int argc, char** argv) {
     if (want_fields && fields_out.empty()) {
         std::fprintf(stderr, "invalid --fields-out (FILE)\n");
         return 2;
+    }
+    uint32_t stats_every = 1;
+    if (want_stats || want_stats_every) {
+        double e = 1.0;
+        const bool ok = want_stats && !stats_out.empty() && (!want_stats_every || (parse_double(stats_every_arg, &e) && e >= 1.0 && e == std::floor(e) && e <= 4294967295.0));
+        if (!ok) {
+            std::fprintf(stderr, "invalid --stats options (--stats-out FILE [--stats-every K >= 1])\n");
+            return 2;
+        }
+        stats_every = (uint32_t)e;
     }
     std::vector<uint32_t> track_ids;
     uint32_t track_every = 1;
@@ -353,6 +376,15 @@ int main(int argc, char** argv) {
         if (rc == SPHX_OK) rc = sphx_track_record(solver->ctx(), (uint32_t)track_max_frames, track_every);
         if (rc != SPHX_OK) {
             std::fprintf(stderr, "--track failed: %s (status %d)\n", sphx_last_error(solver->ctx()), rc);
+            return 1;
+        }
+    }
+    // the statistics recorder, likewise
+    const uint64_t stats_max_frames = want_stats ? (uint64_t)std::max(warmup + steps, 0l) / stats_every : 0;
+    if (stats_max_frames) {
+        const int rc = stats_max_frames > 0xFFFFFFFFull ? SPHX_ERR_CAPACITY : sphx_stats_record(solver->ctx(), nullptr, 0u, (uint32_t)stats_max_frames, stats_every);
+        if (rc != SPHX_OK) {
+            std::fprintf(stderr, "--stats-out failed: %s (status %d)\n", sphx_last_error(solver->ctx()), rc);
             return 1;
         }
     }
@@ -511,6 +543,48 @@ int main(int argc, char** argv) {
         }
         char buf[64];
         std::snprintf(buf, sizeof(buf), ", \"track_frames\": %u", ts.frames);
+        gauge_json += buf;
+    }
+    if (want_stats) {
+        sphx_stats_status ss{};
+        std::vector<sphx_stats_rec> rec;
+        std::vector<sphx_stats_frame> info;
+        int rc = sphx_stats_get_status(solver->ctx(), &ss);
+        if (rc == SPHX_OK && ss.frames) {
+            rec.resize(ss.frames);
+            info.resize(ss.frames);
+            rc = sphx_stats_read(solver->ctx(), 0u, ss.frames, rec.data(), info.data());
+        }
+        if (rc != SPHX_OK) {
+            std::fprintf(stderr, "--stats-out: %s (status %d)\n", sphx_last_error(solver->ctx()), rc);
+            return 1;
+        }
+        FILE* f = std::fopen(stats_out.c_str(), "w");
+        bool ok = f != nullptr;
+        auto num = [](double v) {  // (JSON has no inf: the extremes of an empty record are written as null)
+            char b[40];
+            if (std::isfinite(v)) std::snprintf(b, sizeof(b), "%.17g", v);
+            else std::snprintf(b, sizeof(b), "null");
+            return std::string(b);
+        };
+        for (size_t k = 0; ok && k < rec.size(); ++k) {
+            const sphx_stats_rec& r = rec[k];
+            ok = std::fprintf(f, "{\"step\": %llu, \"dt\": %.9g, \"n\": %u, \"count\": %llu, \"nonfinite\": %llu, \"density_count\": %llu, \"density_valid\": %u, "
+                                 "\"sum_pos\": [%s, %s], \"sum_vel\": [%s, %s], \"sum_speed_sq\": %s, \"sum_angular\": %s, \"sum_density\": %s, "
+                                 "\"sum_density_sq\": %s, \"max_speed_sq\": %s, \"min_pos\": [%s, %s], \"max_pos\": [%s, %s], \"min_density\": %s, \"max_density\": %s}\n",
+                              (unsigned long long)info[k].step, (double)info[k].dt, info[k].n, (unsigned long long)r.count, (unsigned long long)r.nonfinite,
+                              (unsigned long long)r.density_count, r.density_valid, num(r.sum_pos[0]).c_str(), num(r.sum_pos[1]).c_str(), num(r.sum_vel[0]).c_str(),
+                              num(r.sum_vel[1]).c_str(), num(r.sum_speed_sq).c_str(), num(r.sum_angular).c_str(), num(r.sum_density).c_str(),
+                              num(r.sum_density_sq).c_str(), num(r.max_speed_sq).c_str(), num(r.min_pos[0]).c_str(), num(r.min_pos[1]).c_str(),
+                              num(r.max_pos[0]).c_str(), num(r.max_pos[1]).c_str(), num(r.min_density).c_str(), num(r.max_density).c_str()) > 0;
+        }
+        if (f) ok = std::fclose(f) == 0 && ok;
+        if (!ok) {
+            std::fprintf(stderr, "cannot write %s\n", stats_out.c_str());
+            return 1;
+        }
+        char buf[64];
+        std::snprintf(buf, sizeof(buf), ", \"stats_frames\": %u", ss.frames);
         gauge_json += buf;
     }
     if (want_fields) {

@@ -324,6 +324,14 @@ struct sphx_ctx {
         uint32_t* scratch = nullptr;  // window index of sphx_download_by_id + the outputs' device copies on the host-pointer paths
         size_t scratch_cap = 0;       // ... in 4-byte words
     } track;
+    // fluid statistics (sphx_fluid_stats, sphx_stats_*: sphx_stats.inc).  Belongs to the context, not to the particle state.
+    struct Stats {
+        sphx_stats_rec* scratch = nullptr;  // device: stage-1 partial records, then the records of one host-pointer call; allocated on first use
+        sphx_stats_rec* rec = nullptr;      // recording: max_frames frames of 1 + n_rects records
+        sphx_rect rects[SPHX_STATS_MAX_RECTS] = {};  // ... its rectangles
+        uint32_t n_rects = 0, recording = 0, max_frames = 0, every = 0, frames = 0, dropped = 0, steps = 0;  // steps: finished since sphx_stats_record
+        std::vector<sphx_stats_frame> info;  // ... and one entry per stored frame (host)
+    } stats;
     bool uploaded = false, boundary_changed = true, tails_dirty = true, in_step = false;
     bool lists_current = false;  // the neighbour lists were built from the positions the arrays hold (raised by a completed build, dropped with q_noclamp)
     unsigned long long* state_dig = nullptr;  // sphx_state_*: one digest per section (device), allocated on first use

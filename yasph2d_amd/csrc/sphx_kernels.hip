@@ -3342,3 +3342,5 @@ __global__ __launch_bounds__(64) void k_publish(DevScalars* scal, Mailbox* mb, u
 #include "sphx_track.inc"
 // per-particle flow fields from the neighbour lists: velocity gradient, divergence, vorticity, colour gradient (kernel + C ABI)
 #include "sphx_fields.inc"
+// fluid statistics: counts, float64 sums and extremes of the fluid and of probe rectangles, the time-series recorder (kernels + C ABI)
+#include "sphx_stats.inc"
