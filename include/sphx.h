@@ -510,7 +510,9 @@ int sphx_particle_fields(sphx_ctx* ctx, uint32_t flags, const sphx_fields_out* o
  *   sum_density_sq / density_count - (sum_density / density_count)^2.
  * When allowed: sphx_fluid_stats wherever sphx_download is (a pending advection is applied first, as in sphx_render) and before any upload
  *   (N = 0: empty records); SPHX_ERR_NOT_READY between a step_begin and its step_finish (either solver).  Densities never make the call
- *   fail.  A tile context (sphx_tile_*, sphx_multi_tile_ctx) is refused with SPHX_ERR_INVALID_ARGUMENT; sphx_multi_* has no counterpart.
+ *   fail.  A tile context (sphx_tile_*, sphx_multi_tile_ctx) is refused with SPHX_ERR_INVALID_ARGUMENT: its arrays hold ghosts and miss
+ *   the particles other tiles own.  A tiled run has sphx_multi_fluid_stats and sphx_multi_stats_* (below, with sphx_multi): the same
+ *   records over the particles the tiles own, combined across the tiles.
  * Argument errors (SPHX_ERR_INVALID_ARGUMENT, the message names the argument): ctx, out or status NULL, rects NULL with n_rects > 0,
  *   n_rects > SPHX_STATS_MAX_RECTS, a NaN bound, unknown flag bits, a device `out` that is not 8-byte aligned.
  * SPHX_STATS_DEVICE_POINTERS: `out` is device memory on the context's device, 8-byte aligned; the call is enqueued on the context's
@@ -771,6 +773,59 @@ uint64_t sphx_multi_num_owned(const sphx_multi* m);
 int sphx_multi_download(sphx_multi* m, float* pos_xy, float* vel_xy, float* density, uint32_t* ids, uint64_t* inout_n);
 int sphx_multi_info(const sphx_multi* m, sphx_multi_info_t* out);
 sphx_ctx* sphx_multi_tile_ctx(sphx_multi* m, uint32_t local_tile); /* inspection (neighbours, cells, profiling) */
+
+/* ---- fluid statistics of a tiled run (csrc/sphx_stats.inc, csrc/sphx_tiles.cpp, csrc/sphx_stats_merge.hpp) ---------------------------------
+ * The records of sphx_fluid_stats (above: members, terms, rectangle predicate, arithmetic) for a run that is cut into tiles, without a
+ * sphx_multi_download: every tile streams its local arrays once — pos, vel, density and particle_id, 24 bytes per particle — and keeps
+ * the particles it OWNS (bit 31 of the id in the tile's arrays); a ghost enters no count, no sum, no extreme and no rectangle.  Every
+ * particle of the run is owned by exactly one tile.
+ * Combination: record r of the whole fluid is the fold of the tiles' records r in ASCENDING TILE RANK, ((t0 (+) t1) (+) t2) ..., with the
+ *   a (+) b of the device's own reduction: each sum a + b in this order, integer addition for the counts, minimum / maximum for the
+ *   extremes (among zeros of either sign a minimum is -0 if one is present, a maximum +0), fmax for max_speed_sq; density_valid is the AND
+ *   over the tiles.  A tile that owns nothing contributes the empty record (zero sums and counts, +INFINITY / -INFINITY extremes).
+ * Contract: counts, minima, maxima and max_speed_sq are exact.  Each sum is within n * 2^-52 * sum|t| of the exact one, n the number of
+ *   terms of the WHOLE fluid's sum — the bound of sphx_fluid_stats is stated for any order of summation and so covers the fold.  Two calls
+ *   on one state return identical bytes.  For every tiling of the same particle set (and the single context holding it) the counts, extremes
+ *   and max_speed_sq are the same and the sums agree within that bound of the exact value; bitwise equality of the sums ACROSS tilings is not
+ *   promised.
+ * sphx_multi_fluid_stats(m, rects, n_rects, flags = 0, out, out_tiles): out (host, [1 + n_rects]) receives the whole fluid; out_tiles
+ *   (host, [world][1 + n_rects], may be NULL) every tile's own records in ascending tile rank.  In-process (sphx_multi_create): every tile
+ *   enqueues on its own stream and device, then the records are copied back and folded on the host.  Rank mode (sphx_multi_create_rank):
+ *   the call is COLLECTIVE — every rank calls it with the same arguments — and every rank receives the same bytes, out_tiles included; the
+ *   records cross the ranks bit for bit (as integers below 2^32, never as doubles a transport might renormalise).
+ * When allowed: after sphx_multi_upload and after every finished step; SPHX_ERR_NOT_READY between sphx_multi_step_begin and _finish and
+ *   before the first sphx_multi_upload (record and read too; behind a solver object the first simulation step uploads).
+ *   density_valid is 1 in both states (the warm-up block of the upload and every step recompute the densities after the re-grid).
+ *   SPHX_ERR_INVALID_ARGUMENT: m or out NULL, the rectangle errors of sphx_fluid_stats, any flags bit, more than 64 tiles.
+ * Recording: after sphx_multi_stats_record(rects, n_rects, max_frames, every) every every-th SUCCESSFULLY finished multi step (from
+ *   sphx_multi_step_finish or inside sphx_multi_simulation_step(s), counted from the call) makes every tile enqueue one frame of its own
+ *   records into its own device buffer, behind that step's kernels.  Nothing comes back to the host and nothing is synchronised.
+ *   sphx_stats_frame: step = finished steps since the call (1-based), dt = that step's dt, n = the owned count of the whole run as the
+ *   step's last all-reduce left it.  Limits and semantics are those of sphx_stats_record, per tile: 64 MiB (SPHX_ERR_CAPACITY),
+ *   max_frames == 0 stops and frees, every == 0 is SPHX_ERR_INVALID_ARGUMENT, a new call discards the old recording, frames beyond
+ *   max_frames are counted in `dropped`.  The recording survives sphx_multi_upload and re-partitioning.  sphx_multi_stats_read copies the
+ *   tiles' frames [first_frame, first_frame + n_frames), folds each frame as above and waits for the tiles' streams; it is collective in
+ *   rank mode (four meetings of the ranks per record: meant for the end of a run, not for every step); a range beyond `frames` is
+ *   SPHX_ERR_INVALID_ARGUMENT.  A recorded frame equals the sphx_multi_fluid_stats call made at that moment.
+ * No side effects: all of this only reads the tiles' state (a queued run-ahead pass stays valid, the sweep direction is put back).  A run
+ *   with stats calls and a recording between its steps is bit-identical to the same run without: everything sphx_multi_download returns,
+ *   every sphx_step_stats field, sphx_multi_info().exchanges.
+ * One tile: sphx_tile_fluid_stats has the arguments, flags, errors and device-pointer rule of sphx_fluid_stats, is accepted ONLY on a tile
+ *   context (a plain one: SPHX_ERR_INVALID_ARGUMENT) and covers the particles that tile owns; SPHX_ERR_NOT_READY between a halo exchange
+ *   and the tile's re-grid.  sphx_tile_stats_record / _frame / _read are the seam the multi recorder is built on (INTERNAL, like the other
+ *   sphx_tile_* calls); sphx_stats_get_status reads a tile's recording too.
+ * Cost: per tile the two launches of sphx_fluid_stats, 24 instead of 20 bytes per local particle; DESIGN.md section 4i. */
+int sphx_tile_fluid_stats(sphx_ctx* tile_ctx, const sphx_rect* rects /* host */, uint32_t n_rects, uint32_t flags, sphx_stats_rec* out /* [1 + n_rects] */);
+int sphx_tile_stats_record(sphx_ctx* tile_ctx, const sphx_rect* rects /* host */, uint32_t n_rects, uint32_t max_frames, uint32_t every);
+int sphx_tile_stats_frame(sphx_ctx* tile_ctx, float dt, uint32_t n_global); /* one finished step: a frame if the recording is due */
+int sphx_tile_stats_read(sphx_ctx* tile_ctx, uint32_t first_frame, uint32_t n_frames, sphx_stats_rec* out /* host */, sphx_stats_frame* info /* may be NULL */);
+int sphx_multi_fluid_stats(sphx_multi* m, const sphx_rect* rects /* host */, uint32_t n_rects, uint32_t flags /* 0 */,
+                           sphx_stats_rec* out /* host, [1 + n_rects]: the whole fluid */,
+                           sphx_stats_rec* out_tiles /* host, [world][1 + n_rects], may be NULL: per tile, ascending tile rank */);
+int sphx_multi_stats_record(sphx_multi* m, const sphx_rect* rects /* host */, uint32_t n_rects, uint32_t max_frames, uint32_t every);
+int sphx_multi_stats_get_status(const sphx_multi* m, sphx_stats_status* out);
+int sphx_multi_stats_read(sphx_multi* m, uint32_t first_frame, uint32_t n_frames, sphx_stats_rec* out /* host, [n_frames][1 + n_rects] */,
+                          sphx_stats_frame* info /* host, [n_frames], may be NULL */);
 /* Solver::simulation_step(&mut world, &mut time_manager) (solver/mod.rs:17) in ONE call: phase A, the TimeManager mirror
  * (simulation_step() dfsph.rs:433, update_simulation_step dfsph.rs:478-480), phase B */
 struct sphx_timer;
@@ -929,6 +984,9 @@ int sphx_solver_remove(sphx_solver* s, sphx_world* w, const sphx_rect* rects, ui
 int sphx_solver_save(sphx_solver* s, sphx_world* w, sphx_timer* t, const char* path);
 int sphx_solver_load(sphx_solver* s, sphx_world* w, sphx_timer* t, const char* path);
 sphx_ctx* sphx_solver_ctx(sphx_solver* s);
+/* the sphx_multi behind a solver made by sphx_solver_create_dfsph_multi (borrowed: for sphx_multi_fluid_stats, sphx_multi_stats_*,
+ * sphx_multi_info); NULL for every other solver */
+sphx_multi* sphx_solver_multi(sphx_solver* s);
 const char* sphx_solver_last_error(const sphx_solver* s);
 
 #ifdef __cplusplus

@@ -6,6 +6,7 @@ stage 1 reads), measured in the same run.
   tools/stats_bench.py [--particles 16000000] [--warmup 40] [--steps 40] [--calls 25] [--rounds 3]
   rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 tools/stats_bench.py --trace-run [--particles ...] [--calls 25]
   tools/stats_bench.py --from-trace DIR/.../*_kernel_trace.csv --particles N
+  tools/stats_bench.py --tiles K [--particles 16000000] [--warmup 10] [--calls 25]
 
 As tools/fields_bench.py: a scratch context keeps the GPU busy until the context's first step is queued, then --warmup untimed steps
 settle the flow.  Without a profiler, on that settled state:
@@ -17,7 +18,12 @@ settle the flow.  Without a profiler, on that settled state:
 sphx_state_digest, a call with 0 and a call with 8 rectangles.  --from-trace reads that trace: the digest kernel runs once per section,
 in section order (an empty section has none), so launches 0, 1 and 3 of every call are the positions, velocities and densities; stage 1 alternates between 0 and 8
 rectangles.  The ratio of a call's kernels to those three launches and the achieved bytes per second (20 bytes per particle) are
-printed.  There is no pass / fail threshold.  Every mode prints one JSON line."""
+printed.  There is no pass / fail threshold.  Every mode prints one JSON line.
+--tiles K is the tiled run's pass (sphx_multi_fluid_stats: stage 1 also streams particle_id and keeps the owned particles, 24 bytes per
+particle): the same scene in a single context and in a K-tile sphx_multi with all tiles on device 0 (devices=[0]*K), --warmup steps each,
+in one process; per tile the device time of a sphx_tile_fluid_stats call with 0 and with 8 rectangles by the same hipEvent brackets as the
+single context's call, the ratio of tile 0's stage 1 to the single context's (K = 1: everything is owned, the ratio by bytes is 24 / 20)
+and the wall time of the whole sphx_multi_fluid_stats call."""
 import argparse
 import csv
 import json
@@ -76,12 +82,15 @@ def settled(args):
     return w, s, t, scale
 
 
-def timed_call(ctx, calls, rects, out):
+def timed_call(ctx, calls, rects, out, call=None):
     dev, wall = [], []
     for _ in range(calls):
         ctx.profile_reset()
         t0 = time.perf_counter()
-        ctx.stats(rects, out=out)
+        if call is None:
+            ctx.stats(rects, out=out)
+        else:
+            call(rects, out)
         wall.append((time.perf_counter() - t0) * 1e6)
         p = ctx.profile_get()
         assert all(p[k]["launches"] == 1 for k in LABELS)
@@ -138,6 +147,78 @@ def measure(args):
     print(json.dumps(out))
 
 
+def tiled(args):
+    import torch
+
+    import yasph2d_amd as y
+    from yasph2d_amd import _lib
+    from yasph2d_amd.multi import MultiSolver
+
+    scale = float(np.sqrt(args.particles / 4050.0))
+    w = y.FluidParticleWorld()
+    w.reset_fluid(scale)
+    rects = rects_for(scale)
+    buf = {k: torch.empty((1 + k) * 128, dtype=torch.uint8, device="cuda") for k in (0, 8)}
+    out = dict(particles=int(len(w.positions)), tiles=args.tiles, warmup=args.warmup, calls=args.calls)
+
+    def brackets(ctx, n, bytes_pp, call=None):
+        ctx.profile_filter(None)
+        ctx.profile_enable(True)
+        res = {}
+        for k in (0, 8):
+            r = timed_call(ctx, args.calls, rects[:k], buf[k], call)
+            r["bytes_per_s"] = bytes_pp * n / (r["stage1_us"] * 1e-6) if n else 0.0
+            res["rects_%d" % k] = r
+        ctx.profile_enable(False)
+        return res
+
+    # the single context's pass (k_stats_partial<false>: 20 bytes per particle)
+    s = y.DFSPHSolver(w, y.default_params())
+    t = y.TimeManager()
+    s.simulation_steps(w, t, args.warmup, sync_world=False)
+    ctx = s.context()
+    ctx.synchronize()
+    out["single"] = dict(n=ctx.n, bytes_per_particle=20, **brackets(ctx, ctx.n, 20.0))
+    s.close()
+
+    # the same scene cut into tiles, all on device 0
+    w = y.FluidParticleWorld()
+    w.reset_fluid(scale)
+    m = MultiSolver(y.default_params(), devices=[0] * args.tiles)
+    m.set_boundary(w.boundary_particles)
+    m.upload(w.positions)
+    t = y.TimeManager()
+    m.steps(t, args.warmup)
+    m.synchronize()
+    L = m.L
+    per_tile = []
+    for k in range(args.tiles):
+        tc = m.tile_context(k)
+
+        def call(r, o, tc=tc):
+            arr, nr = y._rect_array(r)
+            torch.cuda.current_stream().synchronize()
+            tc._chk(L.sphx_tile_fluid_stats(tc.h, arr, nr, _lib.STATS_DEVICE_POINTERS, o.data_ptr()))
+            tc.synchronize()
+
+        per_tile.append(dict(tile=k, n_local=tc.n, bytes_per_particle=24, **brackets(tc, tc.n, 24.0, call)))
+    out["tiles_detail"] = per_tile
+    wall = []
+    for _ in range(args.calls):
+        t0 = time.perf_counter()
+        rec, tiles = m.stats(rects, per_tile=True)
+        wall.append((time.perf_counter() - t0) * 1e6)
+    out["multi_call_8_rects_wall_us"] = float(np.median(wall))
+    out["counts"] = rec["count"].tolist()
+    out["owned_per_tile"] = tiles["count"][:, 0].tolist()
+    for k in (0, 8):
+        a, b = per_tile[0]["rects_%d" % k]["stage1_us"], out["single"]["rects_%d" % k]["stage1_us"]
+        out["stage1_ratio_tile0_to_single_rects_%d" % k] = a / b
+    out["byte_ratio"] = 24.0 / 20.0
+    m.close()
+    print(json.dumps(out))
+
+
 def trace_run(args):
     import torch
 
@@ -186,11 +267,14 @@ def main():
     ap.add_argument("--calls", type=int, default=25)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--record-rects", action="store_true", help="the recording carries the eight rectangles too (default: record 0 only)")
+    ap.add_argument("--tiles", type=int, default=0, help="the tiled run's pass on K tiles of device 0, next to the single context's")
     ap.add_argument("--trace-run", action="store_true")
     ap.add_argument("--from-trace", metavar="CSV")
     args = ap.parse_args()
     if args.from_trace:
         from_trace(args)
+    elif args.tiles:
+        tiled(args)
     elif args.trace_run:
         trace_run(args)
     else:

@@ -488,6 +488,14 @@ class SphxContext:
         self._chk(self.L.sphx_stats_read(self.h, first, count, _p(rec) if count else None, _p(info) if count else None))
         return rec, info
 
+    def tile_stats(self, rects=()):
+        """sphx_tile_fluid_stats: stats() of a TILE context (MultiSolver.tile_context(k)) over the particles that tile owns — its ghosts
+        enter nothing.  A plain context is refused.  MultiSolver.stats() folds these over the tiles."""
+        arr, k = _rect_array(rects)
+        rec = np.zeros(1 + k, STATS_DTYPE)
+        self._chk(self.L.sphx_tile_fluid_stats(self.h, arr, k, 0, _p(rec)))
+        return rec
+
     def track_record(self, max_frames, every=1):
         """sphx_track_record: from now on every `every`-th finished step stores {x, y, vx, vy} of the tracked ids on the device, up to
         max_frames frames (later ones are counted in track_status()["dropped"]); max_frames=0 stops and frees.  Works inside
@@ -1037,6 +1045,28 @@ class DFSPHMultiSolver(DFSPHSolver):
         if rc:
             raise SphxError(rc, self.L.sphx_multi_last_error(None).decode())
         self.h = h
+
+    def multi(self):
+        """Borrowed MultiSolver view of the tiles behind this solver (statistics, info, tile contexts); the solver keeps owning them."""
+        from .multi import MultiSolver
+
+        m = MultiSolver.__new__(MultiSolver)
+        m.L, m.params, m._borrowed = self.L, None, True
+        m.h = C.c_void_p(self.L.sphx_solver_multi(self.h))
+        return m
+
+    # fluid statistics of the tiled run (MultiSolver.stats and its recorder; the recorder fires behind every step of simulation_steps(k))
+    def stats(self, rects=(), per_tile=False):
+        return self.multi().stats(rects, per_tile)
+
+    def stats_record(self, rects, max_frames, every=1):
+        self.multi().stats_record(rects, max_frames, every)
+
+    def stats_status(self):
+        return self.multi().stats_status()
+
+    def stats_frames(self, first=0, count=None):
+        return self.multi().stats_frames(first, count)
 
 
 class WCSPHSolver(DFSPHSolver):

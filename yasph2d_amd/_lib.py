@@ -217,6 +217,14 @@ SIGNATURES = {
     "sphx_stats_record": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32, _u32]),
     "sphx_stats_get_status": (_i, [_vp, C.POINTER(SphxStatsStatus)]),
     "sphx_stats_read": (_i, [_vp, _u32, _u32, _vp, _vp]),
+    "sphx_tile_fluid_stats": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32, _vp]),
+    "sphx_tile_stats_record": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32, _u32]),
+    "sphx_tile_stats_frame": (_i, [_vp, _f, _u32]),
+    "sphx_tile_stats_read": (_i, [_vp, _u32, _u32, _vp, _vp]),
+    "sphx_multi_fluid_stats": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32, _vp, _vp]),
+    "sphx_multi_stats_record": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32, _u32]),
+    "sphx_multi_stats_get_status": (_i, [_vp, C.POINTER(SphxStatsStatus)]),
+    "sphx_multi_stats_read": (_i, [_vp, _u32, _u32, _vp, _vp]),
     "sphx_debug_correction_counts": (_i, [_vp, _vp]),
     "sphx_download_by_id": (_i, [_vp, _u32, _u32, _u32, C.POINTER(SphxTrackOut), C.POINTER(_u32)]),
     "sphx_download": (_i, [_vp, _vp, _vp, _vp, _vp]),
@@ -350,6 +358,7 @@ SIGNATURES = {
     "sphx_solver_append": (_i, [_vp, _vp, _vp, _vp, _u32, _i, C.POINTER(_u32)]),
     "sphx_solver_remove": (_i, [_vp, _vp, C.POINTER(SphxRect), _u32, _u32, _i, C.POINTER(_u32)]),
     "sphx_solver_ctx": (_vp, [_vp]),
+    "sphx_solver_multi": (_vp, [_vp]),
     "sphx_solver_last_error": (C.c_char_p, [_vp]),
 }
 

@@ -781,6 +781,10 @@ int sphx_solver_load(sphx_solver* s, sphx_world* w, sphx_timer* t, const char* p
     return s->s.load(w->w, t->t, path);
 }
 sphx_ctx* sphx_solver_ctx(sphx_solver* s) { return s->s.ctx(); }
+sphx_multi* sphx_solver_multi(sphx_solver* s) {
+    auto* ms = s ? dynamic_cast<sph::HipDfsphMultiSolver*>(s->sp) : nullptr;
+    return ms ? ms->multi() : nullptr;
+}
 const char* sphx_solver_last_error(const sphx_solver* s) { return s->s.last_error.c_str(); }
 
 }  // extern "C"

@@ -339,6 +339,7 @@ struct sphx_ctx {
     // field sampling (sphx_sample_*): 2 = the cell grids and density[] belong to the current positions (a build plus densities), 1 = a
     // build without densities since, 0 = positions / boundary replaced or a step open; sample_missing says what a query is waiting for
     uint32_t sample_ready = 0;
+    bool tile_density_ready = false;  // tile mode: density[] is that of the last sphx_sub_regrid* and the positions have not moved since
     const char* sample_missing = "no neighbour build yet: run a step, or sphx_update_neighborhood + sphx_update_densities";
     float* sample_buf = nullptr;  // device scratch of the host-pointer queries (points + outputs), grown on demand
     size_t sample_cap = 0;        // ... in 4-byte words

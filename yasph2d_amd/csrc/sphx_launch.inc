@@ -697,6 +697,7 @@ int ensure_index_scratch(sphx_ctx* c) {
 // `missing` as the message) from here until a neighbour build AND the densities of its positions have completed (sphx_ctx::sample_ready).
 static inline void sample_went_stale(sphx_ctx* c, const char* missing) {
     c->sample_ready = 0u;
+    c->tile_density_ready = false;
     c->sample_missing = missing;
 }
 // A finished step whose neighbour build ran (sample_ready == 1: the build completed, its densities are the step's) may be sampled.  A
@@ -2514,6 +2515,7 @@ static int sub_regrid_impl(sphx_ctx* c, uint32_t* out_n_local, bool fuse_div, bo
     c->owned_base = c->owned_cum;
     c->owned_dirty = true;
     c->cached_n = c->N;
+    c->tile_density_ready = true;  // (fuse: the build left density and alpha of these positions)
     if (out_n_local) *out_n_local = c->N;
     return SPHX_OK;
 }

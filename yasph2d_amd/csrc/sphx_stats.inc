@@ -122,8 +122,13 @@ __device__ __forceinline__ void stats_from_rec(const sphx_stats_rec& r, StatsAcc
 // rectangles and a ballot skips them; a wavefront with a lane inside reduces that trip's masked terms at once and its lane 0 adds them
 // to the wavefront's accumulator of that rectangle in LDS — no lane carries a set of sums per rectangle.  `density` is null while
 // density[] does not belong to the positions: nothing of it is read.  The partial records go out with plain stores.
+// OWNED (a tile context: sphx_tile_fluid_stats) also streams pid[]: only a particle the tile owns — bit 31 of its id — is live; a ghost
+// enters no count, no sum, no extreme and no rectangle (24 bytes per particle instead of 20).  NT: pid[] by nontemporal loads, the
+// policy of k_track_lookup.  Without OWNED pid is not read and the kernel is the single context's, instruction for instruction.
+template <bool OWNED, bool NT = false>
 __global__ __launch_bounds__(256) void k_stats_partial(const float2* __restrict__ pos, const float2* __restrict__ vel, const float* __restrict__ density,
-                                                       uint32_t n, uint32_t chunk, StatsRects R, sphx_stats_rec* __restrict__ partial) {
+                                                       uint32_t n, uint32_t chunk, StatsRects R, sphx_stats_rec* __restrict__ partial,
+                                                       const uint32_t* __restrict__ pid) {
     __shared__ StatsAcc wacc[4][STATS_MAX_REC];
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const uint32_t nrec = 1u + R.n;
@@ -136,17 +141,21 @@ __global__ __launch_bounds__(256) void k_stats_partial(const float2* __restrict_
     uint32_t i = begin + threadIdx.x;
     float2 p = make_float2(0.0f, 0.0f), v = p;
     float rho = 0.0f;
+    uint32_t id = 0u;  // (OWNED only)
     if (i < end) {
         p = pos[i], v = vel[i];
         if (density) rho = density[i];
+        if constexpr (OWNED) id = NT ? __builtin_nontemporal_load(pid + i) : pid[i];
     }
     for (uint32_t base = begin; base < end; base += 256u, i += 256u) {
-        const bool live = i < end;
+        bool live = i < end;
+        if constexpr (OWNED) live = live && (id >> 31);
         const float2 pc = p, vc = v;
         const float rc = rho;
         if (i + 256u < end) {
             p = pos[i + 256u], v = vel[i + 256u];
             if (density) rho = density[i + 256u];
+            if constexpr (OWNED) id = NT ? __builtin_nontemporal_load(pid + i + 256u) : pid[i + 256u];
         }
         const bool fin = live && isfinite(pc.x) && isfinite(pc.y) && isfinite(vc.x) && isfinite(vc.y);
         const bool dfin = fin && density != nullptr && isfinite(rc);
@@ -267,21 +276,33 @@ int stats_scratch(sphx_ctx* c) {
     return dev_alloc(c, &c->stats.scratch, STATS_PARTIALS + STATS_MAX_REC);
 }
 
-// both stages behind what is on the stream, 1 + n_rects records to `out` (device); the sweep direction launch() toggles is put back
-void stats_enqueue(sphx_ctx* c, const sphx_rect* rects, uint32_t n_rects, sphx_stats_rec* out) {
+// both stages behind what is on the stream, 1 + n_rects records to `out` (device); the sweep direction launch() toggles is put back.
+// owned (a tile context): the records cover the particles the tile owns.  n is the local count the host holds since the tile's last
+// re-grid (sphx_sub_regrid leaves the exact one in c->N, like for every other kernel of the tile path): nothing is waited for.
+void stats_enqueue(sphx_ctx* c, const sphx_rect* rects, uint32_t n_rects, sphx_stats_rec* out, bool owned = false) {
     sphx_ctx::Stats& s = c->stats;
     const uint32_t n = c->N, nrec = 1u + n_rects;
-    const uint32_t density_valid = c->uploaded && c->sample_ready == 2u ? 1u : 0u;
+    // a tile's densities are those of its last re-grid (sub_regrid_impl: every re-grid of the tile path computes them with the lists)
+    const uint32_t density_valid = owned ? (c->tile_density_ready ? 1u : 0u) : (c->uploaded && c->sample_ready == 2u ? 1u : 0u);
     const uint32_t grid = stats_grid(n), chunk = stats_chunk(n, grid);
     StatsRects R{};
     for (uint32_t k = 0; k < n_rects; ++k) R.r[k] = rects[k];
     R.n = n_rects;
     const uint32_t rev = c->K.rev;
     hipStream_t st = c->stream;
-    if (grid)
+    if (grid && owned)
+        launch(c, "stats_partial", (density_valid ? 24.0 : 20.0) * n, [&] {
+            if (n >= TRACK_NT_FROM)
+                hipLaunchKernelGGL((k_stats_partial<true, true>), dim3(grid), dim3(256), 0, st, (const float2*)c->posA, (const float2*)c->vel,
+                                   density_valid ? (const float*)c->density : (const float*)nullptr, n, chunk, R, s.scratch, (const uint32_t*)c->pid);
+            else
+                hipLaunchKernelGGL((k_stats_partial<true, false>), dim3(grid), dim3(256), 0, st, (const float2*)c->posA, (const float2*)c->vel,
+                                   density_valid ? (const float*)c->density : (const float*)nullptr, n, chunk, R, s.scratch, (const uint32_t*)c->pid);
+        });
+    else if (grid)
         launch(c, "stats_partial", (density_valid ? 20.0 : 16.0) * n, [&] {
-            hipLaunchKernelGGL(k_stats_partial, dim3(grid), dim3(256), 0, st, (const float2*)c->posA, (const float2*)c->vel,
-                               density_valid ? (const float*)c->density : (const float*)nullptr, n, chunk, R, s.scratch);
+            hipLaunchKernelGGL((k_stats_partial<false>), dim3(grid), dim3(256), 0, st, (const float2*)c->posA, (const float2*)c->vel,
+                               density_valid ? (const float*)c->density : (const float*)nullptr, n, chunk, R, s.scratch, (const uint32_t*)nullptr);
         });
     launch(c, "stats_combine", 128.0 * nrec * (grid + 1.0), [&] {
         hipLaunchKernelGGL(k_stats_combine, dim3(nrec), dim3(256), 0, st, (const sphx_stats_rec*)s.scratch, grid, nrec, density_valid, out);
@@ -386,6 +407,108 @@ int sphx_stats_read(sphx_ctx* c, uint32_t first_frame, uint32_t n_frames, sphx_s
         return c->fail(SPHX_ERR_INVALID_ARGUMENT, "sphx_stats_read: first_frame + n_frames is beyond the frames recorded (sphx_stats_get_status)");
     if (n_frames == 0) return SPHX_OK;
     if (!out) return c->fail(SPHX_ERR_INVALID_ARGUMENT, "sphx_stats_read: out is NULL");
+    SPHX_HIP(c, hipSetDevice(c->device));
+    const size_t frame = 1u + s.n_rects;  // records
+    SPHX_HIP(c, hipMemcpyAsync(out, s.rec + first_frame * frame, n_frames * frame * sizeof(sphx_stats_rec), hipMemcpyDeviceToHost, c->stream));
+    SPHX_HIP(c, hipStreamSynchronize(c->stream));
+    if (info) std::memcpy(info, s.info.data() + first_frame, (size_t)n_frames * sizeof(sphx_stats_frame));
+    return SPHX_OK;
+}
+
+// ---- one tile of a tiled run (sphx_multi_fluid_stats and the multi recorder, sphx_tiles.cpp, are built on these) ------------------------
+namespace {
+int stats_check_tile(sphx_ctx* c, const char* fn) {
+    const std::string f = fn;
+    if (!c->tile_mode) return c->fail(SPHX_ERR_INVALID_ARGUMENT, (f + ": not a tile context (sphx_fluid_stats and sphx_stats_* serve a plain one)").c_str());
+    if (c->in_step) return c->fail(SPHX_ERR_NOT_READY, (f + ": between step_begin and step_finish (finish the step first)").c_str());
+    return SPHX_OK;
+}
+// between the packing pass and the re-grid the local count is an upper bound and an advection may be pending: no statistics of that
+int stats_check_tile_state(sphx_ctx* c, const char* fn) {
+    if (c->N && (!c->lists_current || c->tile_pending_dt > 0.0f))
+        return c->fail(SPHX_ERR_NOT_READY, (std::string(fn) + ": the tile is between a halo exchange and its re-grid (sphx_sub_regrid first)").c_str());
+    return SPHX_OK;
+}
+}  // namespace
+
+int sphx_tile_fluid_stats(sphx_ctx* c, const sphx_rect* rects, uint32_t n_rects, uint32_t flags, sphx_stats_rec* out) {
+    if (!c) return SPHX_ERR_INVALID_ARGUMENT;
+    if (!out) return c->fail(SPHX_ERR_INVALID_ARGUMENT, "sphx_tile_fluid_stats: out is NULL");
+    if (const char* bad = stats_check_rects(rects, n_rects)) return c->fail(SPHX_ERR_INVALID_ARGUMENT, "sphx_tile_fluid_stats", bad);
+    if (flags & ~(uint32_t)SPHX_STATS_DEVICE_POINTERS) return c->fail(SPHX_ERR_INVALID_ARGUMENT, "sphx_tile_fluid_stats: unknown flags bits");
+    const bool dev = flags & SPHX_STATS_DEVICE_POINTERS;
+    if (dev && ((uintptr_t)out & 7u)) return c->fail(SPHX_ERR_INVALID_ARGUMENT, "sphx_tile_fluid_stats: out (a device pointer) is not 8-byte aligned");
+    int rc;
+    if ((rc = stats_check_tile(c, "sphx_tile_fluid_stats"))) return rc;
+    if ((rc = stats_check_tile_state(c, "sphx_tile_fluid_stats"))) return rc;
+    SPHX_HIP(c, hipSetDevice(c->device));
+    if ((rc = stats_scratch(c))) return rc;
+    if (dev) {
+        stats_enqueue(c, rects, n_rects, out, true);
+        return SPHX_OK;
+    }
+    sphx_stats_rec* const d_out = c->stats.scratch + STATS_PARTIALS;
+    stats_enqueue(c, rects, n_rects, d_out, true);
+    SPHX_HIP(c, hipMemcpyAsync(out, d_out, (size_t)(1u + n_rects) * sizeof(sphx_stats_rec), hipMemcpyDeviceToHost, c->stream));
+    SPHX_HIP(c, hipStreamSynchronize(c->stream));
+    return SPHX_OK;
+}
+
+int sphx_tile_stats_record(sphx_ctx* c, const sphx_rect* rects, uint32_t n_rects, uint32_t max_frames, uint32_t every) {
+    if (!c) return SPHX_ERR_INVALID_ARGUMENT;
+    int rc;
+    if ((rc = stats_check_tile(c, "sphx_tile_stats_record"))) return rc;
+    if (max_frames) {  // (max_frames == 0 stops and frees, whatever the other arguments say)
+        if (const char* bad = stats_check_rects(rects, n_rects)) return c->fail(SPHX_ERR_INVALID_ARGUMENT, "sphx_tile_stats_record", bad);
+        if (every == 0) return c->fail(SPHX_ERR_INVALID_ARGUMENT, "sphx_tile_stats_record: every must be >= 1");
+        if ((uint64_t)max_frames * (1u + n_rects) * sizeof(sphx_stats_rec) > STATS_REC_BYTES_MAX)
+            return c->fail(SPHX_ERR_CAPACITY, "sphx_tile_stats_record: max_frames * (1 + n_rects) records exceed 64 MiB");
+    }
+    SPHX_HIP(c, hipSetDevice(c->device));
+    SPHX_HIP(c, hipStreamSynchronize(c->stream));  // (a queued frame may still write the old buffer)
+    stats_drop_recording(c);
+    if (!max_frames) return SPHX_OK;
+    if ((rc = stats_scratch(c))) return rc;
+    sphx_ctx::Stats& s = c->stats;
+    if ((rc = dev_alloc(c, &s.rec, (size_t)max_frames * (1u + n_rects)))) return rc;
+    for (uint32_t k = 0; k < n_rects; ++k) s.rects[k] = rects[k];
+    s.n_rects = n_rects;
+    s.max_frames = max_frames;
+    s.every = every;
+    s.recording = 1u;
+    return SPHX_OK;
+}
+
+// The tile loop calls this at the end of every finished step: with a recording on, every `every`-th call queues one frame of the owned
+// particles behind the step's kernels.  n_global is the owned count of the whole run (the tile loop has it from its last all-reduce).
+// Nothing comes back to the host and nothing is waited for.
+int sphx_tile_stats_frame(sphx_ctx* c, float dt, uint32_t n_global) {
+    if (!c || !c->tile_mode) return SPHX_ERR_INVALID_ARGUMENT;
+    sphx_ctx::Stats& s = c->stats;
+    if (!s.recording) return SPHX_OK;
+    if (++s.steps % s.every) return SPHX_OK;
+    if (s.frames >= s.max_frames) {
+        s.dropped += 1u;
+        return SPHX_OK;
+    }
+    int rc;
+    if ((rc = stats_check_tile_state(c, "sphx_tile_stats_frame"))) return rc;
+    SPHX_HIP(c, hipSetDevice(c->device));
+    stats_enqueue(c, s.rects, s.n_rects, s.rec + (size_t)s.frames * (1u + s.n_rects), true);
+    s.info.push_back(sphx_stats_frame{s.steps, dt, n_global});
+    s.frames += 1u;
+    return SPHX_OK;
+}
+
+int sphx_tile_stats_read(sphx_ctx* c, uint32_t first_frame, uint32_t n_frames, sphx_stats_rec* out, sphx_stats_frame* info) {
+    if (!c) return SPHX_ERR_INVALID_ARGUMENT;
+    int rc;
+    if ((rc = stats_check_tile(c, "sphx_tile_stats_read"))) return rc;
+    const sphx_ctx::Stats& s = c->stats;
+    if ((uint64_t)first_frame + n_frames > s.frames)
+        return c->fail(SPHX_ERR_INVALID_ARGUMENT, "sphx_tile_stats_read: first_frame + n_frames is beyond the frames recorded (sphx_stats_get_status)");
+    if (n_frames == 0) return SPHX_OK;
+    if (!out) return c->fail(SPHX_ERR_INVALID_ARGUMENT, "sphx_tile_stats_read: out is NULL");
     SPHX_HIP(c, hipSetDevice(c->device));
     const size_t frame = 1u + s.n_rects;  // records
     SPHX_HIP(c, hipMemcpyAsync(out, s.rec + first_frame * frame, n_frames * frame * sizeof(sphx_stats_rec), hipMemcpyDeviceToHost, c->stream));

@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "../../include/sphx.h"
+#include "sphx_stats_merge.hpp"
 
 namespace {
 
@@ -479,6 +480,7 @@ struct TileDriver {
     float pending_advect_dt = 0.0f;
     bool overlap = false;  // sphx_multi_options.overlap_exchange / SPHX_MULTI_OVERLAP=1: records on a second stream, interior work meanwhile
     bool run_ahead_ok = true;  // SPHX_RUN_AHEAD=0 switches the run-ahead over the step boundary off (A/B runs)
+    sphx_stats_rec* stats_dev = nullptr;  // sphx_multi_fluid_stats: this tile's 1 + SPHX_STATS_MAX_RECTS records (device, allocated on first use)
 
     bool poisoned = false;  // a collective step failed half-way: receives that will never complete may sit on the stream
     int fail(int rc, const std::string& what) {
@@ -520,6 +522,7 @@ struct TileDriver {
             if (b.first) hipFree(b.first);
             if (b.second) hipFree(b.second);
         }
+        if (stats_dev) hipFree(stats_dev);
         if (comm_stream) hipStreamDestroy(comm_stream);
         if (ev_packed) hipEventDestroy(ev_packed);
         if (ev_exchanged) hipEventDestroy(ev_exchanged);
@@ -983,7 +986,29 @@ struct TileDriver {
         last_div_iters = s.divergence_iterations;
         last_div_warm = s.warmstart_divergence;
         s.neighbor_entries = 0;
+        // sphx_multi_stats_record: a frame of this tile's owned particles behind the step's kernels (a flag test without a recording)
+        TCHK(sphx_tile_stats_frame(ctx, dt, (uint32_t)n_owned_global));
         if (st) *st = s;
+        return SPHX_OK;
+    }
+
+    // sphx_multi_fluid_stats, first half: this tile's records go onto its stream, into stats_dev; nothing is waited for
+    int stats_enqueue(const sphx_rect* rects, uint32_t n_rects) {
+        if (hipSetDevice(device) != hipSuccess) return fail(SPHX_ERR_HIP, "hipSetDevice");
+        if (!stats_dev && hipMalloc((void**)&stats_dev, (size_t)(1 + SPHX_STATS_MAX_RECTS) * sizeof(sphx_stats_rec)) != hipSuccess)
+            return fail(SPHX_ERR_HIP, "hipMalloc (statistics records)");
+        const int rc = sphx_tile_fluid_stats(ctx, rects, n_rects, SPHX_STATS_DEVICE_POINTERS, stats_dev);
+        if (rc) {  // (an argument or state error of one call: the run goes on, nobody is waiting in an all-reduce)
+            err = std::string("sphx_tile_fluid_stats: ") + sphx_last_error(ctx);
+            return rc;
+        }
+        return SPHX_OK;
+    }
+    // ... second half: the records come back
+    int stats_fetch(uint32_t n_rects, sphx_stats_rec* out) {
+        if (hipSetDevice(device) != hipSuccess || hipMemcpyAsync(out, stats_dev, (size_t)(1 + n_rects) * sizeof(sphx_stats_rec), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+            hipStreamSynchronize(stream) != hipSuccess)
+            return fail(SPHX_ERR_HIP, "copying the statistics records back");
         return SPHX_OK;
     }
 };
@@ -1038,6 +1063,7 @@ struct sphx_multi {
     std::vector<float> boundary;  // host copy until the upload
     bool have_layout = false;
     Layout explicit_layout;
+    bool uploaded = false;  // a sphx_multi_upload has succeeded: the contexts are tiles and hold a re-gridded particle set
 
     // run f(tile, index) on every tile, each on its own host thread (the tiles meet in barriers); returns the first error
     int each(const std::function<int(TileDriver&, size_t)>& f) {
@@ -1181,9 +1207,11 @@ int sphx_multi_set_boundary(sphx_multi* m, const float* xy, uint32_t n) {
 int sphx_multi_upload(sphx_multi* m, const float* pos_xy, const float* vel_xy, const uint32_t* ids, uint32_t n) {
     if (!m || (n && !pos_xy)) return SPHX_ERR_INVALID_ARGUMENT;
     const Layout L = m->have_layout ? m->explicit_layout : make_layout(m->O, m->P, m->world, pos_xy, n);
-    return m->each([&](TileDriver& t, size_t) {
+    const int rc = m->each([&](TileDriver& t, size_t) {
         return t.setup(L, pos_xy, vel_xy, ids, n, m->boundary.empty() ? nullptr : m->boundary.data(), (uint32_t)(m->boundary.size() / 2));
     });
+    if (!rc) m->uploaded = true;
+    return rc;
 }
 
 int sphx_multi_step_begin(sphx_multi* m, float dt_prev, float* out_vmax) {
@@ -1336,5 +1364,161 @@ int sphx_multi_info(const sphx_multi* m, sphx_multi_info_t* out) {
 }
 
 sphx_ctx* sphx_multi_tile_ctx(sphx_multi* m, uint32_t local_tile) { return (m && local_tile < m->tiles.size()) ? m->tiles[local_tile]->ctx : nullptr; }
+
+// ---- fluid statistics of the tiled run (include/sphx.h, "fluid statistics of a tiled run") ---------------------------------------------
+}  // extern "C"
+
+namespace {
+
+// local[t * cnt + k], t over the LOCAL tiles -> all[rank * cnt + k] over all `world` tiles.  In-process the local tiles are all tiles.
+// Rank mode (collective, every rank with the same cnt): four 64-bit words per meeting of the ranks, each as two integers below 2^32
+// (sphx_stats_merge.hpp) — every rank ends with the same bytes.
+int stats_gather(sphx_multi* m, const std::vector<sphx_stats_rec>& local, size_t cnt, std::vector<sphx_stats_rec>& all) {
+    all.assign((size_t)m->world * cnt, sphx_stats_rec{});
+    if (!m->rank_mode) {
+        std::copy(local.begin(), local.end(), all.begin());
+        return SPHX_OK;
+    }
+    TileDriver& t = *m->tiles[0];
+    Comm& comm = *t.comm;
+    std::vector<double> gathered((size_t)m->world * 8);
+    std::vector<double> halves((size_t)m->world * sphx_stats_host::HALVES);
+    for (size_t k = 0; k < cnt; ++k) {
+        double mine[sphx_stats_host::HALVES];
+        sphx_stats_host::encode(local[k], mine);
+        for (int part = 0; part < sphx_stats_host::HALVES / 8; ++part) {
+            const int rc = comm.allgather8(mine + part * 8, gathered.data());
+            if (rc) {
+                m->err = "the statistics records could not be exchanged between the ranks";
+                return t.fail(rc, m->err);
+            }
+            for (int r = 0; r < m->world; ++r)
+                for (int j = 0; j < 8; ++j) halves[(size_t)r * sphx_stats_host::HALVES + part * 8 + j] = gathered[(size_t)r * 8 + j];
+        }
+        for (int r = 0; r < m->world; ++r) all[(size_t)r * cnt + k] = sphx_stats_host::decode(halves.data() + (size_t)r * sphx_stats_host::HALVES);
+    }
+    return SPHX_OK;
+}
+
+// the argument rules of sphx_fluid_stats that do not need a context (the tiles check them again; checked here so that a refused call
+// has touched no tile)
+const char* multi_stats_check_rects(const sphx_rect* rects, uint32_t n_rects) {
+    if (n_rects > SPHX_STATS_MAX_RECTS) return "n_rects exceeds SPHX_STATS_MAX_RECTS";
+    if (n_rects && !rects) return "rects is NULL with n_rects > 0";
+    for (uint32_t k = 0; k < n_rects; ++k)
+        if (std::isnan(rects[k].x0) || std::isnan(rects[k].y0) || std::isnan(rects[k].x1) || std::isnan(rects[k].y1)) return "rects holds a NaN bound";
+    return nullptr;
+}
+int multi_stats_ready(sphx_multi* m, const char* fn) {
+    if (!m->uploaded) {  // (the contexts become tiles with the first upload)
+        m->err = std::string(fn) + ": before the first sphx_multi_upload";
+        return SPHX_ERR_NOT_READY;
+    }
+    for (auto& t : m->tiles)
+        if (t->in_step) {
+            m->err = std::string(fn) + ": between sphx_multi_step_begin and sphx_multi_step_finish (finish the step first)";
+            return SPHX_ERR_NOT_READY;
+        }
+    return SPHX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sphx_multi_fluid_stats(sphx_multi* m, const sphx_rect* rects, uint32_t n_rects, uint32_t flags, sphx_stats_rec* out, sphx_stats_rec* out_tiles) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    auto bad = [&](const std::string& what) {
+        m->err = "sphx_multi_fluid_stats: " + what;
+        return SPHX_ERR_INVALID_ARGUMENT;
+    };
+    if (!out) return bad("out is NULL");
+    if (const char* b = multi_stats_check_rects(rects, n_rects)) return bad(b);
+    if (flags) return bad("unknown flags bits");
+    if (m->world > 64) return bad("more than 64 tiles");
+    int rc;
+    if ((rc = multi_stats_ready(m, "sphx_multi_fluid_stats"))) return rc;
+    const size_t nrec = 1u + n_rects;
+    // every local tile enqueues on its own stream and device first, then the records are collected: the tiles' passes overlap
+    for (size_t k = 0; k < m->tiles.size(); ++k)
+        if ((rc = m->tiles[k]->stats_enqueue(rects, n_rects))) {
+            m->err = "tile " + std::to_string(k) + ": " + m->tiles[k]->err;
+            return rc;
+        }
+    std::vector<sphx_stats_rec> local(m->tiles.size() * nrec), all;
+    for (size_t k = 0; k < m->tiles.size(); ++k)
+        if ((rc = m->tiles[k]->stats_fetch(n_rects, local.data() + k * nrec))) {
+            m->err = "tile " + std::to_string(k) + ": " + m->tiles[k]->err;
+            return rc;
+        }
+    if ((rc = stats_gather(m, local, nrec, all))) return rc;
+    for (uint32_t r = 0; r < nrec; ++r) out[r] = sphx_stats_host::fold(all.data(), (uint32_t)m->world, nrec, r);
+    if (out_tiles) std::memcpy(out_tiles, all.data(), all.size() * sizeof(sphx_stats_rec));
+    return SPHX_OK;
+}
+
+int sphx_multi_stats_record(sphx_multi* m, const sphx_rect* rects, uint32_t n_rects, uint32_t max_frames, uint32_t every) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    int rc;
+    if ((rc = multi_stats_ready(m, "sphx_multi_stats_record"))) return rc;
+    if (max_frames) {  // (checked before any tile is touched: all tiles keep the old recording or all get the new one)
+        if (const char* b = multi_stats_check_rects(rects, n_rects)) {
+            m->err = std::string("sphx_multi_stats_record: ") + b;
+            return SPHX_ERR_INVALID_ARGUMENT;
+        }
+        if (every == 0) {
+            m->err = "sphx_multi_stats_record: every must be >= 1";
+            return SPHX_ERR_INVALID_ARGUMENT;
+        }
+        if ((uint64_t)max_frames * (1u + n_rects) * sizeof(sphx_stats_rec) > (64ull << 20)) {
+            m->err = "sphx_multi_stats_record: max_frames * (1 + n_rects) records exceed 64 MiB per tile";
+            return SPHX_ERR_CAPACITY;
+        }
+    }
+    for (size_t k = 0; k < m->tiles.size(); ++k)
+        if ((rc = sphx_tile_stats_record(m->tiles[k]->ctx, rects, n_rects, max_frames, every))) {
+            m->err = "tile " + std::to_string(k) + ": " + sphx_last_error(m->tiles[k]->ctx);
+            for (auto& t : m->tiles) sphx_tile_stats_record(t->ctx, nullptr, 0, 0, 1);  // no half-made recording
+            return rc;
+        }
+    return SPHX_OK;
+}
+
+// (every tile counts the same steps and stores the same number of frames: the first local tile speaks for all)
+int sphx_multi_stats_get_status(const sphx_multi* m, sphx_stats_status* out) {
+    if (!m || !out) return SPHX_ERR_INVALID_ARGUMENT;
+    return sphx_stats_get_status(m->tiles[0]->ctx, out);
+}
+
+int sphx_multi_stats_read(sphx_multi* m, uint32_t first_frame, uint32_t n_frames, sphx_stats_rec* out, sphx_stats_frame* info) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    int rc;
+    if ((rc = multi_stats_ready(m, "sphx_multi_stats_read"))) return rc;
+    sphx_stats_status st;
+    sphx_stats_get_status(m->tiles[0]->ctx, &st);
+    if ((uint64_t)first_frame + n_frames > st.frames) {
+        m->err = "sphx_multi_stats_read: first_frame + n_frames is beyond the frames recorded (sphx_multi_stats_get_status)";
+        return SPHX_ERR_INVALID_ARGUMENT;
+    }
+    if (n_frames == 0) return SPHX_OK;
+    if (!out) {
+        m->err = "sphx_multi_stats_read: out is NULL";
+        return SPHX_ERR_INVALID_ARGUMENT;
+    }
+    if (m->world > 64) {
+        m->err = "sphx_multi_stats_read: more than 64 tiles";
+        return SPHX_ERR_INVALID_ARGUMENT;
+    }
+    const size_t nrec = 1u + st.n_rects, cnt = (size_t)n_frames * nrec;
+    std::vector<sphx_stats_rec> local(m->tiles.size() * cnt), all;
+    for (size_t k = 0; k < m->tiles.size(); ++k)
+        if ((rc = sphx_tile_stats_read(m->tiles[k]->ctx, first_frame, n_frames, local.data() + k * cnt, k == 0 ? info : nullptr))) {
+            m->err = "tile " + std::to_string(k) + ": " + sphx_last_error(m->tiles[k]->ctx);
+            return rc;
+        }
+    if ((rc = stats_gather(m, local, cnt, all))) return rc;
+    for (size_t r = 0; r < cnt; ++r) out[r] = sphx_stats_host::fold(all.data(), (uint32_t)m->world, cnt, (uint32_t)r);
+    return SPHX_OK;
+}
 
 }  // extern "C"

@@ -124,7 +124,8 @@ class MultiSolver:
 
     def close(self):
         if getattr(self, "h", None):
-            self.L.sphx_multi_destroy(self.h)
+            if not getattr(self, "_borrowed", False):  # (DFSPHMultiSolver.multi(): the solver object owns the tiles)
+                self.L.sphx_multi_destroy(self.h)
             self.h = None
 
     __del__ = close
@@ -206,6 +207,48 @@ class MultiSolver:
         d = {k: getattr(i, k) for k, _ in i._fields_ if k not in ("reserved", "transport")}
         d["transport"] = i.transport.decode()
         return d
+
+    # ---- fluid statistics of the tiled run (the contract is in include/sphx.h, "fluid statistics of a tiled run") ----
+    def stats(self, rects=(), per_tile=False):
+        """sphx_multi_fluid_stats: the records of SphxContext.stats() over the particles the tiles own, folded over the tiles in ascending
+        rank — a structured array [1 + len(rects)] of STATS_DTYPE; per_tile=True: (that, the tiles' own records [world, 1 + len(rects)]).
+        No download: every tile streams its arrays once on its own device.  Collective in rank mode (every rank gets the same bytes)."""
+        from . import STATS_DTYPE, _rect_array
+
+        arr, k = _rect_array(rects)
+        rec = np.zeros(1 + k, STATS_DTYPE)
+        tiles = np.zeros((self.info()["world"], 1 + k), STATS_DTYPE) if per_tile else None
+        self._chk(self.L.sphx_multi_fluid_stats(self.h, arr, k, 0, _p(rec), _p(tiles)))
+        return (rec, tiles) if per_tile else rec
+
+    def stats_record(self, rects, max_frames, every=1):
+        """sphx_multi_stats_record: from now on every `every`-th finished multi step makes each tile store one frame of its records on its
+        device, up to max_frames frames (later ones are counted in stats_status()["dropped"]); max_frames=0 stops and frees.  Nothing
+        is synchronised and nothing comes back until stats_frames()."""
+        from . import _rect_array
+
+        arr, k = _rect_array(rects)
+        self._chk(self.L.sphx_multi_stats_record(self.h, arr, k, max_frames, every))
+
+    def stats_status(self):
+        """sphx_multi_stats_get_status -> dict(n_rects, recording, max_frames, every, frames, dropped)."""
+        st = _lib.SphxStatsStatus()
+        self._chk(self.L.sphx_multi_stats_get_status(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_ if k != "reserved"}
+
+    def stats_frames(self, first=0, count=None):
+        """sphx_multi_stats_read -> (records [count, 1 + n_rects] of STATS_DTYPE, each frame folded over the tiles; info [count] of
+        STATS_FRAME_DTYPE: step, dt, n) for the recorded frames [first, first + count) (count=None: all from `first`).  Waits for the
+        tiles' streams; collective in rank mode."""
+        from . import STATS_DTYPE, STATS_FRAME_DTYPE
+
+        st = self.stats_status()
+        if count is None:
+            count = max(st["frames"] - first, 0)
+        rec = np.zeros((count, 1 + st["n_rects"]), STATS_DTYPE)
+        info = np.zeros(count, STATS_FRAME_DTYPE)
+        self._chk(self.L.sphx_multi_stats_read(self.h, first, count, _p(rec) if count else None, _p(info) if count else None))
+        return rec, info
 
     def set_tiling_invariant(self, on=True):
         """sphx_set_tiling_invariant on every local tile: cell mates ordered by persistent id (the tiles' warm-start values always travel).
