@@ -57,6 +57,8 @@ extern "C" {
                             * 5 (additive): sphx_append, sphx_remove, sphx_rect, SPHX_REMOVE_*, sphx_solver_append, sphx_solver_remove
                             * 5 (additive): sphx_state_size / _save / _load / _digest / _save_file / _load_file, SPHX_STATE_*, sphx_timer_state,
                             *    sphx_timer_get_state / _set_state, sphx_solver_save / _load
+                            * 5 (additive): sphx_multi_state_size / _save / _load / _digest / _save_file / _load_file, sphx_tile_state_pack / _fetch,
+                            *    sphx_tile_upload_state, sphx_get_tiling_invariant, sphx_solver_multi_checkpoint / _restore
                             * 5 (additive): sphx_track_set / _fetch / _record / _get_status / _read, sphx_download_by_id, sphx_track_out,
                             *    sphx_track_status, SPHX_TRACK_*
                             * 5 (additive): sphx_particle_fields, sphx_fields_out, SPHX_FIELDS_DEVICE_POINTERS
@@ -370,7 +372,8 @@ int sphx_remove(sphx_ctx* ctx, const sphx_rect* rects, uint32_t n_rects, uint32_
  *   failed step; save, load and digest return SPHX_ERR_NOT_READY between a step_begin and its step_finish (either solver); load is allowed
  *   on any context outside a step.  A tile context (sphx_tile_*, sphx_multi_tile_ctx): SPHX_ERR_INVALID_ARGUMENT.  A capacity smaller than
  *   sphx_state_size: SPHX_ERR_CAPACITY with the needed size in *out_bytes (out_bytes may be NULL).  sphx_multi_* has NO counterpart yet: a
- *   multi-GPU run cannot be saved (sphx_solver_save on the multi-GPU solver object: SPHX_ERR_INVALID_ARGUMENT).
+ *   multi-GPU run cannot be saved (sphx_solver_save on the multi-GPU solver object: SPHX_ERR_INVALID_ARGUMENT).  (That holds for THESE
+ *   calls and this blob; a tiled run has a checkpoint of its own: sphx_multi_state_*, "checkpoint of a tiled run" below.)
  * Files: sphx_state_save_file writes exactly the blob (to path + ".tmp", renamed when complete), sphx_state_load_file reads one; an I/O
  *   failure is SPHX_ERR_INVALID_ARGUMENT with errno's text. */
 #define SPHX_STATE_SECTIONS 9
@@ -836,6 +839,95 @@ int sphx_multi_simulation_step(sphx_multi* m, struct sphx_timer* timer, float pa
 int sphx_multi_simulation_steps(sphx_multi* m, struct sphx_timer* timer, float particle_diameter, uint32_t k, sphx_step_stats* out_stats,
                                 uint32_t* out_done);
 
+/* ---- checkpoint of a tiled run (csrc/sphx_multi_state.inc, csrc/sphx_multi_state_format.hpp, csrc/sphx_tiles.cpp) ---------------------------
+ * A sphx_multi put down and picked up, without sphx_multi_download (which drops the warm-start sums that travel with the particles in tile
+ * mode and the iteration counts that decide whether the warm starts fire) and without the warm-up block of sphx_multi_upload.  The
+ * checkpoint is taken on the device from the particles each tile OWNS (bit 31 of the id in the tile's arrays) and is tiling-independent in
+ * content: what 2 x 2 tiles saved loads into 2 strips, 8 strips or one tile.
+ * Parts: a checkpoint is n_parts blobs.  An in-process sphx_multi (sphx_multi_create) writes ONE part, "part 0 of 1", its tiles in ascending
+ *   rank; in rank mode (sphx_multi_create_rank) every rank writes its own part "r of W" and nothing crosses the ranks for a save.  A part
+ *   (byte-exact layout: the top of csrc/sphx_multi_state_format.hpp), little-endian: magic "SPHXMULT" (not the single-context blob's),
+ *   version, endianness tag, total size; the sphx_params with device stored as 0; N_total, N_part, B, part, n_parts; num_density_iters,
+ *   num_divergence_iters, last_div_iters, last_div_warm, steps; the tiling-invariant flag; the saver's layout (world, axis / nx / ny, the
+ *   cuts in a fixed-size array for <= 64 tiles); a table of {offset, bytes, digest} and a digest of the header; then SPHX_MULTI_STATE_SECTIONS
+ *   sections, 8-byte aligned, padding zero: positions, velocities, particle_id (bit 31 cleared), density, alpha, kappa, stiffness of the
+ *   part's particles in the tiles' device order, and the GLOBAL boundary in caller order.  No timestamp, no pointer: two saves of one state
+ *   are byte-identical.
+ * Digest of a particle section with k 32-bit words per particle, all arithmetic mod 2^64 — the section digest above with the word index
+ *   replaced by id * k + c:
+ *     D = sum_owned sum_{c<k} (uint64)w[c] * ((2 (id k + c) + 1) * 0x9E3779B97F4A7C15)  +  (n_owned k) * 0xD6E8FEB86659FD93
+ *   For ids 0 .. N-1 it equals the section digest of the id-ordered array (sphx_download_by_id).  Integer arithmetic: it depends neither
+ *   on the order of accumulation nor on the tiling, and the digest of the whole run is the plain sum of the tiles' (and of the parts').
+ *   The boundary section carries the positional digest.  NOT a cryptographic hash, as above.
+ * Canonical warm-start values: with num_density_iters <= 1 the kappa section is written, and digested, as +0.0 (the next density loop
+ *   zeroes kappa before it reads it, dfsph.rs:199, and the tile loop did not even move it); the same for stiffness with
+ *   num_divergence_iters <= 1 (dfsph.rs:354).
+ * sphx_multi_state_size / _save(buf: host, flags = 0): every local tile enqueues its pass on its own stream and device — three launches,
+ *   36 bytes read per local particle (+ 4 for the count), 36 written per owned one — then copies its sections into buf at its offsets.
+ *   A capacity below the size: SPHX_ERR_CAPACITY with the needed size in *out_bytes (may be NULL).
+ * sphx_multi_state_digest: out[0 .. 7) the id-keyed digests of the WHOLE run's live particle sections, out[7] the boundary's.  Rank mode:
+ *   COLLECTIVE; the 64-bit sums cross the ranks as integers below 2^32 and every rank receives the same 64 bytes.
+ * sphx_multi_state_load(parts, bytes, n_parts, flags = 0) follows sphx_multi_upload's path; every rank is given ALL parts (collective), as
+ *   every rank is given the global arrays there.  Host validation first — per part: magic, version, endianness, sizes, section bounds and
+ *   overlaps, every count against every other, ids below 2^31, zero padding, the boundary's digest; the set: every part index once, scalars,
+ *   params, flag, layout and boundary equal across the parts, sum of N_part = N_total; the params against the multi's by sphx_state_load's
+ *   rule (every field except device and list_span_limit bit for bit; the message names the first that differs); a checkpoint saved in
+ *   tiling-invariant mode loads only into a multi whose tiles are in that mode and the other way round.  A refusal at this stage is
+ *   SPHX_ERR_INVALID_ARGUMENT and leaves the multi UNTOUCHED.  No count is used before it has been checked.  Then: the layout is an
+ *   explicit sphx_multi_set_layout / _set_grid_layout, else the saved cuts if the saver had as many tiles as this multi, else the
+ *   quantile layout of sphx_multi_upload over the checkpoint's positions; the boundary becomes the checkpoint's; every tile keeps its
+ *   rectangle's particles WITH their warm-start values (sphx_tile_upload_state); the iteration counts, last_div_* and steps are restored;
+ *   the ring budget of the ghost band and the info counters start as after an upload.  ONE halo exchange and re-grid runs (ghosts,
+ *   neighbour lists, densities and alpha recomputed): not the warm-up block — the counts are kept — and no SPHX_FLAG_* is raised.  Each
+ *   tile then digests what it owns: the sums for positions, velocities, particle_id, kappa and stiffness must equal the parts'; otherwise
+ *   SPHX_ERR_INVALID_ARGUMENT naming the section, and the multi asks for an upload or a load (steps, statistics and saves return
+ *   SPHX_ERR_NOT_READY).  A statistics recording survives, as it does over an upload.
+ * When allowed: save, size and digest wherever sphx_multi_fluid_stats is; SPHX_ERR_NOT_READY before the first upload or load, between
+ *   sphx_multi_step_begin and _finish and on a multi a failed collective step has poisoned; load is allowed before the first upload too.
+ *   Any flags bit, NULL arguments, more than 64 tiles: SPHX_ERR_INVALID_ARGUMENT.
+ * Files: sphx_multi_state_save_file writes the part to path (in-process) or to path + ".rRRRofWWW" (rank mode: three decimal digits each,
+ *   e.g. ".r001of004"), to a ".tmp" name renamed when complete.  sphx_multi_state_load_file reads `path` if it exists (one or several parts
+ *   back to back), else the complete set path.r000ofWWW ...; an incomplete set or an I/O failure is SPHX_ERR_INVALID_ARGUMENT.
+ * THE PROMISE.
+ *   1. In any mode, directly after a load the run holds exactly the saved particles: positions, velocities, ids, kappa and stiffness bit
+ *      for bit by id, and the counts behind the warm starts.  Two multis that load the same parts with the same world and layout then
+ *      produce identical bits.
+ *   2. In tiling-invariant mode (sphx_set_tiling_invariant on every tile) with fixed iteration counts the loaded run continues
+ *      bit-identically by id to the run that saved, for any tiling of the loader including one tile, and after the load all eight digests
+ *      equal the checkpoint's.
+ *   3. In default mode a continued run is a valid run of the same state, not a bit-equal one: the load re-decomposes and re-exchanges,
+ *      which is the sense in which two tilings of one scene differ (DESIGN.md section 4j has the measured spread).
+ * No side effects of save, size and digest: they only read the tiles' state (a queued run-ahead pass stays valid, the sweep direction is put
+ *   back); a run with saves and digests between its steps is bit-identical to the same run without.
+ * One tile (INTERNAL, like the other sphx_tile_* calls): sphx_tile_state_pack enqueues the pass on a tile context and hands out the seven
+ *   DEVICE section buffers (the context's own scratch, valid until the next pack or upload); with out_digests or out_n_owned non-NULL it
+ *   then waits and returns them, otherwise sphx_tile_state_fetch does later (so that several tiles' passes overlap).
+ *   SPHX_ERR_NOT_READY between a halo exchange and the tile's re-grid.  sphx_tile_upload_state is sphx_tile_upload that also installs the
+ *   two warm-start arrays (NULL: zeros). */
+#define SPHX_MULTI_STATE_SECTIONS 8
+enum {
+    SPHX_MULTI_STATE_SEC_POSITIONS = 0, SPHX_MULTI_STATE_SEC_VELOCITIES = 1, SPHX_MULTI_STATE_SEC_PARTICLE_ID = 2, SPHX_MULTI_STATE_SEC_DENSITY = 3,
+    SPHX_MULTI_STATE_SEC_ALPHA = 4, SPHX_MULTI_STATE_SEC_KAPPA = 5, SPHX_MULTI_STATE_SEC_STIFFNESS = 6, SPHX_MULTI_STATE_SEC_BOUNDARY = 7
+};
+enum { SPHX_TILE_STATE_ZERO_KAPPA = 1u, SPHX_TILE_STATE_ZERO_STIFFNESS = 2u };
+typedef struct sphx_tile_state_out { /* device pointers, n_owned entries each */
+    const float* pos;                /* xy */
+    const float* vel;                /* xy */
+    const uint32_t* id;              /* bit 31 cleared */
+    const float *density, *alpha, *kappa, *stiffness;
+} sphx_tile_state_out;
+int sphx_tile_state_pack(sphx_ctx* tile_ctx, uint32_t flags, sphx_tile_state_out* out, uint64_t* out_digests /* [7], may be NULL */,
+                         uint32_t* out_n_owned /* may be NULL */);
+int sphx_tile_state_fetch(sphx_ctx* tile_ctx, uint64_t* out_digests /* [7], may be NULL */, uint32_t* out_n_owned /* may be NULL */);
+int sphx_tile_upload_state(sphx_ctx* ctx, const float* pos_xy, const float* vel_xy, const uint32_t* ids, const float* kappa, const float* stiffness, uint32_t n);
+int sphx_get_tiling_invariant(const sphx_ctx* ctx); /* 1 in tiling-invariant mode, else 0 */
+int sphx_multi_state_size(sphx_multi* m, uint64_t* out_bytes);
+int sphx_multi_state_save(sphx_multi* m, void* buf /* host */, uint64_t capacity, uint32_t flags /* 0 */, uint64_t* out_bytes /* may be NULL */);
+int sphx_multi_state_load(sphx_multi* m, const void* const* parts /* host */, const uint64_t* bytes, uint32_t n_parts, uint32_t flags /* 0 */);
+int sphx_multi_state_digest(sphx_multi* m, uint64_t* out /* [SPHX_MULTI_STATE_SECTIONS]: the whole run; collective in rank mode */);
+int sphx_multi_state_save_file(sphx_multi* m, const char* path); /* rank mode: path + ".rRRRofWWW" */
+int sphx_multi_state_load_file(sphx_multi* m, const char* path); /* the one file, or the complete set of part files */
+
 /* ---- single-node scalar reductions through POSIX shared memory ---------------------------------------------------------------
  * The three per-step scalars of the tile driver (vmax, two residual sums) already sit in host memory (pinned mailbox) on every
  * rank; for one process per GPU on ONE node a shared-memory all-reduce costs ~1 us instead of a device round trip through
@@ -983,6 +1075,15 @@ int sphx_solver_remove(sphx_solver* s, sphx_world* w, const sphx_rect* rects, ui
  * one (the params check refuses a context that differs).  SPHX_ERR_INVALID_ARGUMENT on the multi-GPU solver and for I/O failures. */
 int sphx_solver_save(sphx_solver* s, sphx_world* w, sphx_timer* t, const char* path);
 int sphx_solver_load(sphx_solver* s, sphx_world* w, sphx_timer* t, const char* path);
+/* The same for the multi-GPU solver object (sphx_solver_create_dfsph_multi), under names of their own — sphx_solver_save / _load keep
+ * refusing it: ONE file holding an 80-byte header ("SPHXMCKP", version, endianness tag, the size of what follows, the sphx_timer_state of
+ * t) and the part(s) of sphx_multi_state_save.  checkpoint: SPHX_ERR_NOT_READY before the solver's first step and when the caller has
+ * edited the world's particles since the last step.  restore: the file is validated as a whole before anything changes
+ * (sphx_multi_state_load's rules; the timer state too); afterwards t holds the saved timer state, the host world the saved boundary and the
+ * run's particle count, its particle arrays marked as behind the device (sphx_solver_sync_world fetches them), and the next
+ * sphx_solver_simulation_step uploads nothing.  SPHX_ERR_INVALID_ARGUMENT on every other solver and for I/O failures. */
+int sphx_solver_multi_checkpoint(sphx_solver* s, sphx_world* w, sphx_timer* t, const char* path);
+int sphx_solver_multi_restore(sphx_solver* s, sphx_world* w, sphx_timer* t, const char* path);
 sphx_ctx* sphx_solver_ctx(sphx_solver* s);
 /* the sphx_multi behind a solver made by sphx_solver_create_dfsph_multi (borrowed: for sphx_multi_fluid_stats, sphx_multi_stats_*,
  * sphx_multi_info); NULL for every other solver */

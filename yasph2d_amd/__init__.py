@@ -1068,6 +1068,22 @@ class DFSPHMultiSolver(DFSPHSolver):
     def stats_frames(self, first=0, count=None):
         return self.multi().stats_frames(first, count)
 
+    # the tiled run put down and picked up (save / load of the base class keep refusing this solver)
+    def checkpoint(self, world, time_manager, path):
+        """sphx_solver_multi_checkpoint: one file holding the part(s) of MultiSolver.save_state() and the timer's state."""
+        rc = self.L.sphx_solver_multi_checkpoint(self.h, world.h, time_manager.h, str(path).encode())
+        if rc:
+            raise SphxError(rc, self.L.sphx_solver_last_error(self.h).decode())
+
+    def restore(self, world, time_manager, path, sync_world=False):
+        """sphx_solver_multi_restore: continue the run of the file; the timer gets the saved state, the world the saved boundary and the
+        run's particle count (sync_world=True also downloads its arrays)."""
+        rc = self.L.sphx_solver_multi_restore(self.h, world.h, time_manager.h, str(path).encode())
+        if rc:
+            raise SphxError(rc, self.L.sphx_solver_last_error(self.h).decode())
+        if sync_world:
+            self.sync_world(world)
+
 
 class WCSPHSolver(DFSPHSolver):
     """Box<dyn Solver> holding the HIP-backed WCSPHSolver (solver/wscsph.rs); the app pairs it with cfl_factor 0.2 (main.rs:116-119)."""

@@ -113,6 +113,8 @@ class SphxRect(C.Structure):
 
 STATE_DEVICE_BUFFER = 1  # sphx_state_save / sphx_state_load flags
 STATE_SECTIONS = ("positions", "velocities", "particle_id", "density", "alpha", "kappa", "stiffness", "accel", "boundary")  # SPHX_STATE_SEC_*
+MULTI_STATE_SECTIONS = ("positions", "velocities", "particle_id", "density", "alpha", "kappa", "stiffness", "boundary")  # SPHX_MULTI_STATE_SEC_*
+TILE_STATE_ZERO_KAPPA, TILE_STATE_ZERO_STIFFNESS = 1, 2  # sphx_tile_state_pack flags
 
 
 TRACK_DEVICE_POINTERS = 1  # sphx_track_fetch / sphx_track_read / sphx_download_by_id flags
@@ -191,6 +193,10 @@ LAYOUT_AUTO, LAYOUT_STRIPS, LAYOUT_GRID = 0, 1, 2
 # every symbol include/sphx.h declares: (restype, argtypes)
 _vp, _u16p = C.c_void_p, C.c_void_p
 _f, _u32, _u64, _i = C.c_float, C.c_uint32, C.c_uint64, C.c_int
+class SphxTileStateOut(C.Structure):  # sphx_tile_state_out: seven device pointers
+    _fields_ = [(k, C.c_void_p) for k in ("pos", "vel", "id", "density", "alpha", "kappa", "stiffness")]
+
+
 SIGNATURES = {
     "sphx_abi_version": (_u32, []),
     "sphx_default_params": (_i, [_f, _f, _f, C.POINTER(SphxParams)]),
@@ -225,6 +231,16 @@ SIGNATURES = {
     "sphx_multi_stats_record": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32, _u32]),
     "sphx_multi_stats_get_status": (_i, [_vp, C.POINTER(SphxStatsStatus)]),
     "sphx_multi_stats_read": (_i, [_vp, _u32, _u32, _vp, _vp]),
+    "sphx_tile_state_pack": (_i, [_vp, _u32, C.POINTER(SphxTileStateOut), C.POINTER(_u64), C.POINTER(_u32)]),
+    "sphx_tile_state_fetch": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u32)]),
+    "sphx_tile_upload_state": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u32]),
+    "sphx_get_tiling_invariant": (_i, [_vp]),
+    "sphx_multi_state_size": (_i, [_vp, C.POINTER(_u64)]),
+    "sphx_multi_state_save": (_i, [_vp, _vp, _u64, _u32, C.POINTER(_u64)]),
+    "sphx_multi_state_load": (_i, [_vp, C.POINTER(_vp), C.POINTER(_u64), _u32, _u32]),
+    "sphx_multi_state_digest": (_i, [_vp, C.POINTER(_u64)]),
+    "sphx_multi_state_save_file": (_i, [_vp, C.c_char_p]),
+    "sphx_multi_state_load_file": (_i, [_vp, C.c_char_p]),
     "sphx_debug_correction_counts": (_i, [_vp, _vp]),
     "sphx_download_by_id": (_i, [_vp, _u32, _u32, _u32, C.POINTER(SphxTrackOut), C.POINTER(_u32)]),
     "sphx_download": (_i, [_vp, _vp, _vp, _vp, _vp]),
@@ -345,6 +361,8 @@ SIGNATURES = {
     "sphx_timer_set_state": (_i, [_vp, C.POINTER(SphxTimerState)]),
     "sphx_solver_save": (_i, [_vp, _vp, _vp, C.c_char_p]),
     "sphx_solver_load": (_i, [_vp, _vp, _vp, C.c_char_p]),
+    "sphx_solver_multi_checkpoint": (_i, [_vp, _vp, _vp, C.c_char_p]),
+    "sphx_solver_multi_restore": (_i, [_vp, _vp, _vp, C.c_char_p]),
     "sphx_solver_create_dfsph": (_i, [_vp, C.POINTER(SphxParams), C.POINTER(_vp)]),
     "sphx_solver_create_wcsph": (_i, [_vp, C.POINTER(SphxParams), C.POINTER(_vp)]),
     "sphx_solver_create_dfsph_multi": (_i, [_vp, C.POINTER(SphxParams), C.POINTER(C.c_int), _i, C.POINTER(SphxMultiOptions), C.POINTER(_vp)]),

@@ -1,6 +1,7 @@
 // sphx_host.cpp — implementation of the host-side mirror (sphx_host.hpp) and its C exports (include/sphx.h, bottom half).
 #include "sphx_host.hpp"
 
+#include "sphx_multi_state_format.hpp"
 #include "sphx_state_format.hpp"
 
 #include <fcntl.h>
@@ -586,6 +587,102 @@ int HipDfsphSolver::load(FluidParticleWorld& w, TimeManager& tm, const char* pat
     return edit_done(w, false, SPHX_OK);
 }
 
+// ---- the tiled run in one file: {CheckpointFileHeader with the timer's state, the part(s) of sphx_multi_state_save} ----------------------
+int HipDfsphMultiSolver::checkpoint(const FluidParticleWorld& w, const TimeManager& tm, const char* path) {
+    auto fail = [&](int rc, const std::string& what) {
+        last_error = what;
+        return last_status = rc;
+    };
+    if (!multi_) return last_status = SPHX_ERR_NO_DEVICE;
+    if (!path) return fail(SPHX_ERR_INVALID_ARGUMENT, "checkpoint: path is NULL");
+    if (uploaded_n_ == (size_t)-1 || w.particles.positions.size() != uploaded_n_ || w.fluid_generation != uploaded_generation_)
+        return fail(SPHX_ERR_NOT_READY, "checkpoint: the tiles do not hold this world yet (step first)");
+    namespace ms = sphx_multi_state;
+    uint64_t bytes = 0;
+    int rc;
+    if ((rc = sphx_multi_state_size(multi_, &bytes))) return fail(rc, sphx_multi_last_error(multi_));
+    std::vector<unsigned char> file(sizeof(ms::CheckpointFileHeader) + bytes);
+    if ((rc = sphx_multi_state_save(multi_, file.data() + sizeof(ms::CheckpointFileHeader), bytes, 0u, nullptr))) return fail(rc, sphx_multi_last_error(multi_));
+    ms::CheckpointFileHeader fh;
+    std::memset(&fh, 0, sizeof(fh));
+    std::memcpy(fh.magic, ms::CHECKPOINT_MAGIC, 8);
+    fh.version = ms::VERSION;
+    fh.endian_tag = ms::ENDIAN_TAG;
+    fh.parts_bytes = bytes;
+    fh.timer = tm.get_state();
+    std::memcpy(file.data(), &fh, sizeof(fh));
+    const std::string tmp = std::string(path) + ".tmp";
+    FILE* f = std::fopen(tmp.c_str(), "wb");
+    bool ok = f != nullptr;
+    if (ok) {
+        ok = std::fwrite(file.data(), 1, file.size(), f) == file.size();
+        ok = std::fclose(f) == 0 && ok;
+    }
+    if (ok) ok = std::rename(tmp.c_str(), path) == 0;
+    if (!ok) {
+        const std::string e = std::strerror(errno);
+        std::remove(tmp.c_str());
+        return fail(SPHX_ERR_INVALID_ARGUMENT, "checkpoint: cannot write " + std::string(path) + ": " + e);
+    }
+    return last_status = SPHX_OK;
+}
+
+int HipDfsphMultiSolver::restore(FluidParticleWorld& w, TimeManager& tm, const char* path) {
+    auto fail = [&](int rc, const std::string& what) {
+        last_error = what;
+        return last_status = rc;
+    };
+    if (!multi_) return last_status = SPHX_ERR_NO_DEVICE;
+    if (!path) return fail(SPHX_ERR_INVALID_ARGUMENT, "restore: path is NULL");
+    namespace ms = sphx_multi_state;
+    FILE* f = std::fopen(path, "rb");
+    if (!f) return fail(SPHX_ERR_INVALID_ARGUMENT, "restore: cannot open " + std::string(path) + ": " + std::strerror(errno));
+    std::vector<unsigned char> file;
+    unsigned char chunk[1 << 16];
+    size_t got;
+    while ((got = std::fread(chunk, 1, sizeof(chunk), f)) > 0) file.insert(file.end(), chunk, chunk + got);
+    const bool bad = std::ferror(f) != 0;
+    std::fclose(f);
+    if (bad) return fail(SPHX_ERR_INVALID_ARGUMENT, "restore: cannot read " + std::string(path));
+    ms::CheckpointFileHeader fh;
+    std::string why;
+    if (!ms::validate_checkpoint_file(file.data(), file.size(), &fh, &why)) return fail(SPHX_ERR_INVALID_ARGUMENT, "restore: " + why);
+    const unsigned char* body = file.data() + sizeof(fh);
+    std::vector<std::pair<uint64_t, uint64_t>> pieces;
+    if (fh.parts_bytes == 0 || !ms::split_parts(body, fh.parts_bytes, &pieces, &why)) return fail(SPHX_ERR_INVALID_ARGUMENT, "restore: " + (fh.parts_bytes ? why : std::string("the file holds no part")));
+    std::vector<const void*> parts;
+    std::vector<uint64_t> bytes;
+    for (const auto& pc : pieces) {
+        parts.push_back(body + pc.first);
+        bytes.push_back(pc.second);
+    }
+    ms::Header h;
+    if (!ms::validate(parts[0], bytes[0], &h, &why)) return fail(SPHX_ERR_INVALID_ARGUMENT, "restore: " + why);
+    // (sphx_multi_state_load validates again, the set and against this multi; a refusal there has changed nothing either)
+    if (int rc = sphx_multi_state_load(multi_, parts.data(), bytes.data(), (uint32_t)parts.size(), 0u)) {
+        const std::string e = sphx_multi_last_error(multi_);
+        // refused before anything changed: the tiles still hold the world; broken half way: the next step uploads the world
+        uint64_t unused;
+        if (sphx_multi_state_size(multi_, &unused) == SPHX_ERR_NOT_READY) uploaded_n_ = (size_t)-1;
+        return fail(rc, e);
+    }
+    tm.set_state(fh.timer);  // (validated above)
+    const sphx_state::Section& sb = h.sec[ms::SEC_BOUNDARY];
+    w.particles.boundary_particles.resize(h.s.b);
+    if (sb.bytes) std::memcpy(&w.particles.boundary_particles[0].x, (const unsigned char*)parts[0] + sb.offset, sb.bytes);
+    w.boundary_changed = false;  // the tiles hold exactly this boundary
+    // the count follows the device, the contents are behind it (as after a headless step): the next simulation_step does not upload
+    const size_t n = (size_t)h.s.n_total;
+    w.particles.positions.resize(n);
+    w.particles.velocities.resize(n, Vector{0, 0});
+    w.particles.densities.resize(n, 0.0f);
+    w.particles.particle_ids.clear();
+    w.stale_prefix = n;
+    uploaded_n_ = n;
+    uploaded_generation_ = w.fluid_generation;
+    return last_status = SPHX_OK;
+}
+
 }  // namespace sph
 
 // =====================================================================================================================
@@ -779,6 +876,24 @@ int sphx_solver_save(sphx_solver* s, sphx_world* w, sphx_timer* t, const char* p
 int sphx_solver_load(sphx_solver* s, sphx_world* w, sphx_timer* t, const char* path) {
     if (!s || !w || !t || !path) return SPHX_ERR_INVALID_ARGUMENT;
     return s->s.load(w->w, t->t, path);
+}
+int sphx_solver_multi_checkpoint(sphx_solver* s, sphx_world* w, sphx_timer* t, const char* path) {
+    if (!s || !w || !t || !path) return SPHX_ERR_INVALID_ARGUMENT;
+    auto* ms = dynamic_cast<sph::HipDfsphMultiSolver*>(s->sp);
+    if (!ms) {
+        s->s.last_error = "sphx_solver_multi_checkpoint: not the multi-GPU solver (sphx_solver_save serves this one)";
+        return s->s.last_status = SPHX_ERR_INVALID_ARGUMENT;
+    }
+    return ms->checkpoint(w->w, t->t, path);
+}
+int sphx_solver_multi_restore(sphx_solver* s, sphx_world* w, sphx_timer* t, const char* path) {
+    if (!s || !w || !t || !path) return SPHX_ERR_INVALID_ARGUMENT;
+    auto* ms = dynamic_cast<sph::HipDfsphMultiSolver*>(s->sp);
+    if (!ms) {
+        s->s.last_error = "sphx_solver_multi_restore: not the multi-GPU solver (sphx_solver_load serves this one)";
+        return s->s.last_status = SPHX_ERR_INVALID_ARGUMENT;
+    }
+    return ms->restore(w->w, t->t, path);
 }
 sphx_ctx* sphx_solver_ctx(sphx_solver* s) { return s->s.ctx(); }
 sphx_multi* sphx_solver_multi(sphx_solver* s) {

@@ -196,6 +196,10 @@ class HipDfsphMultiSolver : public HipDfsphSolver {
     int remove(FluidParticleWorld&, const sphx_rect*, uint32_t, uint32_t, bool, uint32_t*) override { return no_edit(); }
     int save(const FluidParticleWorld&, const TimeManager&, const char*) override { return no_edit("save / load"); }
     int load(FluidParticleWorld&, TimeManager&, const char*) override { return no_edit("save / load"); }
+    // The tiled run put down into one file and picked up from it (sphx_solver_multi_checkpoint / _restore in sphx.h): the part(s) of
+    // sphx_multi_state_save behind a header with the timer's state.  Names of their own: save / load above keep refusing.
+    int checkpoint(const FluidParticleWorld& fluid_world, const TimeManager& time_manager, const char* path);
+    int restore(FluidParticleWorld& fluid_world, TimeManager& time_manager, const char* path);
     sphx_multi* multi() { return multi_; }
 
    private:

@@ -335,6 +335,10 @@ struct sphx_ctx {
     bool uploaded = false, boundary_changed = true, tails_dirty = true, in_step = false;
     bool lists_current = false;  // the neighbour lists were built from the positions the arrays hold (raised by a completed build, dropped with q_noclamp)
     unsigned long long* state_dig = nullptr;  // sphx_state_*: one digest per section (device), allocated on first use
+    // sphx_tile_state_pack (sphx_multi_state.inc): digests, the seven compacted sections of the owned particles and the scan's words
+    uint32_t* mstate_buf = nullptr;
+    size_t mstate_cap = 0;   // ... in 4-byte words
+    uint32_t mstate_n = 0;   // ... and the local count of the pass that filled it
     uint32_t fast_walk_ok = 0;  // this smoothing length allows the FAST walks (sqrt_dist); K.q_noclamp = fast_walk_ok while the lists are fresh
     // field sampling (sphx_sample_*): 2 = the cell grids and density[] belong to the current positions (a build plus densities), 1 = a
     // build without densities since, 0 = positions / boundary replaced or a step open; sample_missing says what a query is waiting for

@@ -3344,3 +3344,5 @@ __global__ __launch_bounds__(64) void k_publish(DevScalars* scal, Mailbox* mb, u
 #include "sphx_fields.inc"
 // fluid statistics: counts, float64 sums and extremes of the fluid and of probe rectangles, the time-series recorder (kernels + C ABI)
 #include "sphx_stats.inc"
+// a tiled run's checkpoint, device half: the owned particles compacted into sections with id-keyed digests (kernels + the tile seam)
+#include "sphx_multi_state.inc"

@@ -22,6 +22,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <cmath>
 #include <condition_variable>
 #include <cstdint>
@@ -39,6 +40,7 @@
 #include <vector>
 
 #include "../../include/sphx.h"
+#include "sphx_multi_state_format.hpp"
 #include "sphx_stats_merge.hpp"
 
 namespace {
@@ -614,7 +616,9 @@ struct TileDriver {
     }
 
     // ---- set-up: every rank is given the SAME global arrays (deterministic scene) and keeps its own cells
-    int setup(const Layout& lay, const float* pos, const float* vel, const uint32_t* ids, uint32_t n, const float* bnd, uint32_t nb) {
+    // kap / stf (sphx_multi_state_load): the warm-start sums of the particles, installed with them; the caller then restores the counts
+    int setup(const Layout& lay, const float* pos, const float* vel, const uint32_t* ids, uint32_t n, const float* bnd, uint32_t nb, const float* kap = nullptr,
+              const float* stf = nullptr) {
         layout = lay;
         if (layout.world() != comm->world) return fail(SPHX_ERR_INVALID_ARGUMENT, "layout and communicator disagree about the number of tiles");
         // Every rank is handed the GLOBAL scene (128 M particles at configs[4]): cells, bounding box, owner and send-band counts of all of
@@ -740,7 +744,17 @@ struct TileDriver {
             }
             id[k] = ids ? ids[i] : i;
         }
-        TCHK(sphx_tile_upload(ctx, p.data(), v.data(), id.data(), (uint32_t)n_own));
+        if (kap && stf) {
+            std::vector<float> ka(n_own), sf(n_own);
+            for (uint64_t k = 0; k < n_own; ++k) {
+                ka[k] = kap[mine[k]];
+                sf[k] = stf[mine[k]];
+            }
+            TCHK(sphx_tile_carry_warmstart(ctx, 1, 1));  // (the re-grid below moves them with their particles)
+            TCHK(sphx_tile_upload_state(ctx, p.data(), v.data(), id.data(), ka.data(), sf.data(), (uint32_t)n_own));
+        } else {
+            TCHK(sphx_tile_upload(ctx, p.data(), v.data(), id.data(), (uint32_t)n_own));
+        }
         n_owned_global = n;
         num_density_iters = 1;
         num_divergence_iters = 0;
@@ -1011,6 +1025,35 @@ struct TileDriver {
             return fail(SPHX_ERR_HIP, "copying the statistics records back");
         return SPHX_OK;
     }
+
+    // sphx_multi_state_*, first half: the pass over this tile's arrays goes onto its stream; nothing is waited for.  The warm-start
+    // sections are canonical: zeros where the next loop will not warm-start (dfsph.rs:199 / :354)
+    sphx_tile_state_out state_out{};
+    uint64_t state_dig[7] = {0};
+    uint32_t state_owned = 0;
+    int state_enqueue() {
+        const uint32_t flags = (num_density_iters <= 1 ? SPHX_TILE_STATE_ZERO_KAPPA : 0u) | (num_divergence_iters <= 1 ? SPHX_TILE_STATE_ZERO_STIFFNESS : 0u);
+        const int rc = sphx_tile_state_pack(ctx, flags, &state_out, nullptr, nullptr);
+        if (rc) err = std::string("sphx_tile_state_pack: ") + sphx_last_error(ctx);  // (a state error of one call: nobody is waiting in an all-reduce)
+        return rc;
+    }
+    // ... second half: the digests and the owned count come back
+    int state_fetch() {
+        const int rc = sphx_tile_state_fetch(ctx, state_dig, &state_owned);
+        if (rc) err = std::string("sphx_tile_state_fetch: ") + sphx_last_error(ctx);
+        return rc;
+    }
+    // ... and `words` 32-bit words per particle of one section into host memory (queued; state_wait() completes them)
+    int state_copy(const void* d_section, uint32_t words, void* host) {
+        if (!state_owned) return SPHX_OK;
+        if (hipSetDevice(device) != hipSuccess || hipMemcpyAsync(host, d_section, (size_t)state_owned * words * 4, hipMemcpyDeviceToHost, stream) != hipSuccess)
+            return fail(SPHX_ERR_HIP, "copying a checkpoint section back");
+        return SPHX_OK;
+    }
+    int state_wait() {
+        if (hipSetDevice(device) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return fail(SPHX_ERR_HIP, "waiting for the checkpoint sections");
+        return SPHX_OK;
+    }
 };
 
 // which layout for `world` tiles over these particles: 2x2 (2 x N/2) on 4 tiles, strips along the longer side otherwise
@@ -1064,6 +1107,7 @@ struct sphx_multi {
     bool have_layout = false;
     Layout explicit_layout;
     bool uploaded = false;  // a sphx_multi_upload has succeeded: the contexts are tiles and hold a re-gridded particle set
+    bool state_broken = false;  // a sphx_multi_state_load found a digest mismatch after the copy: the multi asks for an upload or a load
 
     // run f(tile, index) on every tile, each on its own host thread (the tiles meet in barriers); returns the first error
     int each(const std::function<int(TileDriver&, size_t)>& f) {
@@ -1210,12 +1254,19 @@ int sphx_multi_upload(sphx_multi* m, const float* pos_xy, const float* vel_xy, c
     const int rc = m->each([&](TileDriver& t, size_t) {
         return t.setup(L, pos_xy, vel_xy, ids, n, m->boundary.empty() ? nullptr : m->boundary.data(), (uint32_t)(m->boundary.size() / 2));
     });
-    if (!rc) m->uploaded = true;
+    if (!rc) {
+        m->uploaded = true;
+        m->state_broken = false;
+    }
     return rc;
 }
 
 int sphx_multi_step_begin(sphx_multi* m, float dt_prev, float* out_vmax) {
     if (!m || !out_vmax) return SPHX_ERR_INVALID_ARGUMENT;
+    if (m->state_broken) {
+        m->err = "sphx_multi_step_begin: the last sphx_multi_state_load did not complete (upload or load a state first)";
+        return SPHX_ERR_NOT_READY;
+    }
     std::vector<float> v(m->tiles.size(), 0.0f);
     const int rc = m->each([&](TileDriver& t, size_t k) { return t.step_begin(dt_prev, &v[k]); });
     if (rc) return rc;
@@ -1519,6 +1570,406 @@ int sphx_multi_stats_read(sphx_multi* m, uint32_t first_frame, uint32_t n_frames
     if ((rc = stats_gather(m, local, cnt, all))) return rc;
     for (size_t r = 0; r < cnt; ++r) out[r] = sphx_stats_host::fold(all.data(), (uint32_t)m->world, cnt, (uint32_t)r);
     return SPHX_OK;
+}
+
+}  // extern "C"
+
+// ---- checkpoint of the tiled run (include/sphx.h, "checkpoint of a tiled run"; the device pass is csrc/sphx_multi_state.inc) ------------------
+namespace {
+
+namespace ms = sphx_multi_state;
+
+int multi_state_ready(sphx_multi* m, const char* fn, bool need_state) {
+    for (auto& t : m->tiles) {
+        if (t->poisoned) {
+            m->err = std::string(fn) + ": a collective step of this multi has failed (create a new one)";
+            return SPHX_ERR_NOT_READY;
+        }
+        if (t->in_step) {
+            m->err = std::string(fn) + ": between sphx_multi_step_begin and sphx_multi_step_finish (finish the step first)";
+            return SPHX_ERR_NOT_READY;
+        }
+    }
+    if (need_state && !m->uploaded) {
+        m->err = std::string(fn) + (m->state_broken ? ": the last sphx_multi_state_load did not complete (upload or load a state first)" : ": before the first sphx_multi_upload or sphx_multi_state_load");
+        return SPHX_ERR_NOT_READY;
+    }
+    return SPHX_OK;
+}
+
+// the header of the live state for the local tiles' part (digests not yet filled): n_part particles in this part
+void multi_state_header(const sphx_multi* m, uint64_t n_part, ms::Header& h) {
+    const TileDriver& t = *m->tiles[0];
+    std::memset(&h, 0, sizeof(h));
+    h.params = m->P;
+    h.params.device = 0;
+    ms::Scalars& s = h.s;
+    s.n_part = (uint32_t)n_part;
+    s.n_total = m->rank_mode ? t.n_owned_global : n_part;
+    s.b = (uint32_t)(t.boundary.size() / 2);
+    s.part = m->rank_mode ? (uint32_t)t.comm->rank : 0u;
+    s.n_parts = m->rank_mode ? (uint32_t)m->world : 1u;
+    s.num_density_iters = t.num_density_iters;
+    s.num_divergence_iters = t.num_divergence_iters;
+    s.last_div_iters = t.last_div_iters;
+    s.last_div_warm = t.last_div_warm;
+    s.steps = t.steps;
+    s.tiling_invariant = sphx_get_tiling_invariant(t.ctx) ? 1u : 0u;
+    s.world = (uint32_t)m->world;
+    const Layout& L = t.layout;
+    s.axis = L.axis >= 0 ? L.axis : -1;
+    s.nx = L.axis >= 0 ? 1u : (uint32_t)L.nx;
+    s.ny = L.axis >= 0 ? 1u : (uint32_t)L.ny;
+    uint32_t k = 0;
+    for (uint32_t c : L.xcuts) s.cuts[k++] = c;
+    if (L.axis < 0)
+        for (const auto& col : L.ycuts)
+            for (uint32_t c : col) s.cuts[k++] = c;
+    s.n_cuts = k;
+    ms::layout(h);
+}
+
+// every local tile's pass: enqueued on all of them first, then the digests and counts fetched (the passes overlap)
+int multi_state_pack(sphx_multi* m) {
+    int rc;
+    for (size_t k = 0; k < m->tiles.size(); ++k)
+        if ((rc = m->tiles[k]->state_enqueue())) {
+            m->err = "tile " + std::to_string(k) + ": " + m->tiles[k]->err;
+            return rc;
+        }
+    for (size_t k = 0; k < m->tiles.size(); ++k)
+        if ((rc = m->tiles[k]->state_fetch())) {
+            m->err = "tile " + std::to_string(k) + ": " + m->tiles[k]->err;
+            return rc;
+        }
+    return SPHX_OK;
+}
+
+// the local tiles' seven digests, summed mod 2^64; rank mode with `across`: summed over the ranks too — each 64-bit word as two integers
+// below 2^32 (a sum of <= 64 of them is exact in a double), so that every rank ends with the same bytes
+int multi_state_sum(sphx_multi* m, bool across, uint64_t* out7) {
+    for (int s = 0; s < 7; ++s) {
+        out7[s] = 0;
+        for (auto& t : m->tiles) out7[s] += t->state_dig[s];
+    }
+    if (!m->rank_mode || !across || m->world == 1) return SPHX_OK;
+    TileDriver& t = *m->tiles[0];
+    double limbs[16] = {0}, sums[16] = {0};
+    for (int s = 0; s < 7; ++s) {
+        limbs[2 * s] = (double)(uint32_t)out7[s];
+        limbs[2 * s + 1] = (double)(uint32_t)(out7[s] >> 32);
+    }
+    for (int part = 0; part < 2; ++part) {
+        const int rc = t.comm->allreduce(limbs + 8 * part, 8, 0, sums + 8 * part);
+        if (rc) {
+            m->err = "the checkpoint digests could not be exchanged between the ranks";
+            return t.fail(rc, m->err);
+        }
+    }
+    for (int s = 0; s < 7; ++s) out7[s] = (uint64_t)sums[2 * s] + ((uint64_t)sums[2 * s + 1] << 32);
+    return SPHX_OK;
+}
+
+bool read_whole_file(const std::string& path, std::vector<unsigned char>& out) {
+    FILE* f = std::fopen(path.c_str(), "rb");
+    if (!f) return false;
+    out.clear();
+    unsigned char chunk[1 << 16];
+    size_t got;
+    while ((got = std::fread(chunk, 1, sizeof(chunk), f)) > 0) out.insert(out.end(), chunk, chunk + got);
+    const bool bad = std::ferror(f) != 0;
+    std::fclose(f);
+    return !bad;
+}
+bool file_exists(const std::string& path) {
+    FILE* f = std::fopen(path.c_str(), "rb");
+    if (f) std::fclose(f);
+    return f != nullptr;
+}
+std::string part_suffix(uint32_t r, uint32_t w) {
+    char b[32];
+    std::snprintf(b, sizeof(b), ".r%03uof%03u", r, w);
+    return b;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sphx_multi_state_size(sphx_multi* m, uint64_t* out_bytes) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    if (!out_bytes) {
+        m->err = "sphx_multi_state_size: out_bytes is NULL";
+        return SPHX_ERR_INVALID_ARGUMENT;
+    }
+    *out_bytes = 0;
+    if (int rc = multi_state_ready(m, "sphx_multi_state_size", true)) return rc;
+    if (m->world > (int)ms::MAX_TILES) {
+        m->err = "sphx_multi_state_size: more than 64 tiles";
+        return SPHX_ERR_INVALID_ARGUMENT;
+    }
+    if (int rc = multi_state_pack(m)) return rc;  // (the owned counts are the device's: 4 bytes per local particle would do, the pass is cheap)
+    uint64_t n = 0;
+    for (auto& t : m->tiles) n += t->state_owned;
+    ms::Header h;
+    multi_state_header(m, n, h);
+    *out_bytes = h.total_bytes;
+    return SPHX_OK;
+}
+
+int sphx_multi_state_save(sphx_multi* m, void* buf, uint64_t capacity, uint32_t flags, uint64_t* out_bytes) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    if (out_bytes) *out_bytes = 0;
+    auto bad = [&](const std::string& what) {
+        m->err = "sphx_multi_state_save: " + what;
+        return SPHX_ERR_INVALID_ARGUMENT;
+    };
+    if (flags) return bad("unknown flags bits");
+    if (m->world > (int)ms::MAX_TILES) return bad("more than 64 tiles");
+    int rc;
+    if ((rc = multi_state_ready(m, "sphx_multi_state_save", true))) return rc;
+    if ((rc = multi_state_pack(m))) return rc;
+    uint64_t n = 0;
+    for (auto& t : m->tiles) n += t->state_owned;
+    if (n >= ms::MAX_PART) return bad("more than 2^28 particles in one part");
+    ms::Header h;
+    multi_state_header(m, n, h);
+    if (out_bytes) *out_bytes = h.total_bytes;
+    if (!buf) return bad("buf is NULL");
+    if (capacity < h.total_bytes) {
+        m->err = "sphx_multi_state_save: the buffer is smaller than sphx_multi_state_size";
+        return SPHX_ERR_CAPACITY;
+    }
+    unsigned char* const b = (unsigned char*)buf;
+    // the tiles' sections, tile after tile in ascending rank, every tile copying on its own stream
+    uint64_t before = 0;
+    for (size_t k = 0; k < m->tiles.size(); ++k) {
+        TileDriver& t = *m->tiles[k];
+        const sphx_tile_state_out& o = t.state_out;
+        const void* src[ms::NPARTICLE_SEC] = {o.pos, o.vel, o.id, o.density, o.alpha, o.kappa, o.stiffness};
+        for (uint32_t s = 0; s < ms::NPARTICLE_SEC; ++s) {
+            const uint32_t w = ms::section_words(s);
+            if ((rc = t.state_copy(src[s], w, b + h.sec[s].offset + before * w * 4u))) {
+                m->err = "tile " + std::to_string(k) + ": " + t.err;
+                return rc;
+            }
+        }
+        before += t.state_owned;
+    }
+    const std::vector<float>& bnd = m->tiles[0]->boundary;
+    if (!bnd.empty()) std::memcpy(b + h.sec[ms::SEC_BOUNDARY].offset, bnd.data(), bnd.size() * 4);
+    for (uint32_t s = 0; s < ms::NSEC; ++s) {
+        const uint64_t end = h.sec[s].offset + h.sec[s].bytes, next = s + 1 < ms::NSEC ? h.sec[s + 1].offset : h.total_bytes;
+        if (next > end) std::memset(b + end, 0, next - end);
+    }
+    uint64_t dig[7];
+    if ((rc = multi_state_sum(m, false, dig))) return rc;  // (this part's own: nothing crosses the ranks for a save)
+    for (uint32_t s = 0; s < ms::NPARTICLE_SEC; ++s) h.sec[s].digest = dig[s];
+    h.sec[ms::SEC_BOUNDARY].digest = sphx_state::digest_words(bnd.data(), bnd.size());
+    ms::seal(h);
+    std::memcpy(b, &h, sizeof(h));
+    for (size_t k = 0; k < m->tiles.size(); ++k)
+        if ((rc = m->tiles[k]->state_wait())) {
+            m->err = "tile " + std::to_string(k) + ": " + m->tiles[k]->err;
+            return rc;
+        }
+    return SPHX_OK;
+}
+
+int sphx_multi_state_digest(sphx_multi* m, uint64_t* out) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    if (!out) {
+        m->err = "sphx_multi_state_digest: out is NULL";
+        return SPHX_ERR_INVALID_ARGUMENT;
+    }
+    int rc;
+    if ((rc = multi_state_ready(m, "sphx_multi_state_digest", true))) return rc;
+    if ((rc = multi_state_pack(m))) return rc;
+    if ((rc = multi_state_sum(m, true, out))) return rc;
+    const std::vector<float>& bnd = m->tiles[0]->boundary;
+    out[ms::SEC_BOUNDARY] = sphx_state::digest_words(bnd.data(), bnd.size());
+    return SPHX_OK;
+}
+
+int sphx_multi_state_load(sphx_multi* m, const void* const* parts, const uint64_t* bytes, uint32_t n_parts, uint32_t flags) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    auto bad = [&](const std::string& what) {
+        m->err = "sphx_multi_state_load: " + what;
+        return SPHX_ERR_INVALID_ARGUMENT;
+    };
+    if (flags) return bad("unknown flags bits");
+    if (!parts || !bytes || n_parts == 0) return bad("parts or bytes is NULL, or n_parts is 0");
+    if (n_parts > ms::MAX_TILES) return bad("more than 64 parts");
+    if (m->world > (int)ms::MAX_TILES) return bad("more than 64 tiles");
+    int rc;
+    if ((rc = multi_state_ready(m, "sphx_multi_state_load", false))) return rc;
+    // ---- host-side validation: nothing of the multi changes before it has passed --------------------------------------------------------
+    std::vector<ms::Header> hs(n_parts);
+    std::string why;
+    for (uint32_t i = 0; i < n_parts; ++i)
+        if (!ms::validate(parts[i], bytes[i], &hs[i], &why)) return bad("part " + std::to_string(i) + ": " + why);
+    if (!ms::validate_set(hs.data(), n_parts, &why)) return bad(why);
+    const ms::Header& h0 = hs[0];
+    if (const char* field = sphx_state::params_mismatch(h0.params, m->P))
+        return bad(std::string("the checkpoint was saved under other params than this multi's; first field that differs: ") + field);
+    for (auto& t : m->tiles)
+        if ((h0.s.tiling_invariant != 0) != (sphx_get_tiling_invariant(t->ctx) != 0))
+            return bad(h0.s.tiling_invariant ? "the checkpoint was saved in tiling-invariant mode, this multi's tiles are not in it"
+                                             : "this multi's tiles are in tiling-invariant mode, the checkpoint was not saved in it");
+    // the parts in the order of their index; ids, padding and the boundary of each
+    std::vector<uint32_t> order(n_parts);
+    for (uint32_t i = 0; i < n_parts; ++i) order[hs[i].s.part] = i;  // (validate_set: a permutation of 0 .. n_parts - 1)
+    const uint64_t n = h0.s.n_total;
+    const uint32_t nb = h0.s.b;
+    for (uint32_t i = 0; i < n_parts; ++i) {
+        const unsigned char* p = (const unsigned char*)parts[i];
+        const ms::Header& h = hs[i];
+        if (!ms::padding_is_zero(p, h)) return bad("part " + std::to_string(i) + ": padding bytes are not zero");
+        const ms::Section& sb = h.sec[ms::SEC_BOUNDARY];
+        std::vector<float> bnd((size_t)nb * 2);
+        if (sb.bytes) std::memcpy(bnd.data(), p + sb.offset, sb.bytes);
+        if (sphx_state::digest_words(bnd.data(), sb.bytes / 4u) != sb.digest) return bad("part " + std::to_string(i) + ": digest mismatch in section boundary");
+        const ms::Section& si = h.sec[SPHX_MULTI_STATE_SEC_PARTICLE_ID];
+        for (uint64_t k = 0; k < h.s.n_part; ++k) {
+            uint32_t id;
+            std::memcpy(&id, p + si.offset + 4 * k, 4);
+            if (id >> 31) return bad("part " + std::to_string(i) + ": a particle id is not below 2^31");
+        }
+    }
+    // the global arrays, parts in ascending index (as sphx_multi_upload is given them)
+    std::vector<float> pos(2 * n), vel(2 * n), kap(n), stf(n), bnd((size_t)nb * 2);
+    std::vector<uint32_t> ids(n);
+    uint64_t want[7] = {0};
+    {
+        uint64_t at = 0;
+        for (uint32_t r = 0; r < n_parts; ++r) {
+            const unsigned char* p = (const unsigned char*)parts[order[r]];
+            const ms::Header& h = hs[order[r]];
+            const uint64_t k = h.s.n_part;
+            if (k) {
+                std::memcpy(pos.data() + 2 * at, p + h.sec[SPHX_MULTI_STATE_SEC_POSITIONS].offset, 8 * k);
+                std::memcpy(vel.data() + 2 * at, p + h.sec[SPHX_MULTI_STATE_SEC_VELOCITIES].offset, 8 * k);
+                std::memcpy(ids.data() + at, p + h.sec[SPHX_MULTI_STATE_SEC_PARTICLE_ID].offset, 4 * k);
+                std::memcpy(kap.data() + at, p + h.sec[SPHX_MULTI_STATE_SEC_KAPPA].offset, 4 * k);
+                std::memcpy(stf.data() + at, p + h.sec[SPHX_MULTI_STATE_SEC_STIFFNESS].offset, 4 * k);
+            }
+            at += k;
+            for (int s = 0; s < 7; ++s) want[s] += h.sec[s].digest;
+        }
+        const ms::Section& sb = h0.sec[ms::SEC_BOUNDARY];
+        if (sb.bytes) std::memcpy(bnd.data(), (const unsigned char*)parts[0] + sb.offset, sb.bytes);
+    }
+    // the layout: an explicit one; else the saver's, if it had as many tiles; else the quantile layout over the checkpoint's positions
+    Layout L;
+    if (m->have_layout) {
+        L = m->explicit_layout;
+    } else if ((int)h0.s.world == m->world) {
+        const ms::Scalars& s = h0.s;
+        L.axis = s.axis;
+        if (s.axis >= 0) {
+            L.xcuts.assign(s.cuts, s.cuts + s.n_cuts);
+        } else {
+            L.nx = (int)s.nx;
+            L.ny = (int)s.ny;
+            L.xcuts.assign(s.cuts, s.cuts + s.nx + 1);
+            for (uint32_t ix = 0; ix < s.nx; ++ix) L.ycuts.emplace_back(s.cuts + s.nx + 1 + ix * (s.ny + 1), s.cuts + s.nx + 1 + (ix + 1) * (s.ny + 1));
+        }
+    } else {
+        L = make_layout(m->O, m->P, m->world, pos.data(), (uint32_t)n);
+    }
+    if (L.world() != m->world) return bad("the layout set for this multi and its tile count disagree");
+    // ---- from here on the multi changes -----------------------------------------------------------------------------------------------------
+    auto broken = [&](int code) {  // the tiles hold half a state: the multi asks for an upload or a load
+        m->uploaded = false;
+        m->state_broken = true;
+        return code;
+    };
+    m->boundary = bnd;
+    rc = m->each([&](TileDriver& t, size_t) {
+        const int e = t.setup(L, pos.data(), vel.data(), ids.data(), (uint32_t)n, bnd.empty() ? nullptr : bnd.data(), nb, kap.data(), stf.data());
+        // (setup ends with the one halo exchange and re-grid; it left the counts of a fresh upload)
+        t.num_density_iters = h0.s.num_density_iters;
+        t.num_divergence_iters = h0.s.num_divergence_iters;
+        t.last_div_iters = h0.s.last_div_iters;
+        t.last_div_warm = h0.s.last_div_warm;
+        t.steps = h0.s.steps;
+        return e;
+    });
+    if (rc) return broken(rc);
+    m->uploaded = true;
+    m->state_broken = false;
+    // what arrived, digested where it now lives
+    uint64_t got[7];
+    if ((rc = multi_state_pack(m)) || (rc = multi_state_sum(m, true, got))) return broken(rc);
+    for (uint32_t s : {(uint32_t)SPHX_MULTI_STATE_SEC_POSITIONS, (uint32_t)SPHX_MULTI_STATE_SEC_VELOCITIES, (uint32_t)SPHX_MULTI_STATE_SEC_PARTICLE_ID,
+                       (uint32_t)SPHX_MULTI_STATE_SEC_KAPPA, (uint32_t)SPHX_MULTI_STATE_SEC_STIFFNESS})
+        if (got[s] != want[s]) return broken(bad(std::string("digest mismatch in section ") + ms::section_name(s) + " (upload or load a state again)"));
+    return SPHX_OK;
+}
+
+int sphx_multi_state_save_file(sphx_multi* m, const char* path) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    if (!path) {
+        m->err = "sphx_multi_state_save_file: path is NULL";
+        return SPHX_ERR_INVALID_ARGUMENT;
+    }
+    uint64_t bytes = 0;
+    int rc;
+    if ((rc = sphx_multi_state_size(m, &bytes))) return rc;
+    std::vector<unsigned char> blob(bytes);
+    if ((rc = sphx_multi_state_save(m, blob.data(), bytes, 0u, nullptr))) return rc;
+    const std::string dst = std::string(path) + (m->rank_mode ? part_suffix((uint32_t)m->tiles[0]->comm->rank, (uint32_t)m->world) : std::string());
+    const std::string tmp = dst + ".tmp";
+    FILE* f = std::fopen(tmp.c_str(), "wb");
+    bool ok = f != nullptr;
+    if (ok) {
+        ok = std::fwrite(blob.data(), 1, blob.size(), f) == blob.size();
+        ok = std::fclose(f) == 0 && ok;
+    }
+    if (ok) ok = std::rename(tmp.c_str(), dst.c_str()) == 0;
+    if (!ok) {
+        const std::string e = std::strerror(errno);
+        std::remove(tmp.c_str());
+        m->err = "sphx_multi_state_save_file: cannot write " + dst + ": " + e;
+        return SPHX_ERR_INVALID_ARGUMENT;
+    }
+    return SPHX_OK;
+}
+
+int sphx_multi_state_load_file(sphx_multi* m, const char* path) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    auto bad = [&](const std::string& what) {
+        m->err = "sphx_multi_state_load_file: " + what;
+        return SPHX_ERR_INVALID_ARGUMENT;
+    };
+    if (!path) return bad("path is NULL");
+    std::vector<std::vector<unsigned char>> files;
+    std::vector<const void*> parts;
+    std::vector<uint64_t> bytes;
+    if (file_exists(path)) {
+        files.emplace_back();
+        if (!read_whole_file(path, files[0])) return bad(std::string("cannot read ") + path);
+        std::vector<std::pair<uint64_t, uint64_t>> pieces;
+        std::string why;
+        if (files[0].empty() || !ms::split_parts(files[0].data(), files[0].size(), &pieces, &why)) return bad(files[0].empty() ? "the file is empty" : why);
+        for (const auto& pc : pieces) {
+            parts.push_back(files[0].data() + pc.first);
+            bytes.push_back(pc.second);
+        }
+    } else {
+        uint32_t w = 0;
+        for (uint32_t k = 1; k <= ms::MAX_TILES && !w; ++k)
+            if (file_exists(std::string(path) + part_suffix(0, k))) w = k;
+        if (!w) return bad(std::string("neither ") + path + " nor " + path + ".r000ofWWW exists");
+        files.resize(w);
+        for (uint32_t r = 0; r < w; ++r) {
+            const std::string name = std::string(path) + part_suffix(r, w);
+            if (!read_whole_file(name, files[r]) || files[r].empty()) return bad("the set of part files is incomplete: cannot read " + name);
+            parts.push_back(files[r].data());
+            bytes.push_back(files[r].size());
+        }
+    }
+    return sphx_multi_state_load(m, parts.data(), bytes.data(), (uint32_t)parts.size(), 0u);
 }
 
 }  // extern "C"

@@ -250,6 +250,42 @@ class MultiSolver:
         self._chk(self.L.sphx_multi_stats_read(self.h, first, count, _p(rec) if count else None, _p(info) if count else None))
         return rec, info
 
+    # ---- checkpoint of the tiled run (the contract is in include/sphx.h, "checkpoint of a tiled run") ----
+    def save_state(self):
+        """sphx_multi_state_save -> bytes: this process's part of the checkpoint (in-process: the whole run, part 0 of 1; rank mode: part
+        rank of world).  Taken on the device from the particles the tiles own; two saves of one state are byte-identical."""
+        n = C.c_uint64()
+        self._chk(self.L.sphx_multi_state_size(self.h, C.byref(n)))
+        buf = np.zeros(n.value, np.uint8)
+        self._chk(self.L.sphx_multi_state_save(self.h, _p(buf), n.value, 0, C.byref(n)))
+        return buf[:n.value].tobytes()
+
+    def load_state(self, parts):
+        """sphx_multi_state_load: `parts` is the bytes of one part or a list of all parts of a checkpoint (any order); every rank passes
+        all of them.  The checkpoint may come from another tiling.  Replaces the particles, the boundary and the warm-start state."""
+        if isinstance(parts, (bytes, bytearray, memoryview, np.ndarray)):
+            parts = [parts]
+        arrs = [np.frombuffer(bytes(b), np.uint8) if not isinstance(b, np.ndarray) else np.ascontiguousarray(b, np.uint8) for b in parts]
+        k = len(arrs)
+        ptrs = (C.c_void_p * max(k, 1))(*[a.ctypes.data for a in arrs])
+        sizes = (C.c_uint64 * max(k, 1))(*[a.size for a in arrs])
+        self._chk(self.L.sphx_multi_state_load(self.h, ptrs, sizes, k, 0))
+
+    def state_digest(self):
+        """sphx_multi_state_digest -> {section: digest} of the whole run (_lib.MULTI_STATE_SECTIONS): id-keyed for the particle sections,
+        positional for the boundary.  64 bytes come back; collective in rank mode (every rank gets the same)."""
+        out = (C.c_uint64 * len(_lib.MULTI_STATE_SECTIONS))()
+        self._chk(self.L.sphx_multi_state_digest(self.h, out))
+        return dict(zip(_lib.MULTI_STATE_SECTIONS, (int(v) for v in out)))
+
+    def save_state_file(self, path):
+        """sphx_multi_state_save_file (rank mode: the part goes to path + ".rRRRofWWW")."""
+        self._chk(self.L.sphx_multi_state_save_file(self.h, str(path).encode()))
+
+    def load_state_file(self, path):
+        """sphx_multi_state_load_file: the one file, or the complete set of part files path.r000ofWWW ..."""
+        self._chk(self.L.sphx_multi_state_load_file(self.h, str(path).encode()))
+
     def set_tiling_invariant(self, on=True):
         """sphx_set_tiling_invariant on every local tile: cell mates ordered by persistent id (the tiles' warm-start values always travel).
         A single context and the oracle in the same mode then compute the same run, bit for bit (a comparison mode)."""
