@@ -54,6 +54,8 @@ extern "C" {
                             *    before), SPHX_VISCOSITY_*, sphx_get_viscosity
                             * 5 (additive): sphx_sample_points, sphx_sample_grid, sphx_sample_out, SPHX_SAMPLE_DEVICE_POINTERS
                             * 5 (additive): sphx_render, sphx_render_fit, sphx_render_view, sphx_render_out, SPHX_RENDER_*
+                            * 5 (additive): sphx_multi_render, sphx_multi_render_layer, sphx_render_merge, sphx_render_layer, sphx_tile_render_layer,
+                            *    sphx_tile_render_window
                             * 5 (additive): sphx_append, sphx_remove, sphx_rect, SPHX_REMOVE_*, sphx_solver_append, sphx_solver_remove
                             * 5 (additive): sphx_state_size / _save / _load / _digest / _save_file / _load_file, SPHX_STATE_*, sphx_timer_state,
                             *    sphx_timer_get_state / _set_state, sphx_solver_save / _load
@@ -257,7 +259,8 @@ int sphx_sample_grid(sphx_ctx* ctx, float x0, float y0, float dx, float dy, uint
  * When the call is allowed: wherever sphx_download is (after an upload, after a finished step of either solver; a pending advection is
  * applied first, as there); it needs no neighbour build and no densities.  Between a step_begin and its step_finish: SPHX_ERR_NOT_READY.
  * Before any upload (N = 0): the boundary over the background.  A tile context (sphx_tile_*, sphx_multi_tile_ctx) is refused with
- * SPHX_ERR_INVALID_ARGUMENT (it holds ghosts).  N <= 2^32 - 3 (two owner codes are taken).
+ * SPHX_ERR_INVALID_ARGUMENT (it holds ghosts; a tiled run is drawn by sphx_multi_render, "picture of a tiled run" below).  N <= 2^32 - 3
+ * (two owner codes are taken).
  * Argument errors (SPHX_ERR_INVALID_ARGUMENT, the message names the argument): view / out NULL, both outputs NULL, unknown flag bits,
  * pixel_per_world_unit / center / radius / min_pixel_radius / speed_scale not finite, pixel_per_world_unit <= 0, radius < 0 or
  * > smoothing_length, min_pixel_radius < 0 or > 4, width * height >= 2^28.  width * height == 0 is a successful no-op.  The two upper
@@ -838,6 +841,69 @@ int sphx_multi_simulation_step(sphx_multi* m, struct sphx_timer* timer, float pa
  * stops at the first failing step and returns its code. */
 int sphx_multi_simulation_steps(sphx_multi* m, struct sphx_timer* timer, float particle_diameter, uint32_t k, sphx_step_stats* out_stats,
                                 uint32_t* out_done);
+
+/* ---- picture of a tiled run (csrc/sphx_render.inc, csrc/sphx_render_window.hpp, csrc/sphx_render_merge.hpp, csrc/sphx_tiles.cpp) ---------------
+ * sphx_render's picture (above: pixel geometry, coverage test, disc radius, colour formula, argument errors and limits) of a run that is
+ * cut into tiles, without a sphx_multi_download: 4 bytes per pixel come back instead of 24 per particle.  The calls read only pos, vel and
+ * particle_id of the particles each tile OWNS (bit 31 of the id in the tile's arrays) and the tile's boundary particles; these are exact
+ * after every finished step whatever the ghost band has spent, so no halo exchange is made.
+ * The owner of a pixel — sphx_render's is "the highest device index among all covering fluid particles", and a tiled run has no global
+ * index.  It needs none: inside a tile the owned particles stand in the order a single context would hold them in (ascending Morton
+ * code of the cell, cell mates in their relative order); every cell belongs to exactly one tile (the tiles' rectangles partition
+ * [0, 65536)^2); so of two covering particles of different tiles the one whose cell has the greater Morton code comes later in a single
+ * context's array.  The COMPOSITE RULE:
+ *   per tile     the owner is the highest local index among the covering fluid particles the tile owns;
+ *   across tiles the owner whose cell has the greater Morton code wins: cell = position_to_mortoncellpos(x_owner)
+ *                (neighborhood_search.rs:52-58, the grid's fp32 cell function), code = morton.rs' encode of it;
+ *   fluid beats boundary, boundary beats background.
+ * A LAYER (sphx_render_layer) is one tile's — or several tiles' merged — picture at the full size of the view: per pixel `owner` = the
+ * particle ID (< 2^31; not an index: a tile's indices mean nothing outside it) of a fluid owner, SPHX_RENDER_BOUNDARY or SPHX_RENDER_NONE,
+ * `key` = the Morton code of the fluid owner's cell, else 0, and `rgba` = sphx_render's bytes for that owner (background for NONE).
+ * A tile's layer shows the fluid particles it owns and the boundary particles it holds whose cell lies in its rectangle (the tiles'
+ * clipped boundary sets contain those; together they are the whole boundary).
+ * sphx_render_merge(width, height, layers, n_layers, out): pure host code, no context, no GPU.  Folds the layers in the order given: per
+ *   pixel the class is fluid (2), boundary (1) or none (0); a later layer replaces what has accumulated only if its class is higher, or
+ *   if both are fluid and its key is STRICTLY greater (equal keys — impossible between tiles of one run — keep the earlier layer).  key,
+ *   owner and rgba travel together: no byte of a losing layer reaches the result.  Every non-NULL array of out is written; out may alias
+ *   layers[0].  SPHX_ERR_INVALID_ARGUMENT: out NULL or all three of its arrays NULL, layers NULL with n_layers > 0, a layer without key or
+ *   owner, out->rgba requested and a layer without rgba, width * height >= 2^28, n_layers == 0 with out->rgba requested (no layer supplies
+ *   the background colour; without rgba n_layers == 0 fills the picture with NONE).
+ * sphx_multi_render(m, view, flags = 0, out): the whole run's picture, out->rgba and / or out->owner (host) as sphx_render fills them but
+ *   for the owners, which are particle IDs (and the two codes).  Every local tile enqueues its layer on its own stream and device; the
+ *   layers are copied back and merged in ascending tile rank.  In-process only (sphx_multi_create): in rank mode it returns
+ *   SPHX_ERR_INVALID_ARGUMENT — there each rank takes sphx_multi_render_layer, the caller moves the layers with its own transport and
+ *   merges them with sphx_render_merge.  With one tile the picture equals sphx_render's of that particle set, ids for indices.
+ * sphx_multi_render_layer(m, view, flags = 0, out): the merged layer of the LOCAL tiles (in-process: all; rank mode: this rank's one);
+ *   any non-empty subset of out's arrays (host).  No communication: not collective, a rank may call it alone.
+ * The window: a tile clears, scatters into, resolves and copies back only the pixel rectangle its owned cells can reach (its cell
+ *   rectangle in world units grown by the disc radius and a margin, converted conservatively to pixels, clipped to the image; an edge at
+ *   cell 0 or 65536 extends to the image's edge: the saturated cells hold particles from anywhere beyond the domain).  K tiles cost about
+ *   one frame plus the seams, not K frames.
+ * When allowed: wherever sphx_multi_download is — after sphx_multi_upload and after every finished step.  SPHX_ERR_NOT_READY between
+ *   sphx_multi_step_begin and _finish, before the first sphx_multi_upload, and on a multi a failed sphx_multi_state_load left broken.
+ *   SPHX_ERR_INVALID_ARGUMENT: m / view / out NULL, out requesting nothing, any flags bit, the view errors of sphx_render (same messages),
+ *   more than 64 tiles.  width * height == 0 is a successful no-op.
+ * One tile (INTERNAL, like the other sphx_tile_* calls): sphx_tile_render_layer is accepted ONLY on a tile context (a plain one:
+ *   SPHX_ERR_INVALID_ARGUMENT; sphx_render keeps refusing a tile context), takes SPHX_RENDER_DEVICE_POINTERS like sphx_render (full-size
+ *   device arrays, enqueued, not waited for) and returns SPHX_ERR_NOT_READY between a halo exchange and the tile's re-grid.
+ *   sphx_tile_render_window is the first half of the multi's call: the tile's passes are enqueued, out_window = {x0, x1, y0, y1} (pixel
+ *   columns and rows, all zero: nothing to fetch) and out_dev = device arrays holding the WINDOW's pixels only, row after row, valid until
+ *   the context renders again; nothing is waited for.
+ * No side effects: all of this only reads (a queued run-ahead pass stays valid, the sweep direction is put back).  A run with these calls
+ *   between its steps is bit-identical to the same run without: everything sphx_multi_download returns, every sphx_step_stats field,
+ *   sphx_multi_info().exchanges.
+ * Cost: DESIGN.md section 4k. */
+typedef struct sphx_render_layer {   /* one tile's (or one rank's) picture of the particles it owns, full view size */
+    uint32_t* key;    /* [height*width]: morton(cell_of(x_owner)) for a fluid owner, else 0 */
+    uint32_t* owner;  /* [height*width]: particle id (< 2^31) of a fluid owner, SPHX_RENDER_BOUNDARY, or SPHX_RENDER_NONE */
+    uint8_t*  rgba;   /* [height*width*4] or NULL */
+} sphx_render_layer;
+int sphx_multi_render(sphx_multi* m, const sphx_render_view* view, uint32_t flags /* 0 */, const sphx_render_out* out /* host */);
+int sphx_multi_render_layer(sphx_multi* m, const sphx_render_view* view, uint32_t flags /* 0 */, const sphx_render_layer* out /* host */);
+int sphx_render_merge(uint32_t width, uint32_t height, const sphx_render_layer* layers, uint32_t n_layers, const sphx_render_layer* out);
+int sphx_tile_render_layer(sphx_ctx* tile_ctx, const sphx_render_view* view, uint32_t flags, const sphx_render_layer* out); /* INTERNAL seam */
+int sphx_tile_render_window(sphx_ctx* tile_ctx, const sphx_render_view* view, uint32_t want_rgba, uint32_t* out_window /* [4] */,
+                            sphx_render_layer* out_dev); /* INTERNAL seam */
 
 /* ---- checkpoint of a tiled run (csrc/sphx_multi_state.inc, csrc/sphx_multi_state_format.hpp, csrc/sphx_tiles.cpp) ---------------------------
  * A sphx_multi put down and picked up, without sphx_multi_download (which drops the warm-start sums that travel with the particles in tile

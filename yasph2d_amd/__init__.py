@@ -16,7 +16,7 @@ from ._lib import (FLAG_DENSITY_ITER_CAP, FLAG_DIVERGENCE_ITER_CAP, FLAG_DENSE_C
 
 __all__ = ["SphxContext", "FluidParticleWorld", "TimeManager", "DFSPHSolver", "DFSPHMultiSolver", "default_params", "duration_from_secs_f32",
            "duration_as_secs_f32", "SphxError", "WCSPHSolver", "VISCOSITY_XSPH", "VISCOSITY_PHYSICAL", "SAMPLE_FIELDS", "gauge_elevation",
-           "render_fit", "write_png", "SCENE_RECT", "TRACK_FIELDS", "FIELD_NAMES", "STATS_DTYPE", "STATS_FRAME_DTYPE"]
+           "render_fit", "render_merge", "write_png", "SCENE_RECT", "TRACK_FIELDS", "FIELD_NAMES", "STATS_DTYPE", "STATS_FRAME_DTYPE"]
 
 
 def _p(a):
@@ -156,6 +156,35 @@ def render_fit(width, height, world_rect=SCENE_RECT, **view_fields):
     if rc:
         raise SphxError(rc, "sphx_render_fit: world_rect must be finite with w, h > 0")
     return _set_view_fields(v, view_fields)
+
+
+def render_merge(layers):
+    """sphx_render_merge: the layers of MultiSolver.render_layer() (dicts of key, owner and optionally rgba, all of one view) folded in
+    the order given into one such dict — per pixel fluid over boundary over nothing, and of two fluid owners the one whose cell has the
+    greater Morton code (the composite rule of include/sphx.h, "picture of a tiled run").  rgba is merged iff every layer has it.  Pure
+    host code: needs no GPU."""
+    layers = list(layers)
+    if not layers:
+        raise ValueError("render_merge needs at least one layer (the size of the picture is the layers')")
+    h, w = np.asarray(layers[0]["owner"]).shape
+    rgba = all(l.get("rgba") is not None for l in layers)
+    keep, arr = [], (_lib.SphxRenderLayer * len(layers))()
+    for i, l in enumerate(layers):
+        k, o = np.ascontiguousarray(l["key"], np.uint32), np.ascontiguousarray(l["owner"], np.uint32)
+        c = np.ascontiguousarray(l["rgba"], np.uint8) if rgba else None
+        if k.shape != (h, w) or o.shape != (h, w) or (rgba and c.shape != (h, w, 4)):
+            raise ValueError("layer %d: key and owner must be (%d, %d), rgba (%d, %d, 4)" % (i, h, w, h, w))
+        keep.append((k, o, c))
+        arr[i] = _lib.SphxRenderLayer(k.ctypes.data or 1, o.ctypes.data or 1, (c.ctypes.data or 1) if rgba else None)
+    out = dict(key=np.zeros((h, w), np.uint32), owner=np.zeros((h, w), np.uint32))
+    if rgba:
+        out["rgba"] = np.zeros((h, w, 4), np.uint8)
+    o = _lib.SphxRenderLayer(out["key"].ctypes.data or 1, out["owner"].ctypes.data or 1, (out["rgba"].ctypes.data or 1) if rgba else None)
+    L = _lib.lib()
+    rc = L.sphx_render_merge(w, h, arr, len(layers), C.byref(o))
+    if rc:
+        raise SphxError(rc, L.sphx_multi_last_error(None).decode())
+    return out
 
 
 def _copy_view(view):
@@ -495,6 +524,31 @@ class SphxContext:
         rec = np.zeros(1 + k, STATS_DTYPE)
         self._chk(self.L.sphx_tile_fluid_stats(self.h, arr, k, 0, _p(rec)))
         return rec
+
+    def tile_render_layer(self, view=None, device=False, **view_fields):
+        """sphx_tile_render_layer (a TILE context only: MultiSolver.tile_context(k)) -> dict(key, owner, rgba): the layer of the particles
+        this tile owns and of the boundary particles of its cells, at the full size of the view (include/sphx.h, "picture of a tiled
+        run").  device=True: the arrays are torch tensors on the context's device (key and owner int32: torch has no uint32 arithmetic),
+        written through SPHX_RENDER_DEVICE_POINTERS.  A plain context is refused.  MultiSolver.render_layer() merges these."""
+        from .multi import MultiSolver
+
+        view = MultiSolver._view(view, view_fields)
+        h, w = view.height, view.width
+        if device:
+            import torch
+
+            dev = torch.device("cuda", torch.cuda.current_device())
+            out = dict(key=torch.zeros((h, w), dtype=torch.int32, device=dev), owner=torch.zeros((h, w), dtype=torch.int32, device=dev),
+                       rgba=torch.zeros((h, w, 4), dtype=torch.uint8, device=dev))
+            o = _lib.SphxRenderLayer(*[(out[k].data_ptr() or 1) for k in ("key", "owner", "rgba")])
+            torch.cuda.current_stream(dev).synchronize()
+            self._chk(self.L.sphx_tile_render_layer(self.h, C.byref(view), _lib.RENDER_DEVICE_POINTERS, C.byref(o)))
+            self.synchronize()
+            return out
+        out = dict(key=np.zeros((h, w), np.uint32), owner=np.zeros((h, w), np.uint32), rgba=np.zeros((h, w, 4), np.uint8))
+        o = _lib.SphxRenderLayer(*[(out[k].ctypes.data or 1) for k in ("key", "owner", "rgba")])
+        self._chk(self.L.sphx_tile_render_layer(self.h, C.byref(view), 0, C.byref(o)))
+        return out
 
     def track_record(self, max_frames, every=1):
         """sphx_track_record: from now on every `every`-th finished step stores {x, y, vx, vy} of the tracked ids on the device, up to
@@ -1067,6 +1121,13 @@ class DFSPHMultiSolver(DFSPHSolver):
 
     def stats_frames(self, first=0, count=None):
         return self.multi().stats_frames(first, count)
+
+    # the picture of the tiled run (MultiSolver.render / render_layer: drawn by the tiles, merged on the host; owners are particle ids)
+    def render(self, view=None, *, owner=False, rgba=True, **view_fields):
+        return self.multi().render(view, owner=owner, rgba=rgba, **view_fields)
+
+    def render_layer(self, view=None, **view_fields):
+        return self.multi().render_layer(view, **view_fields)
 
     # the tiled run put down and picked up (save / load of the base class keep refusing this solver)
     def checkpoint(self, world, time_manager, path):

@@ -103,6 +103,10 @@ class SphxRenderOut(C.Structure):
     _fields_ = [("rgba", C.c_void_p), ("owner", C.c_void_p)]
 
 
+class SphxRenderLayer(C.Structure):  # sphx_render_layer: one tile's (or rank's) picture at the full size of the view
+    _fields_ = [("key", C.c_void_p), ("owner", C.c_void_p), ("rgba", C.c_void_p)]
+
+
 REMOVE_OUTSIDE = 1  # sphx_remove flags
 REMOVE_MAX_RECTS = 8
 
@@ -251,6 +255,11 @@ SIGNATURES = {
     "sphx_sample_grid": (_i, [_vp, _f, _f, _f, _f, _u32, _u32, _i, _u32, C.POINTER(SphxSampleOut)]),
     "sphx_render_fit": (_i, [_u32, _u32, _f, _f, _f, _f, C.POINTER(SphxRenderView)]),
     "sphx_render": (_i, [_vp, C.POINTER(SphxRenderView), _u32, C.POINTER(SphxRenderOut)]),
+    "sphx_multi_render": (_i, [_vp, C.POINTER(SphxRenderView), _u32, C.POINTER(SphxRenderOut)]),
+    "sphx_multi_render_layer": (_i, [_vp, C.POINTER(SphxRenderView), _u32, C.POINTER(SphxRenderLayer)]),
+    "sphx_render_merge": (_i, [_u32, _u32, C.POINTER(SphxRenderLayer), _u32, C.POINTER(SphxRenderLayer)]),
+    "sphx_tile_render_layer": (_i, [_vp, C.POINTER(SphxRenderView), _u32, C.POINTER(SphxRenderLayer)]),
+    "sphx_tile_render_window": (_i, [_vp, C.POINTER(SphxRenderView), _u32, C.POINTER(_u32), C.POINTER(SphxRenderLayer)]),
     "sphx_clear_cached": (_i, [_vp]),
     "sphx_step_begin": (_i, [_vp, _f, C.POINTER(_f)]),
     "sphx_step_begin_law": (_i, [_vp, _f, _vp, _vp]),

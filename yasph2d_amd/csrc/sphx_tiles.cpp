@@ -41,6 +41,8 @@
 
 #include "../../include/sphx.h"
 #include "sphx_multi_state_format.hpp"
+#include "sphx_render_merge.hpp"
+#include "sphx_render_window.hpp"
 #include "sphx_stats_merge.hpp"
 
 namespace {
@@ -1026,6 +1028,36 @@ struct TileDriver {
         return SPHX_OK;
     }
 
+    // sphx_multi_render*, first half: this tile's layer goes onto its stream, into the context's render scratch — the pixels of its
+    // window only (sphx_render_window.hpp); nothing is waited for
+    uint32_t render_win[4] = {0, 0, 0, 0};  // pixel columns [0], [1]) and rows [2], [3]) of the layer in flight; all zero: nothing to fetch
+    sphx_render_layer render_dev{nullptr, nullptr, nullptr};
+    std::vector<uint32_t> render_key, render_owner, render_rgba;  // the window on the host (grown on demand)
+    int render_enqueue(const sphx_render_view* view, bool rgba) {
+        if (hipSetDevice(device) != hipSuccess) return fail(SPHX_ERR_HIP, "hipSetDevice");
+        const int rc = sphx_tile_render_window(ctx, view, rgba ? 1u : 0u, render_win, &render_dev);
+        if (rc) err = std::string("sphx_tile_render_window: ") + sphx_last_error(ctx);  // (an argument or state error of one call: nobody is waiting in an all-reduce)
+        return rc;
+    }
+    size_t render_pixels() const { return (size_t)(render_win[1] - render_win[0]) * (render_win[3] - render_win[2]); }
+    // ... second half: the window's pixels are queued for the host (render_wait() completes the copies)
+    int render_fetch(bool rgba) {
+        const size_t n = render_pixels();
+        if (!n) return SPHX_OK;
+        if (render_key.size() < n) render_key.resize(n), render_owner.resize(n);
+        if (rgba && render_rgba.size() < n) render_rgba.resize(n);
+        if (hipSetDevice(device) != hipSuccess || hipMemcpyAsync(render_key.data(), render_dev.key, n * 4, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+            hipMemcpyAsync(render_owner.data(), render_dev.owner, n * 4, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+            (rgba && hipMemcpyAsync(render_rgba.data(), render_dev.rgba, n * 4, hipMemcpyDeviceToHost, stream) != hipSuccess))
+            return fail(SPHX_ERR_HIP, "copying a layer's window back");
+        return SPHX_OK;
+    }
+    int render_wait() {
+        if (!render_pixels()) return SPHX_OK;
+        if (hipSetDevice(device) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return fail(SPHX_ERR_HIP, "waiting for a layer's window");
+        return SPHX_OK;
+    }
+
     // sphx_multi_state_*, first half: the pass over this tile's arrays goes onto its stream; nothing is waited for.  The warm-start
     // sections are canonical: zeros where the next loop will not warm-start (dfsph.rs:199 / :354)
     sphx_tile_state_out state_out{};
@@ -1970,6 +2002,113 @@ int sphx_multi_state_load_file(sphx_multi* m, const char* path) {
         }
     }
     return sphx_multi_state_load(m, parts.data(), bytes.data(), (uint32_t)parts.size(), 0u);
+}
+
+}  // extern "C"
+
+// ---- picture of the tiled run (include/sphx.h, "picture of a tiled run"; the device passes are csrc/sphx_render.inc) ---------------------------
+namespace {
+
+// The merged layer of the local tiles into acc (host, full size; acc.rgba null: no colours): every tile enqueues its window on its own
+// stream and device, then the windows are copied back and folded in ascending tile rank.  Outside its window a tile shows nothing.
+int multi_render_layers(sphx_multi* m, const char* fn, const sphx_render_view* view, const sphx_render_layer& acc) {
+    const size_t npix = (size_t)view->width * view->height;
+    const bool rgba = acc.rgba != nullptr;
+    for (size_t p = 0; p < npix; ++p) {
+        acc.key[p] = 0u;
+        acc.owner[p] = (uint32_t)SPHX_RENDER_NONE;
+        if (rgba) std::memcpy(acc.rgba + 4 * p, view->background, 4);
+    }
+    int rc;
+    for (size_t k = 0; k < m->tiles.size(); ++k)
+        if ((rc = m->tiles[k]->render_enqueue(view, rgba))) {
+            m->err = std::string(fn) + ": tile " + std::to_string(k) + ": " + m->tiles[k]->err;
+            return rc;
+        }
+    for (size_t k = 0; k < m->tiles.size(); ++k)
+        if ((rc = m->tiles[k]->render_fetch(rgba))) {
+            m->err = std::string(fn) + ": tile " + std::to_string(k) + ": " + m->tiles[k]->err;
+            return rc;
+        }
+    for (size_t k = 0; k < m->tiles.size(); ++k) {
+        TileDriver& t = *m->tiles[k];
+        if ((rc = t.render_wait())) {
+            m->err = std::string(fn) + ": tile " + std::to_string(k) + ": " + t.err;
+            return rc;
+        }
+        if (!t.render_pixels()) continue;
+        const uint32_t* w = t.render_win;
+        if (w[0] > w[1] || w[1] > view->width || w[2] > w[3] || w[3] > view->height) {  // (cannot happen: the window is clipped to the image)
+            m->err = std::string(fn) + ": tile " + std::to_string(k) + " returned a window outside the image";
+            return SPHX_ERR_HIP;
+        }
+        const sphx_render_layer src{t.render_key.data(), t.render_owner.data(), rgba ? (uint8_t*)t.render_rgba.data() : nullptr};
+        sphx_render_host::fold_window(acc, view->width, src, w[0], w[1], w[2], w[3]);
+    }
+    return SPHX_OK;
+}
+
+// the rules both calls share, in sphx_render's order: SPHX_OK go on, RENDER_NOOP a successful no-op (no pixels), else the error code
+constexpr int RENDER_NOOP = -1;  // (no status code is negative)
+int multi_render_ready(sphx_multi* m, const char* fn, const sphx_render_view* view, bool has_out, bool no_output, const char* none_msg, uint32_t flags) {
+    auto bad = [&](const std::string& what) {
+        m->err = std::string(fn) + ": " + what;
+        return SPHX_ERR_INVALID_ARGUMENT;
+    };
+    if (!view) return bad("view is NULL");
+    if (!has_out) return bad("out is NULL");
+    if (no_output) return bad(none_msg);
+    if (flags) return bad("unknown flags bits");
+    if (m->world > 64) return bad("more than 64 tiles");
+    if (const char* b = sphx::render_view_error(view, m->P.smoothing_length)) return bad(b);
+    if ((uint64_t)view->width * view->height == 0) return RENDER_NOOP;
+    return multi_state_ready(m, fn, true);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sphx_render_merge(uint32_t width, uint32_t height, const sphx_render_layer* layers, uint32_t n_layers, const sphx_render_layer* out) {
+    if (const char* b = sphx_render_host::merge_error(width, height, layers, n_layers, out)) {
+        g_multi_error = std::string("sphx_render_merge: ") + b;  // (no object to hang the message on: sphx_multi_last_error(NULL))
+        return SPHX_ERR_INVALID_ARGUMENT;
+    }
+    sphx_render_host::merge(width, height, layers, n_layers, out);
+    return SPHX_OK;
+}
+
+int sphx_multi_render_layer(sphx_multi* m, const sphx_render_view* view, uint32_t flags, const sphx_render_layer* out) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    const char* const fn = "sphx_multi_render_layer";
+    int rc;
+    if ((rc = multi_render_ready(m, fn, view, out != nullptr, out && !out->key && !out->owner && !out->rgba, "out requests no output (key, owner and rgba are NULL)", flags)))
+        return rc == RENDER_NOOP ? SPHX_OK : rc;
+    // (the fold needs keys and owners whatever the caller asks for)
+    const size_t npix = (size_t)view->width * view->height;
+    std::vector<uint32_t> key, owner;
+    if (!out->key) key.resize(npix);
+    if (!out->owner) owner.resize(npix);
+    const sphx_render_layer acc{out->key ? out->key : key.data(), out->owner ? out->owner : owner.data(), out->rgba};
+    return multi_render_layers(m, fn, view, acc);
+}
+
+int sphx_multi_render(sphx_multi* m, const sphx_render_view* view, uint32_t flags, const sphx_render_out* out) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    const char* const fn = "sphx_multi_render";
+    if (m->rank_mode) {  // (whatever the other arguments say: this process holds one tile of the run)
+        m->err = std::string(fn) + ": not available in rank mode (one tile per process): take each rank's sphx_multi_render_layer, move the layers with "
+                                   "your own transport and merge them with sphx_render_merge";
+        return SPHX_ERR_INVALID_ARGUMENT;
+    }
+    int rc;
+    if ((rc = multi_render_ready(m, fn, view, out != nullptr, out && !out->rgba && !out->owner, "out requests no output (rgba and owner are NULL)", flags)))
+        return rc == RENDER_NOOP ? SPHX_OK : rc;
+    const size_t npix = (size_t)view->width * view->height;
+    std::vector<uint32_t> key(npix), owner;
+    if (!out->owner) owner.resize(npix);
+    const sphx_render_layer acc{key.data(), out->owner ? out->owner : owner.data(), out->rgba};
+    return multi_render_layers(m, fn, view, acc);
 }
 
 }  // extern "C"

@@ -250,6 +250,46 @@ class MultiSolver:
         self._chk(self.L.sphx_multi_stats_read(self.h, first, count, _p(rec) if count else None, _p(info) if count else None))
         return rec, info
 
+    # ---- picture of the tiled run (the contract is in include/sphx.h, "picture of a tiled run") ----
+    @staticmethod
+    def _view(view, view_fields):
+        from . import SCENE_RECT, _copy_view, _set_view_fields, render_fit
+
+        if view is None:
+            width, height = view_fields.pop("width", 1920), view_fields.pop("height", 1080)
+            view = render_fit(width, height, view_fields.pop("world_rect", SCENE_RECT))
+        else:
+            view = _copy_view(view)
+        return _set_view_fields(view, view_fields)
+
+    def render(self, view=None, *, owner=False, rgba=True, **view_fields):
+        """sphx_multi_render: the whole run drawn as SphxContext.render draws a single context (host path), without a download: every
+        tile draws the particles it owns on its own device, the pictures are merged on the host.  Returns the uint8 (H, W, 4) image;
+        with owner=True the pair (image, uint32 (H, W) owners: a particle ID, _lib.RENDER_BOUNDARY or _lib.RENDER_NONE); with
+        rgba=False the owners alone.  In-process only: a rank of a multi-process run takes render_layer() and render_merge()."""
+        view = self._view(view, view_fields)
+        if not rgba and not owner:
+            raise ValueError("nothing to render: rgba and owner are both off")
+        h, w = view.height, view.width
+        img = np.zeros((h, w, 4), np.uint8) if rgba else None
+        own = np.zeros((h, w), np.uint32) if owner else None
+        o = _lib.SphxRenderOut()
+        o.rgba = (img.ctypes.data or 1) if rgba else None
+        o.owner = (own.ctypes.data or 1) if owner else None
+        self._chk(self.L.sphx_multi_render(self.h, C.byref(view), 0, C.byref(o)))
+        return own if not rgba else ((img, own) if owner else img)
+
+    def render_layer(self, view=None, **view_fields):
+        """sphx_multi_render_layer -> dict(key uint32 (H, W), owner uint32 (H, W), rgba uint8 (H, W, 4)): the merged layer of the local
+        tiles (in-process: all of them; rank mode: this rank's one).  No communication; layers of the ranks of one run are combined
+        with yasph2d_amd.render_merge."""
+        view = self._view(view, view_fields)
+        h, w = view.height, view.width
+        out = dict(key=np.zeros((h, w), np.uint32), owner=np.zeros((h, w), np.uint32), rgba=np.zeros((h, w, 4), np.uint8))
+        o = _lib.SphxRenderLayer(*[(out[k].ctypes.data or 1) for k in ("key", "owner", "rgba")])
+        self._chk(self.L.sphx_multi_render_layer(self.h, C.byref(view), 0, C.byref(o)))
+        return out
+
     # ---- checkpoint of the tiled run (the contract is in include/sphx.h, "checkpoint of a tiled run") ----
     def save_state(self):
         """sphx_multi_state_save -> bytes: this process's part of the checkpoint (in-process: the whole run, part 0 of 1; rank mode: part
