@@ -572,6 +572,10 @@ int sphx_stats_read(sphx_ctx* ctx, uint32_t first_frame, uint32_t n_frames, sphx
  * Collected only by a context created with SPHX_ZERO_SKIP_COUNT=1 in the environment (all zero otherwise); the skip itself is on by
  * default in a context of 4 M particles or more; SPHX_ZERO_SKIP=0 turns it off, =1 on at every size.  Waits for the stream. */
 int sphx_debug_correction_counts(sphx_ctx* ctx, uint64_t out[3]);
+/* Test aid for the quiet-scene exit of the same corrections, cumulative since sphx_create:
+ * out[0] = workgroups that left through the quiet exit (each of them also counts in out[0] of sphx_debug_correction_counts),
+ * out[1] = corrections the host queued in the decide-first form.  Collected only with SPHX_ZERO_SKIP_COUNT=1.  Waits for the stream. */
+int sphx_debug_quiet_counts(sphx_ctx* ctx, uint64_t out[2]);
 
 /* ---- Solver trait (solver/mod.rs:12-18) ---------------------------------------------------------------------- */
 /* Solver::clear_cached_data (dfsph.rs:406-412) */

@@ -36,16 +36,18 @@ def main():
         done += k
     ctx = solver.context()
     c0 = np.array(ctx.correction_counts(), np.int64)
+    q0 = np.array(ctx.quiet_counts(), np.int64)
     stats = solver.simulation_steps(w, timer, args.steps, sync_world=False)
     c1 = np.array(ctx.correction_counts(), np.int64)
     d = c1 - c0
+    q = np.array(ctx.quiet_counts(), np.int64) - q0  # (quiet-scene exits, corrections queued in the decide-first form)
     total = int(d.sum())
     print(json.dumps({
         "particles": len(w.positions), "skip_steps": args.skip_steps, "steps": args.steps,
         "mean_density_iterations": float(np.mean([s["density_iterations"] for s in stats])),
         "mean_divergence_iterations": float(np.mean([s["divergence_iterations"] for s in stats])),
         "correction_workgroups": total, "skipped": int(d[0]), "stopped_by_window_flag": int(d[1]), "stopped_by_remote_entry": int(d[2]),
-        "skip_share": (float(d[0]) / total) if total else None}))
+        "skip_share": (float(d[0]) / total) if total else None, "quiet_exits": int(q[0]), "decide_first_launches": int(q[1])}))
 
 
 if __name__ == "__main__":

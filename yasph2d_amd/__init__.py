@@ -629,6 +629,13 @@ class SphxContext:
         self._chk(self.L.sphx_debug_correction_counts(self.h, out))
         return int(out[0]), int(out[1]), int(out[2])
 
+    def quiet_counts(self):
+        """sphx_debug_quiet_counts -> (workgroups that left through the quiet-scene exit, corrections queued in the decide-first
+        form): cumulative, of a context created with SPHX_ZERO_SKIP_COUNT=1 in the environment (all zero otherwise)."""
+        out = (C.c_uint64 * 2)()
+        self._chk(self.L.sphx_debug_quiet_counts(self.h, out))
+        return int(out[0]), int(out[1])
+
     def grid_info(self, which=0):
         """Cell table behind the grid: covered blocks, table entries, directory extent (sphx_grid_info)."""
         out = (C.c_uint32 * 4)()

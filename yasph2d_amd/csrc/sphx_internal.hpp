@@ -178,7 +178,8 @@ struct alignas(128) Stripe {
     // zero-correction skip (k_correct), cumulative, collected only with SPHX_ZERO_SKIP_COUNT=1: workgroups that skipped
     // their walk / that a flag of their window stopped / that a flag behind an out-of-window table line stopped
     unsigned long long zs_skipped, zs_window, zs_remote;
-    uint32_t pad[14];
+    unsigned long long zs_quiet;    // ... and, of the skipped ones, those that left through the quiet-scene exit (decide-first form)
+    uint32_t pad[12];
 };
 static_assert(sizeof(Stripe) == 128, "one stripe, one cache line");
 // The max-velocity ring lives on cache lines of its own: the first density iteration READS it (velocity prediction folded into
@@ -188,6 +189,15 @@ static_assert(sizeof(Stripe) == 128, "one stripe, one cache line");
 struct alignas(128) VmaxStripe {
     uint32_t vmax[4];
     uint32_t pad[28];
+};
+// Scene-wide "some k is not +-0" mark (knz_store): the reduction sequence number (ResArgs::rseq) of the latest iteration in which a
+// wavefront of a workgroup with this stripe number stored a k other than +-0.  Never reset: a reader compares with its own number.
+// On lines of its own, for the reason VmaxStripe is: a first form kept the word in Stripe's padding, where the plain stores of a
+// disturbed scene's wavefronts met the residual atomics of the same launch — compute_density_error 198.9 -> 253.6 us and
+// compute_density_change 135.9 -> 164.5 us at 16 M, 2500 steps in (profiles/quiet_scene/ab_16M_1M.txt).
+struct alignas(128) MarkStripe {
+    uint32_t knz_mark;
+    uint32_t pad[31];
 };
 struct DevScalars {
     uint32_t flags;        // DF_*
@@ -200,6 +210,7 @@ struct DevScalars {
     uint32_t pad[18];
     Stripe stripe[STRIPES];
     VmaxStripe vstripe[STRIPES];
+    MarkStripe mstripe[STRIPES];
 };
 
 // Pinned, host-coherent memory the device publishes step scalars into (no D2H copy, no stream sync on the fast path).
@@ -207,7 +218,9 @@ struct Mailbox {
     volatile uint32_t seq;  // written last (system scope); the host waits for the value it passed to the kernel
     uint32_t flags;
     uint32_t vmax_sq_bits;  // max |v + a*dt|^2 as float bits
-    uint32_t pad;
+    // quiet-scene hint (k_correct): a correction launched with flags writes its own `seq` here when no stripe carries its
+    // iteration's mark (every k of the scene is +-0), else 0; written before seq, like err_sum.  Other corrections leave it alone.
+    uint32_t quiet_seq;
     double err_sum;         // residual sum of the last compute_error launch
     unsigned long long nb_entries;
     unsigned long long owned_cum;
@@ -370,7 +383,13 @@ struct sphx_ctx {
     // 1 M they are 2 %, and a step in which nothing can be skipped runs 3.6 % slower with the flags on — profiles/zero_skip/.)
     int zero_skip = -1;
     bool zero_skip_on() const { return zero_skip < 0 ? N >= 4000000u : zero_skip != 0; }
-    int zero_skip_count = 0;                   // SPHX_ZERO_SKIP_COUNT=1 (test aid: the three counters of Stripe)
+    int zero_skip_count = 0;                   // SPHX_ZERO_SKIP_COUNT=1 (test aid: the counters of Stripe and qf_launches)
+    // Quiet-scene hint, one per loop kind ([0] density, [1] divergence): the loop's latest terminating correction saw no mark of its
+    // iteration in any stripe.  launch_correct then queues the decide-first form of the correction.  A hint only: both forms compute
+    // the same bits for any scene.  Scratch, not state: dropped with the lists (lists_went_stale), by sphx_set_boundary and by fail().
+    bool quiet_hint[2] = {false, false};
+    uint32_t div_mark_tag = 0;                 // the reduction sequence number the fused build (div_knz_fused) left its mark under
+    unsigned long long qf_launches = 0;        // corrections queued in the decide-first form (counted with SPHX_ZERO_SKIP_COUNT=1)
     float2* accel = nullptr;                   // [N]
     float *density = nullptr, *alpha = nullptr, *alpha2 = nullptr, *kappa = nullptr, *stiff = nullptr;  // [N]
     float *kappa2 = nullptr, *stiff2 = nullptr;  // gather targets (tile mode only)
@@ -498,6 +517,7 @@ struct sphx_ctx {
     std::map<std::string, sphx::ProfTotals> prof_totals;
 
     int fail(int code, const char* what, const char* detail = nullptr) {
+        quiet_hint[0] = quiet_hint[1] = false;  // (a failed call: the next corrections decide behind the head again)
         err = what;
         if (detail) {
             err += ": ";

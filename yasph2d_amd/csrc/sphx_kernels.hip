@@ -1381,14 +1381,26 @@ struct DivArgs {
     const float* warm;  // MODE 3: warm-start stiffness, slot-bound (dfsph.rs:316-344)
     float lim;          // MODE 3: -0.5 rho0^2, dfsph.rs:356-358
     uint32_t* knz;      // MODE 2: per-wavefront "some k is not +-0" word, like k_compute_error (nullptr: not wanted)
+    uint32_t knz_tag;   // MODE 2, with knz: the reduction sequence number the loop's first iteration will get (MarkStripe::knz_mark)
 };
 __device__ __forceinline__ void block_residual_add(float e, DevScalars* __restrict__ scal);
 // The producers of kbuf[] also leave one word per wavefront: 1 when some live lane's k has a bit pattern other than +-0 (a NaN
 // counts), else 0.  A correction whose whole reach is free of flags has nothing to add to any velocity (k_correct).  Called by
 // every lane of the wavefront; dead lanes pass +0.  One ballot, one plain store by one lane.
-__device__ __forceinline__ void knz_store(uint32_t* __restrict__ knz, uint32_t i, uint32_t k_bits) {
+// Scene-wide mark: a wavefront with a flag also stores `tag` — its iteration's reduction sequence number, ResArgs::rseq — into
+// MarkStripe::knz_mark of its workgroup's stripe number (a plain store, nothing comes back, 32 addresses on lines no atomic
+// touches).  The correction of iteration `tag` knows the scene is free of factors when no stripe holds `tag`.
+// Scheme: a tag unique to the iteration, no reset.  Only producers write the word, and the stream puts no producer between an
+// iteration's producer and its correction, so a stripe that got `tag` still holds it when the correction looks.  A word can EQUAL
+// a tag by accident (left by an iteration 2^32 numbers back, or under a number handed out again after the counter was restored),
+// which only reads as "some k is set" — the side on which the correction decides per workgroup, as before.  The fused build stores
+// under the number its loop's first iteration WILL get; the host drops the flags if that iteration gets another (enqueue_iteration).
+__device__ __forceinline__ void knz_store(uint32_t* __restrict__ knz, uint32_t i, uint32_t k_bits, DevScalars* __restrict__ scal, uint32_t tag) {
     const unsigned long long nz = __ballot((k_bits << 1) != 0u);
-    if ((threadIdx.x & 63u) == 0u) knz[i >> 6] = nz ? 1u : 0u;
+    if ((threadIdx.x & 63u) == 0u) {
+        knz[i >> 6] = nz ? 1u : 0u;
+        if (nz) scal->mstripe[blockIdx.x % STRIPES].knz_mark = tag;
+    }
 }
 // LDS byte address of a __shared__ object / a 32-bit store to one: the candidate scan keeps the ADDRESS of its next list row in a
 // register and moves it by one row per accepted candidate (one add instead of a clamp, a shift-add and an index add per candidate)
@@ -1652,7 +1664,7 @@ __device__ __forceinline__ void nb_tail(const float2* __restrict__ posA, uint32_
         if (WARM) *(float2*)((char*)dv.velw + 2u * i4) = make_float2(vi.x - wsx * K.mass, vi.y - wsy * K.mass);  // dfsph.rs:342
     }
     if constexpr (DIV) {
-        if (dv.knz) knz_store(dv.knz, i, k_bits);
+        if (dv.knz) knz_store(dv.knz, i, k_bits, scal, dv.knz_tag);
     }
     // ---- list rows ----------------------------------------------------------------------------------------------------------------
     uint32_t spill_rem = 0, spill_before = 0;
@@ -2775,7 +2787,7 @@ __global__ TRAV_BOUNDS void k_compute_error(PVr PV, const float* __restrict__ de
                                                         NbView nb, float* __restrict__ kbuf, float* __restrict__ warm_zero,
                                                         DevScalars* __restrict__ scal, const float* __restrict__ dt_dev, LoopArgs la,
                                                         uint32_t* __restrict__ clear_hist, uint32_t clear_len, PredArgs pa,
-                                                        uint32_t* __restrict__ knz) {
+                                                        uint32_t* __restrict__ knz, uint32_t knz_tag) {
     // device-run loop: an iteration queued behind the one that met the residual test has nothing to do
     if (la.enabled && la.iter > 1u && scal->loop_done != 0u) return;
     if (dt_dev) dt = *dt_dev;
@@ -2872,7 +2884,7 @@ __global__ TRAV_BOUNDS void k_compute_error(PVr PV, const float* __restrict__ de
         if (warm_zero) warm_zero[i] = 0.0f;  // dfsph.rs:206-208 / 361-363 (callers whose first correction does not start from zero itself)
         e_owned = tile_owns(K, pvi.x, pvi.y) ? e : 0.0f;
     }
-    if constexpr (KNZ) knz_store(knz, i, k_bits);  // (the grid is rounded up to whole workgroups, and so is knz[])
+    if constexpr (KNZ) knz_store(knz, i, k_bits, scal, knz_tag);  // (the grid is rounded up to whole workgroups, and so is knz[])
     block_residual_add(e_owned, scal);  // read by the correction queued behind this launch (ResArgs)
 }
 
@@ -2903,13 +2915,21 @@ struct ZeroSkipArgs {
 };
 // ZS: the instantiation with the zero-correction skip's decision in it; a launch without flags runs the one without (the code from
 // before the skip, to the instruction).
-template <bool WARM, bool INV_DT, bool TILE = false, bool ZS = false>
+//
+// Quiet scene (QF, the decide-first form).  When NO particle of the scene has a k other than +-0 — no stripe holds this
+// iteration's mark, knz_store — every workgroup's reach is flag-free and nobody has to look at its own: the first wavefront reads
+// the 32 stripe words, together with the own particle's words that both paths need, and the workgroup leaves through the skip's exit
+// before a list word, a count word, a table line or a flag word has been requested.  With the mark set it goes on into the ZS path
+// below, one round trip late — so the host queues this form only while the loop's latest correction reported a quiet scene
+// (Mailbox::quiet_seq, written by the judging wavefront of every ZS launch; sphx_ctx::quiet_hint).
+template <bool WARM, bool INV_DT, bool TILE = false, bool ZS = false, bool QF = false>
 __global__ TRAV_BOUNDS void k_correct(float2* __restrict__ vel, const float2* __restrict__ posA, const float* __restrict__ kbuf,
                                                   float* __restrict__ warm, uint32_t n,
                                                   uint32_t soff, Consts K, float inv_dt, float lim, NbView nb,
                                                   const float* __restrict__ dt_dev, CountArgs ca, DevScalars* __restrict__ scal, LoopArgs la, ResArgs ra,
                                                   uint32_t first, TileClassArgs tc, ZeroSkipArgs zs) {
     static_assert(!ZS || (!WARM && !TILE), "the skip belongs to the plain corrections");
+    static_assert(!QF || ZS, "the decide-first form falls back to the skip's decision");
     float dt = WARM ? ca.dt : (la.enabled ? la.dt : ca.dt);
     if (dt_dev) {
         dt = *dt_dev;
@@ -2924,12 +2944,15 @@ __global__ TRAV_BOUNDS void k_correct(float2* __restrict__ vel, const float2* __
     const bool judge = need_verdict && threadIdx.x < 64;
     unsigned long long hi = 0, lo = 0, snap_h = 0, snap_l = 0;
     uint32_t sticky = 0;
+    uint32_t jmark = ~ra.rseq;  // ZS, the judging wavefront: the scene-wide mark of one stripe
     const uint32_t rp = ra.rseq & 1u;
     if (RES && ra.enabled) {
         // device-run loop: an iteration queued behind the one that met the residual test has nothing to do
         const uint32_t done_before = (la.enabled && la.iter > 1u) ? scal->loop_done : 0u;
         if (judge) {  // everything the verdict needs is requested here, in one round trip, ahead of the staging loads
             residual_stripe_load(scal, hi, lo);
+            if constexpr (ZS)
+                if (threadIdx.x < STRIPES) jmark = scal->mstripe[threadIdx.x].knz_mark;
             snap_h = scal->snap_hi[rp ^ 1u];
             snap_l = scal->snap_lo[rp ^ 1u];
             sticky = scal->flags;
@@ -3050,11 +3073,14 @@ __global__ TRAV_BOUNDS void k_correct(float2* __restrict__ vel, const float2* __
                 if (more && la.iter > la.max_iters) more = false;    // dfsph.rs:236 / :391
             }
         }
+        // ZS: what the host's hint for this loop's next corrections is made from (a launch without flags knows of no mark)
+        [[maybe_unused]] const bool marked = ZS ? __any(jmark == ra.rseq) != 0 : true;
         if (blockIdx.x == 0) {
             if (threadIdx.x == 0) {
                 scal->snap_hi[rp] = hi;
                 scal->snap_lo[rp] = lo;
                 ra.mb->err_sum = sum64;
+                if constexpr (ZS) ra.mb->quiet_seq = (zs.knz && !marked) ? ra.seq : 0u;
                 if (la.enabled) {
                     ra.mb->loop_hist[la.iter % LOOP_HIST] = sum64;
                     __hip_atomic_store(&scal->loop_done, more ? 0u : la.iter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -3070,6 +3096,53 @@ __global__ TRAV_BOUNDS void k_correct(float2* __restrict__ vel, const float2* __
     }
     };
     const uint32_t blk0 = xcd_bid(K.rev, K.xcd_shift);
+    // quiet scene: the mark is requested in front of everything else and looked at before the head is issued.  The scalar conditions
+    // are the skip's (zs.knz stands for K.q_noclamp, no tile, a positive finite mass: launch_correct).
+    if constexpr (QF) {
+        const uint32_t b0 = blk0 * 256u;
+        if (zs.knz && b0 < n && (!INV_DT || (inv_dt > 0.0f && inv_dt <= 3.402823466e38f))) {
+            __shared__ uint32_t quiet_s;
+            // (one wavefront reads the stripes, as the velocity prediction reads its maximum: every workgroup sees the same 32 words,
+            // nobody writes them while this launch runs, and the XCD's L2 serves them)
+            uint32_t mk = ~ra.rseq;
+            if (threadIdx.x < STRIPES) mk = scal->mstripe[threadIdx.x].knz_mark;
+            const uint32_t i = b0 + threadIdx.x, ic = min(i, n - 1u);
+            const float2 vi = INV_DT ? gat((const float2*)vel, ic) : make_float2(0.0f, 0.0f);
+            const float2 pi = INV_DT ? gat(posA, ic) : make_float2(0.0f, 0.0f);
+            // first: the sum starts from +0 and k_i is +0 or -0 — (+0) + (+0) = +0 and (+0) + (-0) = +0 in round-to-nearest, the bits
+            // 0x00000000 either way, which is what `0.0f + k_i` of the skip's exit below stores.  Neither word is read.
+            const float warm_i = first ? 0.0f : warm[ic];
+            const float ki = first ? 0.0f : kbuf[ic];
+            if (threadIdx.x < 64) {
+                const bool marked = __any(mk == ra.rseq) != 0;
+                if (threadIdx.x == 0) quiet_s = marked ? 0u : 1u;
+            }
+            __syncthreads();
+            if (quiet_s) {
+                if (zs.count && threadIdx.x == 0) {  // (a quiet exit is a skip: both counters)
+                    atomicAdd(&scal->stripe[blockIdx.x % STRIPES].zs_skipped, 1ull);
+                    atomicAdd(&scal->stripe[blockIdx.x % STRIPES].zs_quiet, 1ull);
+                }
+                verdict();
+                float2 pnew = make_float2(0.0f, 0.0f);
+                DirAhead ahead{0xFFFFFFFFu, EMPTY};
+                if (i < n) {
+                    if (INV_DT) {
+                        if (ca.hist) {
+                            uint32_t cx0, cy0;
+                            cell_of(K, pi, cx0, cy0);
+                            ahead = dir_ahead(ca.g, cx0, cy0);
+                        }
+                        pnew = make_float2(pi.x + vi.x * dt, pi.y + vi.y * dt);  // dfsph.rs:499-510, as the skip's exit below
+                    }
+                    store_cold(&warm[i], warm_i + ki, K.nt_cold);  // dfsph.rs:142 / :296
+                }
+                if (INV_DT)
+                    if (ca.hist) count_cell(K, ca.g, i < n, i, pnew, ca.hist, ca.cidx, ca.slot, 1u, scal, ahead);
+                return;
+            }
+        }
+    }
     // zero-correction skip, 1: the flag words of the wavefronts that overlap the window [lw0, lw0 + lwlen) of nb_head — contiguous, at
     // most nine — requested here (scalar loads), looked at behind the head's loads
     bool zs_try = false;

@@ -726,6 +726,7 @@ static inline void stats_after_step(sphx_ctx* c, float dt) {
 static inline void lists_went_stale(sphx_ctx* c) {
     c->K.q_noclamp = 0u;
     c->lists_current = false;
+    c->quiet_hint[0] = c->quiet_hint[1] = false;  // (another scene, for all the corrections know)
     // (a caller that has already dropped the sampling state keeps its own, more specific message)
     if (c->sample_ready) sample_went_stale(c, "the positions changed since the last neighbour build: run a step, or sphx_update_neighborhood + sphx_update_densities");
 }
@@ -971,6 +972,9 @@ int update_neighborhood(sphx_ctx* c, bool extra_alpha, float advect_dt, bool fus
             dv.kbuf = c->kbuf;
             dv.knz = zero_skip_flags(c);
             c->div_knz_fused = dv.knz != nullptr;
+            // the scene-wide mark goes under the number the divergence loop's first iteration will get when it is queued next
+            // (sphx_step_finish does that; enqueue_iteration drops the flags if something took the number in between)
+            dv.knz_tag = c->div_mark_tag = c->res_seq + 1u;
             launch(c, "neighbor_build+density_alpha+density_change", (8.0 + list_bytes(c) + 8.0 + 8.0 + 4.0) * n, [&] {
                 hipLaunchKernelGGL(k_neighbor_build<2>, dim3(nblocks(n)), dim3(256), 0, st, (const float2*)c->posA, n, c->soff(), c->K, c->gdyn.nview(),
                                    c->gstat.nview(), c->nb_list, c->nb_counts, c->nb_wave, c->nb_remote, c->density, c->alpha, c->d_scal, n_dev, dv);
@@ -1094,7 +1098,7 @@ void launch_predict(sphx_ctx* c, const char* label, float dt, const VmaxArgs& va
 // prediction on the way, from accel[] into vel2[].  clear_hist: the cell count the previous iteration's correction left, wiped on the
 // way.  (No warm_zero array: the zeroing of dfsph.rs:206-208 / :361-363 is implicit, the first correction starts the sum from zero.)
 void launch_compute_error(sphx_ctx* c, bool divergence, float dt, const float* dt_dev, const LoopArgs& la, uint32_t* clear_hist, uint32_t clear_len,
-                          const PredArgs* pred, uint32_t* knz) {
+                          const PredArgs* pred, uint32_t* knz, uint32_t knz_tag) {
     const uint32_t n = c->N;
     hipStream_t st = c->stream;
     const dim3 g(nblocks(n)), b(256);
@@ -1103,10 +1107,10 @@ void launch_compute_error(sphx_ctx* c, bool divergence, float dt, const float* d
         launch(c, "compute_density_change", (16 + 4 + 4 + lb) * n, [&] {
             if (knz)
                 hipLaunchKernelGGL((k_compute_error<true, false, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt, c->nbv(),
-                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz);
+                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz, knz_tag);
             else
                 hipLaunchKernelGGL((k_compute_error<true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt, c->nbv(),
-                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz);
+                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz, knz_tag);
         });
     } else if (pred) {
         PredArgs pa = *pred;
@@ -1115,19 +1119,19 @@ void launch_compute_error(sphx_ctx* c, bool divergence, float dt, const float* d
         launch(c, "velocity_prediction+compute_density_error", (16 + 8 + 8 + 4 + 4 + 4 + lb) * n, [&] {
             if (knz)
                 hipLaunchKernelGGL((k_compute_error<false, true, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt,
-                                   c->nbv(), c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, pa, knz);
+                                   c->nbv(), c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, pa, knz, knz_tag);
             else
                 hipLaunchKernelGGL((k_compute_error<false, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt,
-                                   c->nbv(), c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, pa, knz);
+                                   c->nbv(), c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, pa, knz, knz_tag);
         });
     } else {
         launch(c, "compute_density_error", (16 + 4 + 4 + 4 + lb) * n + (clear_hist ? 4.0 * clear_len : 0.0), [&] {
             if (knz)
                 hipLaunchKernelGGL((k_compute_error<false, false, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt, c->nbv(),
-                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz);
+                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz, knz_tag);
             else
                 hipLaunchKernelGGL((k_compute_error<false>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt, c->nbv(),
-                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz);
+                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz, knz_tag);
         });
     }
 }
@@ -1146,10 +1150,20 @@ void launch_correct(sphx_ctx* c, bool divergence, float dt, const float* dt_dev,
     const bool skip_ok = knz && c->K.q_noclamp && !tc.pid && std::isfinite(c->K.mass) && c->K.mass > 0.0f &&
                          (dt_dev || divergence || (inv_dt > 0.0f && std::isfinite(inv_dt)));
     const ZeroSkipArgs zs{skip_ok ? knz : nullptr, c->zero_skip_count ? 1u : 0u};
+    // The decide-first form (quiet scene) only while this loop's latest correction saw no mark: a workgroup that walks pays a round
+    // trip for looking first.  A hint — either form computes the same bits whatever the scene is.
+    const bool quiet_first = zs.knz && c->quiet_hint[divergence ? 1 : 0];
+    if (quiet_first && c->zero_skip_count) c->qf_launches += 1;
     launch(c, divergence ? "correct_velocity_with_divergence_error" : "correct_velocity_with_density_error",
            (16 + 8 + 12 + 8 + list_bytes(c) + (ca.hist ? (tc.pid ? 8 + 4 : 8) : 0)) * n, [&] {
                // (a launch without flags runs the instantiation without the skip's decision: the code from before it)
-               if (divergence && zs.knz)
+               if (divergence && quiet_first)
+                   hipLaunchKernelGGL((k_correct<false, false, false, true, true>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(),
+                                      c->K, inv_dt, lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, f, tc, zs);
+               else if (quiet_first)
+                   hipLaunchKernelGGL((k_correct<false, true, false, true, true>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(),
+                                      c->K, inv_dt, lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, f, tc, zs);
+               else if (divergence && zs.knz)
                    hipLaunchKernelGGL((k_correct<false, false, false, true>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K,
                                       inv_dt, lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, f, tc, zs);
                else if (divergence)
@@ -1221,9 +1235,9 @@ uint32_t enqueue_iteration(sphx_ctx* c, const IterSpec& s) {
     uint32_t* knz = s.tc.pid ? nullptr : zero_skip_flags(c);
     if (s.divergence && s.first && c->div_error_fused) {  // the neighbour build has left this iteration's errors, residual and zeroed warm-start values
         c->div_error_fused = false;
-        if (!c->div_knz_fused) knz = nullptr;
+        if (!c->div_knz_fused || c->div_mark_tag != ra.rseq) knz = nullptr;  // (a mark under another number says nothing about this one)
     } else
-        launch_compute_error(c, s.divergence, s.dt, s.dt_dev, s.la, s.clear_hist, s.clear_len, s.pred, knz);
+        launch_compute_error(c, s.divergence, s.dt, s.dt_dev, s.la, s.clear_hist, s.clear_len, s.pred, knz, ra.rseq);
     if (s.pred) std::swap(c->vel, c->vel2);  // the predicted velocities are the velocities from here on (the boundary tail is zero in both)
     if (s.drop_count) drop_fused_count(c);
     if (s.ca.hist) {
@@ -1400,6 +1414,8 @@ int solver_loop(sphx_ctx* c, bool divergence, float dt, uint32_t* out_iters, flo
         iters = c->mbox->loop_iters;
         // the terminating iteration's publish (flags, counters) is complete once ITS seq has arrived
         if ((rc = wait_mailbox(c, seq1 + iters - 1))) return rc;
+        // the hint for this loop's next corrections: the terminating one (launched with flags) saw no mark of its iteration
+        c->quiet_hint[divergence ? 1 : 0] = c->mbox->quiet_seq == seq1 + iters - 1;
         // Verify every decision the device took, bit for bit, from the residual sums it left in the mailbox.
         const uint32_t first = iters > LOOP_HIST - 1 ? iters - (LOOP_HIST - 1) : 1;
         for (uint32_t k = first; k <= iters; ++k) {
@@ -1420,7 +1436,10 @@ int solver_loop(sphx_ctx* c, bool divergence, float dt, uint32_t* out_iters, flo
             if ((rc = wait_mailbox(c, seq))) return rc;
             bool more;
             if ((rc = judge_residual(c, divergence, c->mbox->err_sum, iters, dt, &avg, &more, io_flags))) return rc;
-            if (!more) break;
+            if (!more) {
+                c->quiet_hint[divergence ? 1 : 0] = c->mbox->quiet_seq == seq;
+                break;
+            }
             seq = enqueue_context_iteration(c, divergence, dt, nullptr, iters + 1, 0, out_warm);
         }
     }
@@ -1479,6 +1498,18 @@ int sphx_debug_correction_counts(sphx_ctx* c, uint64_t out[3]) {
         out[1] += s.zs_window;
         out[2] += s.zs_remote;
     }
+    return SPHX_OK;
+}
+
+int sphx_debug_quiet_counts(sphx_ctx* c, uint64_t out[2]) {
+    if (!c || !out) return SPHX_ERR_INVALID_ARGUMENT;
+    SPHX_HIP(c, hipSetDevice(c->device));
+    SPHX_HIP(c, hipStreamSynchronize(c->stream));
+    std::vector<Stripe> st(STRIPES);
+    SPHX_HIP(c, hipMemcpy(st.data(), c->d_scal->stripe, sizeof(Stripe) * STRIPES, hipMemcpyDeviceToHost));
+    out[0] = 0;
+    for (const Stripe& s : st) out[0] += s.zs_quiet;
+    out[1] = c->qf_launches;
     return SPHX_OK;
 }
 
@@ -1706,6 +1737,7 @@ int sphx_set_boundary(sphx_ctx* c, const float* xy, uint32_t n) {
         SPHX_HIP(c, hipStreamSynchronize(c->stream));
     }
     c->h_boundary.assign(xy, xy + 2 * (size_t)n);
+    c->quiet_hint[0] = c->quiet_hint[1] = false;
     c->boundary_changed = true;  // fluidparticleworld.rs:194 (the static grid is rebuilt lazily, :247-252)
     return ensure_index_scratch(c);
 }
