@@ -576,6 +576,16 @@ int sphx_debug_correction_counts(sphx_ctx* ctx, uint64_t out[3]);
  * out[0] = workgroups that left through the quiet exit (each of them also counts in out[0] of sphx_debug_correction_counts),
  * out[1] = corrections the host queued in the decide-first form.  Collected only with SPHX_ZERO_SKIP_COUNT=1.  Waits for the stream. */
 int sphx_debug_quiet_counts(sphx_ctx* ctx, uint64_t out[2]);
+/* Test aid for the quiet take-over, cumulative since sphx_create:
+ * out[0] = corrections queued in the thin form (counted by the host on every context);
+ * out[1] = producers that took over — a neighbour build or compute_density_change that also stored the warm-start sums, a
+ *          compute_density_error that also made the cell count.  Counted when the producer is queued: a build whose correction
+ *          later runs the full form after all (its mark's number was taken by another iteration) is counted too;
+ * out[2] = particles whose cell the recount of a marked thin density correction moved (collected only with SPHX_ZERO_SKIP_COUNT=1).
+ * Waits for the stream.  Switches, read by sphx_create: SPHX_QUIET_TAKEOVER=0 (never) / 1 (default: under a loop's quiet hint,
+ * wherever flags exist) / force (every first iteration with flags), SPHX_QUIET_TAKEOVER_DENSITY=0 (the divergence loop only),
+ * SPHX_THIN_GRID=n (workgroups of a thin launch; default 2 048). */
+int sphx_debug_takeover_counts(sphx_ctx* ctx, uint64_t out[3]);
 
 /* ---- Solver trait (solver/mod.rs:12-18) ---------------------------------------------------------------------- */
 /* Solver::clear_cached_data (dfsph.rs:406-412) */

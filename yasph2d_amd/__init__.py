@@ -636,6 +636,13 @@ class SphxContext:
         self._chk(self.L.sphx_debug_quiet_counts(self.h, out))
         return int(out[0]), int(out[1])
 
+    def takeover_counts(self):
+        """sphx_debug_takeover_counts -> (corrections queued in the thin form, producers that also stored the warm-start sums,
+        particles whose cell a recount moved — always 0): cumulative since the context was created."""
+        out = (C.c_uint64 * 3)()
+        self._chk(self.L.sphx_debug_takeover_counts(self.h, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
     def grid_info(self, which=0):
         """Cell table behind the grid: covered blocks, table entries, directory extent (sphx_grid_info)."""
         out = (C.c_uint32 * 4)()

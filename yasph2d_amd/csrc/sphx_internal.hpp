@@ -199,6 +199,16 @@ struct alignas(128) MarkStripe {
     uint32_t knz_mark;
     uint32_t pad[31];
 };
+// Quiet take-over of the density loop: the cell count compute_density_error makes ahead of its correction is
+// speculative — right iff the correction turns out to be the identity — and so are the DF_* flags that count raises.  They wait
+// here, on a line no residual, mark or sticky flag shares, until the thin correction merges them into DevScalars::flags (quiet) or
+// drops them (marked: its recount raises the real ones).  moved: particles whose cell a recount changed (SPHX_ZERO_SKIP_COUNT=1).
+struct alignas(128) SpecLine {
+    uint32_t flags;
+    uint32_t pad0;
+    unsigned long long moved;
+    uint32_t pad[28];
+};
 struct DevScalars {
     uint32_t flags;        // DF_*
     uint32_t ticket;       // second-level arrival counter (one arrival per stripe); reset by the last arriver
@@ -211,6 +221,7 @@ struct DevScalars {
     Stripe stripe[STRIPES];
     VmaxStripe vstripe[STRIPES];
     MarkStripe mstripe[STRIPES];
+    SpecLine spec;
 };
 
 // Pinned, host-coherent memory the device publishes step scalars into (no D2H copy, no stream sync on the fast path).
@@ -390,6 +401,18 @@ struct sphx_ctx {
     bool quiet_hint[2] = {false, false};
     uint32_t div_mark_tag = 0;                 // the reduction sequence number the fused build (div_knz_fused) left its mark under
     unsigned long long qf_launches = 0;        // corrections queued in the decide-first form (counted with SPHX_ZERO_SKIP_COUNT=1)
+    // Quiet take-over: under a loop's quiet hint the producer of the first iteration's k also stores the warm-start
+    // sums (0 + k) — and, in the density loop, makes the next build's cell count, speculatively — and the correction is queued in the
+    // thin form (k_correct_thin).  SPHX_QUIET_TAKEOVER=0: never (the A/B switch); 1: wherever flags exist (default); force = 2:
+    // whatever the hint says (test aid — either form computes the same bits).
+    int quiet_takeover = 1;
+    uint32_t thin_grid = 0;                    // SPHX_THIN_GRID=n (test aid): workgroups of a thin launch; 0: one resident generation
+    bool div_warm_taken = false;               // the neighbour build that left the flags (div_knz_fused) stored the warm-start sums too
+    int quiet_takeover_density = 1;            // SPHX_QUIET_TAKEOVER_DENSITY=0: the density loop keeps the parent's launches (per-part A/B)
+    bool take_over(bool divergence) const {
+        return !tile_mode && (divergence || quiet_takeover_density) && (quiet_takeover == 2 || (quiet_takeover == 1 && quiet_hint[divergence ? 1 : 0]));
+    }
+    unsigned long long thin_launches = 0, takeover_producers = 0;  // sphx_debug_takeover_counts
     float2* accel = nullptr;                   // [N]
     float *density = nullptr, *alpha = nullptr, *alpha2 = nullptr, *kappa = nullptr, *stiff = nullptr;  // [N]
     float *kappa2 = nullptr, *stiff2 = nullptr;  // gather targets (tile mode only)

@@ -102,8 +102,9 @@ constexpr uint32_t NT_COLD_FROM = 6000000u;
 // 32 ... 128 blocks are within noise of each other, 512 costs 0.3-0.8 %, 2 048 gives half the late windows' gain back.
 inline uint32_t xcd_shift_of(const sphx_ctx* c) { return c->xcd_chunk >= 0 ? xcd_shift_clamp(c->xcd_chunk) : 7u; }
 // Launch wrapper: `bytes` = algorithmic HBM bytes of this launch (DESIGN.md §4), used for the roofline line of bench.py.
+// sweeps = false: a launch that touches no particle in the expected case (the thin correction) leaves the direction alone, like the scan.
 template <class F>
-inline void launch(sphx_ctx* c, const char* name, double bytes, F&& f) {
+inline void launch(sphx_ctx* c, const char* name, double bytes, F&& f, bool sweeps = true) {
     Roctx& rx = roctx();
     if (rx.push) rx.push(name);
     struct Pop {
@@ -115,7 +116,7 @@ inline void launch(sphx_ctx* c, const char* name, double bytes, F&& f) {
     // (xcd_bid: every sweep over the particles starts where its predecessor stopped.  Not the scan — it runs over the cell table — and
     // not the scatter: between the density correction and the gather the scan and the scatter stream ~260 MB, a cache's worth; with the
     // scatter keeping the correction's direction the GATHER turns round against both: -0.4 % per step over toggling at every launch)
-    if (c->alternate_sweep && std::strcmp(name, "cell_scan") != 0 && !(c->alternate_sweep != 2 && std::strcmp(name, "cell_scatter") == 0)) c->K.rev ^= 1u;
+    if (sweeps && c->alternate_sweep && std::strcmp(name, "cell_scan") != 0 && !(c->alternate_sweep != 2 && std::strcmp(name, "cell_scatter") == 0)) c->K.rev ^= 1u;
     c->K.xcd_shift = xcd_shift_of(c);
     c->K.nt_cold = c->nt_cold_stores < 0 ? (c->N >= NT_COLD_FROM ? 1u : 0u) : (uint32_t)c->nt_cold_stores;
     if (c->profiling && (c->prof_filter.empty() || (c->prof_filter == name && (c->prof_counter++ % c->prof_every) == 0))) {
@@ -727,6 +728,7 @@ static inline void lists_went_stale(sphx_ctx* c) {
     c->K.q_noclamp = 0u;
     c->lists_current = false;
     c->quiet_hint[0] = c->quiet_hint[1] = false;  // (another scene, for all the corrections know)
+    if (c->d_scal) hipMemsetAsync(&c->d_scal->spec.flags, 0, sizeof(uint32_t), c->stream);  // (... and no speculative flag of the old one)
     // (a caller that has already dropped the sampling state keeps its own, more specific message)
     if (c->sample_ready) sample_went_stale(c, "the positions changed since the last neighbour build: run a step, or sphx_update_neighborhood + sphx_update_densities");
 }
@@ -956,6 +958,7 @@ int update_neighborhood(sphx_ctx* c, bool extra_alpha, float advect_dt, bool fus
         c->div_error_fused = false;
         c->div_warm_fused = false;
         c->div_knz_fused = false;
+        c->div_warm_taken = false;
         if (fuse && fuse_warm) {
             DivArgs dv{};
             dv.velw = c->vel;
@@ -975,9 +978,20 @@ int update_neighborhood(sphx_ctx* c, bool extra_alpha, float advect_dt, bool fus
             // the scene-wide mark goes under the number the divergence loop's first iteration will get when it is queued next
             // (sphx_step_finish does that; enqueue_iteration drops the flags if something took the number in between)
             dv.knz_tag = c->div_mark_tag = c->res_seq + 1u;
+            // take-over: the loop's first correction stores 0 + k into the stiffness whatever path it takes, and nothing reads the
+            // array between this build and that correction — under the quiet hint the build stores it, and the correction can be thin
+            if (dv.knz && c->take_over(true)) {
+                dv.warm = c->stiff;
+                c->div_warm_taken = true;
+                c->takeover_producers += 1;
+            }
             launch(c, "neighbor_build+density_alpha+density_change", (8.0 + list_bytes(c) + 8.0 + 8.0 + 4.0) * n, [&] {
-                hipLaunchKernelGGL(k_neighbor_build<2>, dim3(nblocks(n)), dim3(256), 0, st, (const float2*)c->posA, n, c->soff(), c->K, c->gdyn.nview(),
-                                   c->gstat.nview(), c->nb_list, c->nb_counts, c->nb_wave, c->nb_remote, c->density, c->alpha, c->d_scal, n_dev, dv);
+                if (c->div_warm_taken)
+                    hipLaunchKernelGGL((k_neighbor_build<2, true>), dim3(nblocks(n)), dim3(256), 0, st, (const float2*)c->posA, n, c->soff(), c->K, c->gdyn.nview(),
+                                       c->gstat.nview(), c->nb_list, c->nb_counts, c->nb_wave, c->nb_remote, c->density, c->alpha, c->d_scal, n_dev, dv);
+                else
+                    hipLaunchKernelGGL(k_neighbor_build<2>, dim3(nblocks(n)), dim3(256), 0, st, (const float2*)c->posA, n, c->soff(), c->K, c->gdyn.nview(),
+                                       c->gstat.nview(), c->nb_list, c->nb_counts, c->nb_wave, c->nb_remote, c->density, c->alpha, c->d_scal, n_dev, dv);
             });
             c->div_error_fused = true;
         } else if (fuse)
@@ -1098,40 +1112,50 @@ void launch_predict(sphx_ctx* c, const char* label, float dt, const VmaxArgs& va
 // prediction on the way, from accel[] into vel2[].  clear_hist: the cell count the previous iteration's correction left, wiped on the
 // way.  (No warm_zero array: the zeroing of dfsph.rs:206-208 / :361-363 is implicit, the first correction starts the sum from zero.)
 void launch_compute_error(sphx_ctx* c, bool divergence, float dt, const float* dt_dev, const LoopArgs& la, uint32_t* clear_hist, uint32_t clear_len,
-                          const PredArgs* pred, uint32_t* knz, uint32_t knz_tag) {
+                          const PredArgs* pred, uint32_t* knz, uint32_t knz_tag, bool take_warm = false,
+                          const CountArgs& take_count = CountArgs{}) {
     const uint32_t n = c->N;
     hipStream_t st = c->stream;
     const dim3 g(nblocks(n)), b(256);
     const double lb = list_bytes(c);
     if (divergence) {
         launch(c, "compute_density_change", (16 + 4 + 4 + lb) * n, [&] {
-            if (knz)
+            if (knz && take_warm)  // (take-over: the warm-start sums 0 + k go out with k)
+                hipLaunchKernelGGL((k_compute_error<true, false, true, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt,
+                                   c->nbv(), c->kbuf, c->stiff, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz, knz_tag, NoTake{});
+            else if (knz)
                 hipLaunchKernelGGL((k_compute_error<true, false, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt, c->nbv(),
-                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz, knz_tag);
+                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz, knz_tag, NoTake{});
             else
                 hipLaunchKernelGGL((k_compute_error<true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt, c->nbv(),
-                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz, knz_tag);
+                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz, knz_tag, NoTake{});
         });
     } else if (pred) {
         PredArgs pa = *pred;
         pa.accel = c->accel;
         pa.vel_out = c->vel2;
         launch(c, "velocity_prediction+compute_density_error", (16 + 8 + 8 + 4 + 4 + 4 + lb) * n, [&] {
-            if (knz)
+            if (knz && take_warm)  // (take-over: kappa = 0 + k and the speculative cell count go out with k)
+                hipLaunchKernelGGL((k_compute_error<false, true, true, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt,
+                                   c->nbv(), c->kbuf, c->kappa, c->d_scal, dt_dev, la, clear_hist, clear_len, pa, knz, knz_tag, take_count);
+            else if (knz)
                 hipLaunchKernelGGL((k_compute_error<false, true, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt,
-                                   c->nbv(), c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, pa, knz, knz_tag);
+                                   c->nbv(), c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, pa, knz, knz_tag, NoTake{});
             else
                 hipLaunchKernelGGL((k_compute_error<false, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt,
-                                   c->nbv(), c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, pa, knz, knz_tag);
+                                   c->nbv(), c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, pa, knz, knz_tag, NoTake{});
         });
     } else {
         launch(c, "compute_density_error", (16 + 4 + 4 + 4 + lb) * n + (clear_hist ? 4.0 * clear_len : 0.0), [&] {
-            if (knz)
+            if (knz && take_warm)
+                hipLaunchKernelGGL((k_compute_error<false, false, true, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt,
+                                   c->nbv(), c->kbuf, c->kappa, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz, knz_tag, take_count);
+            else if (knz)
                 hipLaunchKernelGGL((k_compute_error<false, false, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt, c->nbv(),
-                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz, knz_tag);
+                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz, knz_tag, NoTake{});
             else
                 hipLaunchKernelGGL((k_compute_error<false>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt, c->nbv(),
-                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz, knz_tag);
+                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz, knz_tag, NoTake{});
         });
     }
 }
@@ -1139,21 +1163,48 @@ void launch_compute_error(sphx_ctx* c, bool divergence, float dt, const float* d
 // correct_velocity_with_{density,divergence}_error (dfsph.rs:218 / :373).  ca.hist: the density correction also makes the next build's
 // cell count (+8 B per particle); tc.pid: and the tile's send classification (+4 B).
 // knz: the flags this iteration's producer wrote (nullptr: none) — handed to the kernel only where a skipped walk is an exact identity.
+// (q_noclamp: the lists were built from these positions, every grad W is finite; a dt the device derives is tested by the kernel)
+inline bool correct_skip_ok(const sphx_ctx* c, bool divergence, float dt, const float* dt_dev, const TileClassArgs& tc, const uint32_t* knz) {
+    const float inv_dt = 1.0f / dt;
+    return knz && c->K.q_noclamp && !tc.pid && std::isfinite(c->K.mass) && c->K.mass > 0.0f && (dt_dev || divergence || (inv_dt > 0.0f && std::isfinite(inv_dt)));
+}
 void launch_correct(sphx_ctx* c, bool divergence, float dt, const float* dt_dev, const CountArgs& ca, const LoopArgs& la, const ResArgs& ra, bool first,
-                    const TileClassArgs& tc, const uint32_t* knz) {
+                    const TileClassArgs& tc, const uint32_t* knz, bool warm_taken = false) {
     const uint32_t n = c->N, f = first ? 1u : 0u;
     hipStream_t st = c->stream;
     const dim3 g(nblocks(n)), b(256);
     const float inv_dt = 1.0f / dt, lim = -0.5f * c->K.rho0 * c->K.rho0;
     float* warm = divergence ? c->stiff : c->kappa;
-    // (q_noclamp: the lists were built from these positions, every grad W is finite; a dt the device derives is tested by the kernel)
-    const bool skip_ok = knz && c->K.q_noclamp && !tc.pid && std::isfinite(c->K.mass) && c->K.mass > 0.0f &&
-                         (dt_dev || divergence || (inv_dt > 0.0f && std::isfinite(inv_dt)));
+    const bool skip_ok = correct_skip_ok(c, divergence, dt, dt_dev, tc, knz);
     const ZeroSkipArgs zs{skip_ok ? knz : nullptr, c->zero_skip_count ? 1u : 0u};
     // The decide-first form (quiet scene) only while this loop's latest correction saw no mark: a workgroup that walks pays a round
     // trip for looking first.  A hint — either form computes the same bits whatever the scene is.
     const bool quiet_first = zs.knz && c->quiet_hint[divergence ? 1 : 0];
-    if (quiet_first && c->zero_skip_count) c->qf_launches += 1;
+    // The thin form (take-over): a first correction whose producer has stored the warm-start sums.  2 048 workgroups (k_correct's
+    // resident generation, 8 per CU x 256 CUs) stand for the whole grid; a quiet scene costs them one look at the marks.  256 ... 4 096
+    // measure alike, 16 384 is slower (profiles/quiet_takeover/ab_16M_1M.txt).
+    // (density loop: the producer has also made the cell count, speculatively — enqueue_iteration takes over only where this launch
+    // will be thin, so that every speculative count meets the kernel that confirms or corrects it)
+    const bool thin = first && warm_taken && zs.knz && (divergence || ca.hist);
+    if ((quiet_first || thin) && c->zero_skip_count) c->qf_launches += 1;
+    if (thin) {
+        c->thin_launches += 1;
+        const uint32_t vblocks = nblocks(n);
+        const dim3 tg(std::min(vblocks, c->thin_grid ? c->thin_grid : 2048u));
+        launch(
+            c, divergence ? "correct_velocity_with_divergence_error" : "correct_velocity_with_density_error",
+            (16 + 8 + 12 + 8 + list_bytes(c) + (ca.hist ? 8 : 0)) * n,
+            [&] {
+                if (divergence)
+                    hipLaunchKernelGGL((k_correct_thin<false>), tg, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K,
+                                       inv_dt, lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, zs, vblocks);
+                else
+                    hipLaunchKernelGGL((k_correct_thin<true>), tg, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K,
+                                       inv_dt, lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, zs, vblocks);
+            },
+            false);
+        return;
+    }
     launch(c, divergence ? "correct_velocity_with_divergence_error" : "correct_velocity_with_density_error",
            (16 + 8 + 12 + 8 + list_bytes(c) + (ca.hist ? (tc.pid ? 8 + 4 : 8) : 0)) * n, [&] {
                // (a launch without flags runs the instantiation without the skip's decision: the code from before it)
@@ -1233,18 +1284,27 @@ uint32_t enqueue_iteration(sphx_ctx* c, const IterSpec& s) {
     const ResArgs ra{1u, ++c->res_seq, c->mbox_dev, seq};  // the correction reads (and publishes) the residual its compute_error leaves
     // the flags the correction may trust: the ones the producer of THIS iteration's kbuf wrote
     uint32_t* knz = s.tc.pid ? nullptr : zero_skip_flags(c);
+    bool warm_taken = false;  // take-over: this iteration's producer has stored the warm-start sums its correction would store
     if (s.divergence && s.first && c->div_error_fused) {  // the neighbour build has left this iteration's errors, residual and zeroed warm-start values
         c->div_error_fused = false;
         if (!c->div_knz_fused || c->div_mark_tag != ra.rseq) knz = nullptr;  // (a mark under another number says nothing about this one)
-    } else
-        launch_compute_error(c, s.divergence, s.dt, s.dt_dev, s.la, s.clear_hist, s.clear_len, s.pred, knz, ra.rseq);
+        warm_taken = knz && c->div_warm_taken;
+    } else {
+        // (a count an earlier correction left is dropped in FRONT of this compute_error: under the take-over it makes the new one)
+        if (s.drop_count) drop_fused_count(c);
+        // density loop: only with the count to make, and only where the correction will be thin (launch_correct's conditions)
+        warm_taken = s.first && knz && c->take_over(s.divergence) && (s.divergence || (s.ca.hist && correct_skip_ok(c, false, s.dt, s.dt_dev, s.tc, knz)));
+        if (warm_taken) c->takeover_producers += 1;
+        launch_compute_error(c, s.divergence, s.dt, s.dt_dev, s.la, s.clear_hist, s.clear_len, s.pred, knz, ra.rseq, warm_taken, s.ca);
+    }
+    c->div_warm_taken = false;
     if (s.pred) std::swap(c->vel, c->vel2);  // the predicted velocities are the velocities from here on (the boundary tail is zero in both)
-    if (s.drop_count) drop_fused_count(c);
+    if (s.drop_count) drop_fused_count(c);  // (the fused-build path; a no-op behind the one above)
     if (s.ca.hist) {
         c->count_done = true;
         c->count_n = c->N;
     }
-    launch_correct(c, s.divergence, s.dt, s.dt_dev, s.ca, s.la, ra, s.first, s.tc, knz);
+    launch_correct(c, s.divergence, s.dt, s.dt_dev, s.ca, s.la, ra, s.first, s.tc, knz, warm_taken);
     return seq;
 }
 
@@ -1501,6 +1561,18 @@ int sphx_debug_correction_counts(sphx_ctx* c, uint64_t out[3]) {
     return SPHX_OK;
 }
 
+int sphx_debug_takeover_counts(sphx_ctx* c, uint64_t out[3]) {
+    if (!c || !out) return SPHX_ERR_INVALID_ARGUMENT;
+    out[0] = c->thin_launches;
+    out[1] = c->takeover_producers;
+    SPHX_HIP(c, hipSetDevice(c->device));
+    SPHX_HIP(c, hipStreamSynchronize(c->stream));
+    unsigned long long moved = 0;
+    SPHX_HIP(c, hipMemcpy(&moved, &c->d_scal->spec.moved, sizeof(moved), hipMemcpyDeviceToHost));
+    out[2] = moved;
+    return SPHX_OK;
+}
+
 int sphx_debug_quiet_counts(sphx_ctx* c, uint64_t out[2]) {
     if (!c || !out) return SPHX_ERR_INVALID_ARGUMENT;
     SPHX_HIP(c, hipSetDevice(c->device));
@@ -1549,6 +1621,9 @@ int sphx_create(const sphx_params* params, sphx_ctx** out) {
     if (const char* e = std::getenv("SPHX_ALTERNATE_SWEEP")) c->alternate_sweep = e[0] == '2' ? 2 : (e[0] != '0');  // (0: every launch bottom-up; 2: the scatter toggles too — A/B forms)
     if (const char* e = std::getenv("SPHX_ZERO_SKIP")) c->zero_skip = e[0] != '0';  // (0: no correction skips its walk, no flags are written; 1: also below 4 M particles)
     if (const char* e = std::getenv("SPHX_ZERO_SKIP_COUNT")) c->zero_skip_count = e[0] == '1';  // (test aid: sphx_debug_correction_counts)
+    if (const char* e = std::getenv("SPHX_QUIET_TAKEOVER")) c->quiet_takeover = std::strcmp(e, "force") == 0 ? 2 : (e[0] != '0' ? 1 : 0);  // (0: the A/B switch)
+    if (const char* e = std::getenv("SPHX_QUIET_TAKEOVER_DENSITY")) c->quiet_takeover_density = e[0] != '0';  // (0: divergence loop only — the per-part A/B)
+    if (const char* e = std::getenv("SPHX_THIN_GRID")) c->thin_grid = (uint32_t)std::max(0, std::atoi(e));  // (test aid: small scenes run the block loop)
     if (const char* e = std::getenv("SPHX_FUSE_WARM")) c->fuse_warm = e[0] != '0';  // (A/B: the divergence warm start as a walk of its own behind k_neighbor_build<1>)
     c->P = *params;
     c->device = params->device;
