@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/sphx.h"
+#include "sphx_handoff.hpp"
 
 namespace sphx {
 
@@ -389,7 +390,6 @@ struct sphx_ctx {
     // [N / 64] one word per wavefront of kbuf: some live lane's k is not +-0 (scratch, not state).  Written with kbuf by the single
     // context's iterations; a correction whose whole reach is flag-free skips its walk (k_correct; SPHX_ZERO_SKIP=0 turns it off)
     uint32_t* knz = nullptr;
-    bool div_knz_fused = false;                // the neighbour build that left kbuf (div_error_fused) left the flags too
     // SPHX_ZERO_SKIP=0/1; -1: by size, on from 4 M particles.  (Measured: at 16 M the skipped walks are 4.7 % of the lattice step; at
     // 1 M they are 2 %, and a step in which nothing can be skipped runs 3.6 % slower with the flags on — profiles/zero_skip/.)
     int zero_skip = -1;
@@ -399,7 +399,6 @@ struct sphx_ctx {
     // iteration in any stripe.  launch_correct then queues the decide-first form of the correction.  A hint only: both forms compute
     // the same bits for any scene.  Scratch, not state: dropped with the lists (lists_went_stale), by sphx_set_boundary and by fail().
     bool quiet_hint[2] = {false, false};
-    uint32_t div_mark_tag = 0;                 // the reduction sequence number the fused build (div_knz_fused) left its mark under
     unsigned long long qf_launches = 0;        // corrections queued in the decide-first form (counted with SPHX_ZERO_SKIP_COUNT=1)
     // Quiet take-over: under a loop's quiet hint the producer of the first iteration's k also stores the warm-start
     // sums (0 + k) — and, in the density loop, makes the next build's cell count, speculatively — and the correction is queued in the
@@ -407,7 +406,6 @@ struct sphx_ctx {
     // whatever the hint says (test aid — either form computes the same bits).
     int quiet_takeover = 1;
     uint32_t thin_grid = 0;                    // SPHX_THIN_GRID=n (test aid): workgroups of a thin launch; 0: one resident generation
-    bool div_warm_taken = false;               // the neighbour build that left the flags (div_knz_fused) stored the warm-start sums too
     int quiet_takeover_density = 1;            // SPHX_QUIET_TAKEOVER_DENSITY=0: the density loop keeps the parent's launches (per-part A/B)
     bool take_over(bool divergence) const {
         return !tile_mode && (divergence || quiet_takeover_density) && (quiet_takeover == 2 || (quiet_takeover == 1 && quiet_hint[divergence ? 1 : 0]));
@@ -475,17 +473,16 @@ struct sphx_ctx {
     int fuse_predict = SPHX_DEFAULT_FUSE_PREDICT;  // SPHX_FUSE_PREDICT=0: the velocity prediction is never folded into the first compute_density_error
     // tile path: the last density correction classifies its particles for the halo exchange (TileClassArgs; SPHX_TILE_FUSE_CLASS=0: off)
     int tile_fuse_class = 1;
-    bool tile_class_done = false;   // ... has happened, for tile_class_n particles advected by the dt with these bits
     uint32_t tile_band_packs = 0;   // statistics: sphx_tile_band_packs
-    bool count_from_class = false;  // the fused cell count on the device is that correction's (drop_class_count)
-    uint32_t tile_class_n = 0, tile_class_dt_bits = 0;
     bool tile_fix_owner = false;    // the re-grid's gather clears the owner bit of kept particles that left the own rectangle
     int fuse_div = 1;              // SPHX_FUSE_DIV=0: the divergence loop's first compute_density_change is never folded into the neighbour build
     int xcd_chunk = -1;            // SPHX_XCD_CHUNK: log2 of the chunk length in blocks, clamped to [0, XCD_SHIFT_MAX] (0: contiguous eighths; -1: by size)
     int alternate_sweep = 1;       // SPHX_ALTERNATE_SWEEP=0: every launch sweeps the particle blocks bottom-up (rounds 1-5)
     int fuse_warm = 1;             // SPHX_FUSE_WARM=0: the divergence warm start is never folded into the neighbour build (A/B)
-    bool div_error_fused = false;  // the latest neighbour build did that pass: the loop's first iteration skips it
-    bool div_warm_fused = false;   // the latest neighbour build applied the divergence loop's warm start
+    // What the latest neighbour build left for the divergence loop (sphx_handoff.hpp).  None -> WarmApplied / FirstErrors: update_neighborhood
+    // (fuse_warm / fuse_div).  Back to None: the loop's first iteration (enqueue_iteration) and sphx_sub_warmstart by taking it; clear() in
+    // update_neighborhood, sphx_step_finish's broken(), sphx_state_load and sub_iteration_impl (an iteration the build did not work for).
+    sphx::BuildHandoff handoff;
     int host_loop = 0;        // SPHX_HOST_LOOP=1: the host judges every residual (round-1 behaviour; A/B runs)
     std::string prof_filter;  // sphx_profile_filter: only launches with this label are timed, every prof_every-th of them
     uint32_t prof_every = 1, prof_counter = 0;
@@ -510,9 +507,11 @@ struct sphx_ctx {
     uint32_t scan_partials_cap = 0;
     unsigned long long* scan_state = nullptr;  // one-pass scan: {epoch, flag, value} per 4096-entry tile
     uint32_t scan_state_cap = 0, scan_epoch = 0;
-    bool fuse_count_ok = false;  // inside sphx_step_finish / _begin_law: the density correction may do the re-grid's cell count
-    bool count_done = false;     // gdyn.hist / key / slot hold the count of the latest density correction (not yet consumed)
-    uint32_t count_n = 0;
+    // The cell count in gdyn.hist / key / slot of a build that has not come yet (sphx_handoff.hpp).  Nobody -> Correction / Classifier: a
+    // counting / classifying density correction (enqueue_iteration); -> Pack: tile_pack_impl (its own count, or the classifier's taken
+    // over), sphx_tile_count_kept.  Back to Nobody: build_grid (consumed), drop_fused_count, drop_class_count (the classifier's only),
+    // clear_histograms, set_directory.  A Classifier's count loses `takeable` in the tile entry points without a flush_pending_advect.
+    sphx::PendingCount pending;
     int no_fused_count = 0;      // SPHX_NO_FUSED_COUNT=1 (A/B runs)
     int scan_two_pass = 0;  // SPHX_SCAN_TWO_PASS=1: the two-launch scan (A/B runs)
     // scalars

@@ -310,7 +310,7 @@ int set_directory(sphx_ctx* c, Grid& g, uint32_t bx0, uint32_t by0, uint32_t bx1
         g.tile_cap = ntile;
     }
     SPHX_HIP(c, hipMemsetAsync(g.tile_empty, 0x01, (size_t)g.tile_cap * 4, c->stream));  // the zeroed table says "empty" everywhere
-    if (&g == &c->gdyn) c->count_done = false;  // a count made with the old directory is gone with the old histogram
+    if (&g == &c->gdyn) c->pending.forget();  // a count made with the old directory is gone with the old histogram
     const uint32_t need = nblocks(len, std::min(SCAN_TILE, SCAN1_TILE)) + 1;
     if (need > c->scan_partials_cap) {
         if ((rc = dev_alloc(c, &c->scan_partials, need))) return rc;
@@ -540,34 +540,31 @@ int publish_and_wait(sphx_ctx* c) {
 
 // The density correction of a step may have left the NEXT build's cell count in gdyn.hist / key / slot (CountArgs).  Whoever
 // needs those buffers clean, or changes what the count was made with, calls this first.
+void wipe_histogram(sphx_ctx* c, Grid& g) {
+    if (g.hist && g.len()) hipMemsetAsync(g.hist, 0, (size_t)g.len() * 4, c->stream);
+}
 void drop_fused_count(sphx_ctx* c) {
-    if (!c->count_done) return;
-    c->count_done = false;
-    if (c->gdyn.hist && c->gdyn.len()) hipMemsetAsync(c->gdyn.hist, 0, (size_t)c->gdyn.len() * 4, c->stream);
+    if (c->pending.drop()) wipe_histogram(c, c->gdyn);
 }
 // A call that failed on the device (SPHX_ERR_HIP, SPHX_ERR_NONFINITE) may have stopped between a cell count and the scatter that
 // counts the histogram back down: with or without a pending fused count, neither histogram is known to be zero any more.  Called by
 // step_finish's failure path and by every sphx_upload (new positions: any count made before is void anyway), so that a failure in
 // any entry point — step_begin's warm-up build included — is cleaned up by the re-upload the context then asks for.
 void clear_histograms(sphx_ctx* c) {
-    c->count_done = false;
-    for (Grid* g : {&c->gdyn, &c->gstat})
-        if (g->hist && g->len()) hipMemsetAsync(g->hist, 0, (size_t)g->len() * 4, c->stream);
+    c->pending.forget();
+    for (Grid* g : {&c->gdyn, &c->gstat}) wipe_histogram(c, *g);
 }
 
 // A cell count made by a tile's density correction (TileClassArgs) is made from ADVECTED positions and leaves out what the tile
 // retires: it is only good for the packing pass that takes over from there (tile_pack_impl).  Whoever else comes first drops it.
 void drop_class_count(sphx_ctx* c) {
-    if (!c->count_from_class) return;
-    c->count_from_class = false;
-    c->tile_class_done = false;
-    drop_fused_count(c);
+    if (c->pending.drop_if_from_classifier()) wipe_histogram(c, c->gdyn);
 }
 // tile path: see sphx_ctx::tile_pending_dt
 void flush_pending_advect(sphx_ctx* c) {
     // (entry points call this before their own hipSetDevice; the launches and the memset below must target THIS context's device —
     // in-process multi-device tiles run each tile on a host thread whose current device is still 0)
-    if (c->count_from_class || c->tile_pending_dt > 0.0f) (void)hipSetDevice(c->device);
+    if (c->pending.from_classifier() || c->tile_pending_dt > 0.0f) (void)hipSetDevice(c->device);
     drop_class_count(c);
     if (!(c->tile_pending_dt > 0.0f)) return;
     const uint32_t n = c->tile_pending_n;
@@ -590,6 +587,13 @@ void flush_pending_advect(sphx_ctx* c) {
     hipLaunchKernelGGL(k_advect, dim3(nblocks(n)), dim3(256), 0, c->stream, c->posA, (const float2*)c->vel, n, dt);
 }
 
+// What every sub-step entry point that reads or moves the particles starts with: a pass that ran ahead is stale from here, and what
+// the packing pass left to the re-grid's gather is done on the spot (with it goes a classifier's count nobody took over).
+void sub_step_enter(sphx_ctx* c) {
+    c->ahead.valid = false;
+    flush_pending_advect(c);
+}
+
 // ---- grid build (a1-a4) -------------------------------------------------------------------------------------------
 // Sorts `n` points into Morton cell order (stable) and leaves the cell table in g.fine.  Attribute arrays in `ga` are
 // gathered alongside; the caller swaps its buffers afterwards.  advect_dt > 0: the fluid build inside a step — the position
@@ -601,20 +605,14 @@ int build_grid(sphx_ctx* c, Grid& g, const float2* pos, uint32_t n, const Gather
     DevScalars* ds = c->d_scal;
     const uint32_t len = g.len();
     const uint32_t nt = nblocks(len, c->scan_two_pass ? SCAN_TILE : SCAN1_TILE);
-    const bool counted = &g == &c->gdyn && c->count_done && advect_dt > 0 && c->count_n == n && !tile_n;
-    // tile path: sphx_tile_count_kept has counted the first count_n particles while the halo exchange was in flight
-    const bool partial = &g == &c->gdyn && c->count_done && tile_n && advect_dt == 0.0f && c->count_n <= n && !counted;
-    uint32_t first = 0;
-    if (&g == &c->gdyn) {
-        if (counted || partial) {
-            c->count_done = false;  // consumed: k_scatter counts the histogram back down to zero as always
-            if (partial) first = c->count_n;
-        } else {
-            drop_fused_count(c);
-        }
-    } else {
-        drop_fused_count(c);  // key / slot are shared with the other grid's build
-    }
+    const bool counted = &g == &c->gdyn && advect_dt > 0 && !tile_n && c->pending.is_for(n);
+    // tile path: the packing pass or sphx_tile_count_kept has counted the first so many particles while the halo exchange was in flight
+    const bool partial = &g == &c->gdyn && tile_n && advect_dt == 0.0f && !counted && c->pending.is_for_first_of(n);
+    const uint32_t first = partial ? c->pending.n() : 0u;
+    if (counted || partial)
+        c->pending.forget();  // consumed: k_scatter counts the histogram back down to zero, as behind any count (the scan leaves it as it is)
+    else
+        drop_fused_count(c);  // (the other grid's build too: key / slot are shared)
     if (n > first && !counted) {
         const uint32_t gbc = std::max(1u, nblocks(n - first));
         if (advect_dt > 0)
@@ -925,7 +923,7 @@ int update_neighborhood(sphx_ctx* c, bool extra_alpha, float advect_dt, bool fus
     if (c->tile_pending_dt > 0.0f) {
         // the packing pass left the advection of the kept particles to this gather — which is only right if its cell count (made
         // from the advected positions) is still the one this build starts from
-        if (c->tile_mode && advect_dt == 0.0f && c->count_done && c->count_n == c->tile_pending_n && c->tile_pending_n <= c->N) {
+        if (c->tile_mode && advect_dt == 0.0f && c->pending.is_for(c->tile_pending_n) && c->tile_pending_n <= c->N) {
             ga.advect_dt = c->tile_pending_dt;
             ga.advect_below = c->tile_pending_n;
             c->tile_pending_dt = 0.0f;
@@ -955,55 +953,40 @@ int update_neighborhood(sphx_ctx* c, bool extra_alpha, float advect_dt, bool fus
     const uint32_t* n_dev = c->tile_mode ? (const uint32_t*)&c->d_scal->sort_total : (const uint32_t*)nullptr;
     if (c->N) {
         const uint32_t n = c->N;
-        c->div_error_fused = false;
-        c->div_warm_fused = false;
-        c->div_knz_fused = false;
-        c->div_warm_taken = false;
+        auto go = [&](auto kernel, const DivArgs& dv) {
+            hipLaunchKernelGGL(kernel, dim3(nblocks(n)), dim3(256), 0, st, (const float2*)c->posA, n, c->soff(), c->K, c->gdyn.nview(), c->gstat.nview(),
+                               c->nb_list, c->nb_counts, c->nb_wave, c->nb_remote, c->density, c->alpha, c->d_scal, n_dev, dv);
+        };
+        c->handoff.clear();
         if (fuse && fuse_warm) {
             DivArgs dv{};
             dv.velw = c->vel;
             dv.warm = c->stiff;
             dv.lim = -0.5f * c->K.rho0 * c->K.rho0;
-            launch(c, "neighbor_build+density_alpha+divergence_warmstart", (8.0 + list_bytes(c) + 8.0 + 8.0 + 8.0 + 4.0) * n, [&] {
-                hipLaunchKernelGGL(k_neighbor_build<3>, dim3(nblocks(n)), dim3(256), 0, st, (const float2*)c->posA, n, c->soff(), c->K, c->gdyn.nview(),
-                                   c->gstat.nview(), c->nb_list, c->nb_counts, c->nb_wave, c->nb_remote, c->density, c->alpha, c->d_scal, n_dev, dv);
-            });
-            c->div_warm_fused = true;
+            launch(c, "neighbor_build+density_alpha+divergence_warmstart", (8.0 + list_bytes(c) + 8.0 + 8.0 + 8.0 + 4.0) * n, [&] { go(k_neighbor_build<3>, dv); });
+            c->handoff = BuildHandoff::warm_applied();
         } else if (fuse && fuse_div) {
             DivArgs dv{};
             dv.vel = (const float2*)c->vel;
             dv.kbuf = c->kbuf;
             dv.knz = zero_skip_flags(c);
-            c->div_knz_fused = dv.knz != nullptr;
             // the scene-wide mark goes under the number the divergence loop's first iteration will get when it is queued next
-            // (sphx_step_finish does that; enqueue_iteration drops the flags if something took the number in between)
-            dv.knz_tag = c->div_mark_tag = c->res_seq + 1u;
+            // (sphx_step_finish does that; BuildHandoff::take_first_errors drops the flags if something took the number in between)
+            dv.knz_tag = c->res_seq + 1u;
             // take-over: the loop's first correction stores 0 + k into the stiffness whatever path it takes, and nothing reads the
             // array between this build and that correction — under the quiet hint the build stores it, and the correction can be thin
-            if (dv.knz && c->take_over(true)) {
+            const bool take = dv.knz && c->take_over(true);
+            if (take) {
                 dv.warm = c->stiff;
-                c->div_warm_taken = true;
                 c->takeover_producers += 1;
             }
-            launch(c, "neighbor_build+density_alpha+density_change", (8.0 + list_bytes(c) + 8.0 + 8.0 + 4.0) * n, [&] {
-                if (c->div_warm_taken)
-                    hipLaunchKernelGGL((k_neighbor_build<2, true>), dim3(nblocks(n)), dim3(256), 0, st, (const float2*)c->posA, n, c->soff(), c->K, c->gdyn.nview(),
-                                       c->gstat.nview(), c->nb_list, c->nb_counts, c->nb_wave, c->nb_remote, c->density, c->alpha, c->d_scal, n_dev, dv);
-                else
-                    hipLaunchKernelGGL(k_neighbor_build<2>, dim3(nblocks(n)), dim3(256), 0, st, (const float2*)c->posA, n, c->soff(), c->K, c->gdyn.nview(),
-                                       c->gstat.nview(), c->nb_list, c->nb_counts, c->nb_wave, c->nb_remote, c->density, c->alpha, c->d_scal, n_dev, dv);
-            });
-            c->div_error_fused = true;
+            launch(c, "neighbor_build+density_alpha+density_change", (8.0 + list_bytes(c) + 8.0 + 8.0 + 4.0) * n,
+                   [&] { take ? go(k_neighbor_build<2, true>, dv) : go(k_neighbor_build<2>, dv); });
+            c->handoff = BuildHandoff::first_errors(dv.knz != nullptr, dv.knz_tag, take);
         } else if (fuse)
-            launch(c, "neighbor_build+density_alpha", (8.0 + list_bytes(c) + 8.0) * n, [&] {
-                hipLaunchKernelGGL(k_neighbor_build<1>, dim3(nblocks(n)), dim3(256), 0, st, (const float2*)c->posA, n, c->soff(), c->K,
-                                   c->gdyn.nview(), c->gstat.nview(), c->nb_list, c->nb_counts, c->nb_wave, c->nb_remote, c->density, c->alpha, c->d_scal, n_dev, DivArgs{});
-            });
+            launch(c, "neighbor_build+density_alpha", (8.0 + list_bytes(c) + 8.0) * n, [&] { go(k_neighbor_build<1>, DivArgs{}); });
         else
-            launch(c, "neighbor_build", (8.0 + list_bytes(c)) * n, [&] {
-                hipLaunchKernelGGL(k_neighbor_build<0>, dim3(nblocks(n)), dim3(256), 0, st, (const float2*)c->posA, n, c->soff(), c->K,
-                                   c->gdyn.nview(), c->gstat.nview(), c->nb_list, c->nb_counts, c->nb_wave, c->nb_remote, c->density, c->alpha, c->d_scal, n_dev, DivArgs{});
-            });
+            launch(c, "neighbor_build", (8.0 + list_bytes(c)) * n, [&] { go(k_neighbor_build<0>, DivArgs{}); });
     }
     if (c->tile_mode && c->N) {
         if ((rc = wait_mailbox(c, tile_n))) return rc;  // tile_n carries the sequence number of the publish inside build_grid
@@ -1019,24 +1002,13 @@ template <int KIND>
 void launch_density(sphx_ctx* c, bool density, bool alpha) {
     const uint32_t n = c->N;
     if (!n) return;
-    hipStream_t st = c->stream;
-    const dim3 g(nblocks(n)), b(256);
     const double bytes = (8.0 + list_bytes(c) + (density ? 4 : 0) + (alpha ? 4 : 0)) * n;
-    if (density && alpha)
-        launch(c, "density_alpha", bytes, [&] {
-            hipLaunchKernelGGL((k_density_alpha<KIND, true, true>), g, b, 0, st, (const float2*)c->posA, n, c->soff(), c->K,
-                               c->nbv(), c->density, c->alpha);
-        });
-    else if (density)
-        launch(c, "update_densities", bytes, [&] {
-            hipLaunchKernelGGL((k_density_alpha<KIND, true, false>), g, b, 0, st, (const float2*)c->posA, n, c->soff(), c->K,
-                               c->nbv(), c->density, c->alpha);
-        });
-    else
-        launch(c, "compute_alpha_factors", bytes, [&] {
-            hipLaunchKernelGGL((k_density_alpha<0, false, true>), g, b, 0, st, (const float2*)c->posA, n, c->soff(), c->K,
-                               c->nbv(), c->density, c->alpha);
-        });
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(nblocks(n)), dim3(256), 0, c->stream, (const float2*)c->posA, n, c->soff(), c->K, c->nbv(), c->density, c->alpha);
+    };
+    if (density && alpha) return launch(c, "density_alpha", bytes, [&] { go(k_density_alpha<KIND, true, true>); });
+    if (density) return launch(c, "update_densities", bytes, [&] { go(k_density_alpha<KIND, true, false>); });
+    launch(c, "compute_alpha_factors", bytes, [&] { go(k_density_alpha<0, false, true>); });
 }
 
 // cap: the capacity to allocate when n does not fit (0: exactly n).  keep_set (sphx_append): positions, velocities and ids of [0, N)
@@ -1115,47 +1087,32 @@ void launch_compute_error(sphx_ctx* c, bool divergence, float dt, const float* d
                           const PredArgs* pred, uint32_t* knz, uint32_t knz_tag, bool take_warm = false,
                           const CountArgs& take_count = CountArgs{}) {
     const uint32_t n = c->N;
-    hipStream_t st = c->stream;
-    const dim3 g(nblocks(n)), b(256);
     const double lb = list_bytes(c);
+    // warm: where a take-over producer stores the warm-start sums 0 + k; take: NoTake{}, or the speculative cell count that goes out with them
+    auto go = [&](auto kernel, float* warm, const PredArgs& pa, auto take) {
+        hipLaunchKernelGGL(kernel, dim3(nblocks(n)), dim3(256), 0, c->stream, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt,
+                           c->nbv(), c->kbuf, warm, c->d_scal, dt_dev, la, clear_hist, clear_len, pa, knz, knz_tag, take);
+    };
     if (divergence) {
         launch(c, "compute_density_change", (16 + 4 + 4 + lb) * n, [&] {
-            if (knz && take_warm)  // (take-over: the warm-start sums 0 + k go out with k)
-                hipLaunchKernelGGL((k_compute_error<true, false, true, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt,
-                                   c->nbv(), c->kbuf, c->stiff, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz, knz_tag, NoTake{});
-            else if (knz)
-                hipLaunchKernelGGL((k_compute_error<true, false, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt, c->nbv(),
-                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz, knz_tag, NoTake{});
-            else
-                hipLaunchKernelGGL((k_compute_error<true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt, c->nbv(),
-                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz, knz_tag, NoTake{});
+            if (knz && take_warm) return go(k_compute_error<true, false, true, true>, c->stiff, PredArgs{}, NoTake{});  // (take-over: the sums 0 + k go out with k)
+            if (knz) return go(k_compute_error<true, false, true>, nullptr, PredArgs{}, NoTake{});
+            go(k_compute_error<true>, nullptr, PredArgs{}, NoTake{});
         });
     } else if (pred) {
         PredArgs pa = *pred;
         pa.accel = c->accel;
         pa.vel_out = c->vel2;
         launch(c, "velocity_prediction+compute_density_error", (16 + 8 + 8 + 4 + 4 + 4 + lb) * n, [&] {
-            if (knz && take_warm)  // (take-over: kappa = 0 + k and the speculative cell count go out with k)
-                hipLaunchKernelGGL((k_compute_error<false, true, true, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt,
-                                   c->nbv(), c->kbuf, c->kappa, c->d_scal, dt_dev, la, clear_hist, clear_len, pa, knz, knz_tag, take_count);
-            else if (knz)
-                hipLaunchKernelGGL((k_compute_error<false, true, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt,
-                                   c->nbv(), c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, pa, knz, knz_tag, NoTake{});
-            else
-                hipLaunchKernelGGL((k_compute_error<false, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt,
-                                   c->nbv(), c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, pa, knz, knz_tag, NoTake{});
+            if (knz && take_warm) return go(k_compute_error<false, true, true, true>, c->kappa, pa, take_count);  // (take-over: kappa = 0 + k and the count go out too)
+            if (knz) return go(k_compute_error<false, true, true>, nullptr, pa, NoTake{});
+            go(k_compute_error<false, true>, nullptr, pa, NoTake{});
         });
     } else {
         launch(c, "compute_density_error", (16 + 4 + 4 + 4 + lb) * n + (clear_hist ? 4.0 * clear_len : 0.0), [&] {
-            if (knz && take_warm)
-                hipLaunchKernelGGL((k_compute_error<false, false, true, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt,
-                                   c->nbv(), c->kbuf, c->kappa, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz, knz_tag, take_count);
-            else if (knz)
-                hipLaunchKernelGGL((k_compute_error<false, false, true>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt, c->nbv(),
-                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz, knz_tag, NoTake{});
-            else
-                hipLaunchKernelGGL((k_compute_error<false>), g, b, 0, st, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt, c->nbv(),
-                                   c->kbuf, (float*)nullptr, c->d_scal, dt_dev, la, clear_hist, clear_len, PredArgs{}, knz, knz_tag, NoTake{});
+            if (knz && take_warm) return go(k_compute_error<false, false, true, true>, c->kappa, PredArgs{}, take_count);
+            if (knz) return go(k_compute_error<false, false, true>, nullptr, PredArgs{}, NoTake{});
+            go(k_compute_error<false>, nullptr, PredArgs{}, NoTake{});
         });
     }
 }
@@ -1171,9 +1128,8 @@ inline bool correct_skip_ok(const sphx_ctx* c, bool divergence, float dt, const 
 void launch_correct(sphx_ctx* c, bool divergence, float dt, const float* dt_dev, const CountArgs& ca, const LoopArgs& la, const ResArgs& ra, bool first,
                     const TileClassArgs& tc, const uint32_t* knz, bool warm_taken = false) {
     const uint32_t n = c->N, f = first ? 1u : 0u;
-    hipStream_t st = c->stream;
-    const dim3 g(nblocks(n)), b(256);
     const float inv_dt = 1.0f / dt, lim = -0.5f * c->K.rho0 * c->K.rho0;
+    const char* const label = divergence ? "correct_velocity_with_divergence_error" : "correct_velocity_with_density_error";
     float* warm = divergence ? c->stiff : c->kappa;
     const bool skip_ok = correct_skip_ok(c, divergence, dt, dt_dev, tc, knz);
     const ZeroSkipArgs zs{skip_ok ? knz : nullptr, c->zero_skip_count ? 1u : 0u};
@@ -1190,62 +1146,39 @@ void launch_correct(sphx_ctx* c, bool divergence, float dt, const float* dt_dev,
     if (thin) {
         c->thin_launches += 1;
         const uint32_t vblocks = nblocks(n);
-        const dim3 tg(std::min(vblocks, c->thin_grid ? c->thin_grid : 2048u));
-        launch(
-            c, divergence ? "correct_velocity_with_divergence_error" : "correct_velocity_with_density_error",
-            (16 + 8 + 12 + 8 + list_bytes(c) + (ca.hist ? 8 : 0)) * n,
-            [&] {
-                if (divergence)
-                    hipLaunchKernelGGL((k_correct_thin<false>), tg, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K,
-                                       inv_dt, lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, zs, vblocks);
-                else
-                    hipLaunchKernelGGL((k_correct_thin<true>), tg, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K,
-                                       inv_dt, lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, zs, vblocks);
-            },
-            false);
-        return;
+        auto go_thin = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(std::min(vblocks, c->thin_grid ? c->thin_grid : 2048u)), dim3(256), 0, c->stream, c->vel, (const float2*)c->posA,
+                               (const float*)c->kbuf, warm, n, c->soff(), c->K, inv_dt, lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, zs, vblocks);
+        };
+        const double bytes = (16 + 8 + 12 + 8 + list_bytes(c) + (ca.hist ? 8 : 0)) * n;
+        return launch(c, label, bytes, [&] { divergence ? go_thin(k_correct_thin<false>) : go_thin(k_correct_thin<true>); }, false);
     }
-    launch(c, divergence ? "correct_velocity_with_divergence_error" : "correct_velocity_with_density_error",
-           (16 + 8 + 12 + 8 + list_bytes(c) + (ca.hist ? (tc.pid ? 8 + 4 : 8) : 0)) * n, [&] {
-               // (a launch without flags runs the instantiation without the skip's decision: the code from before it)
-               if (divergence && quiet_first)
-                   hipLaunchKernelGGL((k_correct<false, false, false, true, true>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(),
-                                      c->K, inv_dt, lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, f, tc, zs);
-               else if (quiet_first)
-                   hipLaunchKernelGGL((k_correct<false, true, false, true, true>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(),
-                                      c->K, inv_dt, lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, f, tc, zs);
-               else if (divergence && zs.knz)
-                   hipLaunchKernelGGL((k_correct<false, false, false, true>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K,
-                                      inv_dt, lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, f, tc, zs);
-               else if (divergence)
-                   hipLaunchKernelGGL((k_correct<false, false>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K, inv_dt,
-                                      lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, f, tc, zs);
-               else if (tc.pid)
-                   hipLaunchKernelGGL((k_correct<false, true, true>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K,
-                                      inv_dt, lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, f, tc, ZeroSkipArgs{});
-               else if (zs.knz)
-                   hipLaunchKernelGGL((k_correct<false, true, false, true>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K,
-                                      inv_dt, lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, f, tc, zs);
-               else
-                   hipLaunchKernelGGL((k_correct<false, true>), g, b, 0, st, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K, inv_dt,
-                                      lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, f, tc, zs);
-           });
+    auto go = [&](auto kernel, const ZeroSkipArgs& zsa) {
+        hipLaunchKernelGGL(kernel, dim3(nblocks(n)), dim3(256), 0, c->stream, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K, inv_dt,
+                           lim, c->nbv(), dt_dev, ca, c->d_scal, la, ra, f, tc, zsa);
+    };
+    launch(c, label, (16 + 8 + 12 + 8 + list_bytes(c) + (ca.hist ? (tc.pid ? 8 + 4 : 8) : 0)) * n, [&] {
+        // (a launch without flags runs the instantiation without the skip's decision: the code from before it)
+        if (divergence && quiet_first) return go(k_correct<false, false, false, true, true>, zs);
+        if (quiet_first) return go(k_correct<false, true, false, true, true>, zs);
+        if (divergence && zs.knz) return go(k_correct<false, false, false, true>, zs);
+        if (divergence) return go(k_correct<false, false>, zs);
+        if (tc.pid) return go(k_correct<false, true, true>, ZeroSkipArgs{});
+        if (zs.knz) return go(k_correct<false, true, false, true>, zs);
+        go(k_correct<false, true>, zs);
+    });
 }
 
 // The warm start in front of a loop (dfsph.rs:199-205 / :354-360).  labelled = false (the tile sub-step): a bare launch, outside
 // launch() — no label, no profile record, and K.rev / K.xcd_shift / K.nt_cold stay as the launch before it left them.
 void launch_warmstart(sphx_ctx* c, bool divergence, float dt, const float* dt_dev, bool labelled) {
     const uint32_t n = c->N;
-    const dim3 g(nblocks(n)), b(256);
     const float inv_dt = 1.0f / dt, lim = -0.5f * c->K.rho0 * c->K.rho0;
-    auto go = [&] {
-        if (divergence)
-            hipLaunchKernelGGL((k_correct<true, false>), g, b, 0, c->stream, c->vel, (const float2*)c->posA, (const float*)c->kbuf, c->stiff, n, c->soff(), c->K,
-                               inv_dt, lim, c->nbv(), dt_dev, CountArgs{}, c->d_scal, LoopArgs{}, ResArgs{}, 0u, TileClassArgs{}, ZeroSkipArgs{});
-        else
-            hipLaunchKernelGGL((k_correct<true, true>), g, b, 0, c->stream, c->vel, (const float2*)c->posA, (const float*)c->kbuf, c->kappa, n, c->soff(), c->K,
-                               inv_dt, lim, c->nbv(), dt_dev, CountArgs{}, c->d_scal, LoopArgs{}, ResArgs{}, 0u, TileClassArgs{}, ZeroSkipArgs{});
+    auto one = [&](auto kernel, float* warm) {
+        hipLaunchKernelGGL(kernel, dim3(nblocks(n)), dim3(256), 0, c->stream, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K, inv_dt,
+                           lim, c->nbv(), dt_dev, CountArgs{}, c->d_scal, LoopArgs{}, ResArgs{}, 0u, TileClassArgs{}, ZeroSkipArgs{});
     };
+    auto go = [&] { divergence ? one(k_correct<true, false>, c->stiff) : one(k_correct<true, true>, c->kappa); };
     if (!labelled) return go();
     // own position + velocity read, velocity written, staged positions, warm-start values
     launch(c, divergence ? "correct_divergence_error_warmstart" : "correct_density_error_warmstart", (16 + 8 + 8 + 4 + list_bytes(c)) * n, go);
@@ -1275,9 +1208,7 @@ uint32_t enqueue_iteration(sphx_ctx* c, const IterSpec& s) {
     if (s.out_warm && s.first) {
         const bool warm = (s.divergence ? c->num_divergence_iters : c->num_density_iters) > 1;  // dfsph.rs:199 / :354
         *s.out_warm = warm ? 1u : 0u;
-        if (warm && s.divergence && c->div_warm_fused)  // the neighbour build has applied it
-            c->div_warm_fused = false;
-        else if (warm)
+        if (warm && !(s.divergence && c->handoff.take_warm()))  // (taken: the neighbour build has applied it)
             launch_warmstart(c, s.divergence, s.dt, s.dt_dev, true);
     }
     const uint32_t seq = ++c->seq;
@@ -1285,10 +1216,10 @@ uint32_t enqueue_iteration(sphx_ctx* c, const IterSpec& s) {
     // the flags the correction may trust: the ones the producer of THIS iteration's kbuf wrote
     uint32_t* knz = s.tc.pid ? nullptr : zero_skip_flags(c);
     bool warm_taken = false;  // take-over: this iteration's producer has stored the warm-start sums its correction would store
-    if (s.divergence && s.first && c->div_error_fused) {  // the neighbour build has left this iteration's errors, residual and zeroed warm-start values
-        c->div_error_fused = false;
-        if (!c->div_knz_fused || c->div_mark_tag != ra.rseq) knz = nullptr;  // (a mark under another number says nothing about this one)
-        warm_taken = knz && c->div_warm_taken;
+    const BuildHandoff::Taken built = c->handoff.take_first_errors(s.divergence && s.first, ra.rseq);
+    if (built.fused) {  // the neighbour build has left this iteration's errors, residual and zeroed warm-start values
+        if (!built.flags_usable) knz = nullptr;
+        warm_taken = knz && built.warm_taken;
     } else {
         // (a count an earlier correction left is dropped in FRONT of this compute_error: under the take-over it makes the new one)
         if (s.drop_count) drop_fused_count(c);
@@ -1297,21 +1228,19 @@ uint32_t enqueue_iteration(sphx_ctx* c, const IterSpec& s) {
         if (warm_taken) c->takeover_producers += 1;
         launch_compute_error(c, s.divergence, s.dt, s.dt_dev, s.la, s.clear_hist, s.clear_len, s.pred, knz, ra.rseq, warm_taken, s.ca);
     }
-    c->div_warm_taken = false;
     if (s.pred) std::swap(c->vel, c->vel2);  // the predicted velocities are the velocities from here on (the boundary tail is zero in both)
     if (s.drop_count) drop_fused_count(c);  // (the fused-build path; a no-op behind the one above)
-    if (s.ca.hist) {
-        c->count_done = true;
-        c->count_n = c->N;
-    }
+    // the correction below counts (tc.pid: and classifies, with this dt)
+    if (s.ca.hist) s.tc.pid ? c->pending.made_by_classifier(c->N, s.dt) : c->pending.made_by_correction(c->N);
     launch_correct(c, s.divergence, s.dt, s.dt_dev, s.ca, s.la, ra, s.first, s.tc, knz, warm_taken);
     return seq;
 }
 
 // The single context's form of it.  dt_dev: queued by sphx_step_begin_law before the host knows dt.  iter: 1-based index inside its
-// loop; gen: generation number of a device-run loop (0: the host judges the residual).  pred (first density iteration, no warm start
-// in front of it): the caller has NOT launched k_predict.
-uint32_t enqueue_context_iteration(sphx_ctx* c, bool divergence, float dt, const float* dt_dev, uint32_t iter, uint32_t gen, uint32_t* out_warm,
+// loop; gen: generation number of a device-run loop (0: the host judges the residual).  count_ok (the density loops of
+// sphx_step_finish / _begin_law): the correction may do the re-grid's cell count.  pred (first density iteration, no warm start in
+// front of it): the caller has NOT launched k_predict.
+uint32_t enqueue_context_iteration(sphx_ctx* c, bool divergence, float dt, const float* dt_dev, uint32_t iter, uint32_t gen, uint32_t* out_warm, bool count_ok,
                                    const PredArgs* pred = nullptr) {
     IterSpec s{divergence, iter == 1, dt, dt_dev, out_warm, pred};
     if (gen) {
@@ -1326,12 +1255,12 @@ uint32_t enqueue_context_iteration(sphx_ctx* c, bool divergence, float dt, const
         s.la.dt = dt;
     }
     if (!divergence) s.clear_len = c->gdyn.len();
-    if (!divergence && c->fuse_count_ok && !c->no_fused_count && !c->tile_mode && c->gdyn.len()) {
+    if (!divergence && count_ok && !c->no_fused_count && !c->tile_mode && c->gdyn.len()) {
         // Every correction counts.  Host-run loop: the count of a correction that turned out not to be the last is dropped in front of
         // the next one; device-run loop: an iteration that follows another has its compute_error wipe that one's count.
         s.ca = count_args(c, dt);
         s.drop_count = !gen || s.first;
-        if (!s.drop_count && c->count_done) s.clear_hist = c->gdyn.hist;
+        if (!s.drop_count && c->pending.live()) s.clear_hist = c->gdyn.hist;
     }
     return enqueue_iteration(c, s);
 }
@@ -1410,13 +1339,13 @@ uint32_t take_vmax_slot(sphx_ctx* c) {
 // The non-pressure pass of dfsph.rs:436-477 (accelerations + max |v + a dt_prev|^2 into vmax slot `vslot`).
 void enqueue_nonpressure(sphx_ctx* c, float dt_prev, uint32_t vslot) {
     const uint32_t n = c->N;
+    auto go = [&](auto kernel, auto visc) {
+        hipLaunchKernelGGL(kernel, dim3(nblocks(n)), dim3(256), 0, c->stream, c->pv(), (const float*)c->density, n, c->soff(), c->K, dt_prev, c->nbv(), c->accel,
+                           c->d_scal, vslot, visc);
+    };
     launch(c, "nonpressure_accel_vmax", (16.0 + 8 + 4 + list_bytes(c)) * n, [&] {
-        if (c->VK.visc_model == SPHX_VISCOSITY_PHYSICAL)
-            hipLaunchKernelGGL(k_nonpressure<SPHX_VISCOSITY_PHYSICAL>, dim3(nblocks(n)), dim3(256), 0, c->stream, c->pv(), (const float*)c->density, n,
-                               c->soff(), c->K, dt_prev, c->nbv(), c->accel, c->d_scal, vslot, ViscArg<SPHX_VISCOSITY_PHYSICAL>{c->VK});
-        else
-            hipLaunchKernelGGL(k_nonpressure<SPHX_VISCOSITY_XSPH>, dim3(nblocks(n)), dim3(256), 0, c->stream, c->pv(), (const float*)c->density, n,
-                               c->soff(), c->K, dt_prev, c->nbv(), c->accel, c->d_scal, vslot, ViscArg<SPHX_VISCOSITY_XSPH>{});
+        if (c->VK.visc_model == SPHX_VISCOSITY_PHYSICAL) return go(k_nonpressure<SPHX_VISCOSITY_PHYSICAL>, ViscArg<SPHX_VISCOSITY_PHYSICAL>{c->VK});
+        go(k_nonpressure<SPHX_VISCOSITY_XSPH>, ViscArg<SPHX_VISCOSITY_XSPH>{});
     });
 }
 
@@ -1438,9 +1367,9 @@ void enqueue_run_ahead(sphx_ctx* c, float dt, bool publish) {
 }
 
 // One solver loop (dfsph.rs:195-247 density / :346-402 divergence).  pre_seq != 0: `pre_q` iterations (the first one publishing
-// pre_seq) of loop generation pre_gen are already on the stream.
+// pre_seq) of loop generation pre_gen are already on the stream.  count_ok: see enqueue_context_iteration.
 // run_ahead (last loop of a step only): see sphx_ctx::ahead.
-int solver_loop(sphx_ctx* c, bool divergence, float dt, uint32_t* out_iters, float* out_avg, uint32_t* out_warm, uint32_t* io_flags,
+int solver_loop(sphx_ctx* c, bool divergence, float dt, uint32_t* out_iters, float* out_avg, uint32_t* out_warm, uint32_t* io_flags, bool count_ok,
                 uint32_t pre_seq = 0, uint32_t pre_q = 0, uint32_t pre_gen = 0, bool run_ahead = false) {
     uint32_t iters = 0;
     float avg = 0;
@@ -1455,10 +1384,10 @@ int solver_loop(sphx_ctx* c, bool divergence, float dt, uint32_t* out_iters, flo
         if (!pre_seq) {
             if (++c->loop_gen == 0) c->loop_gen = 1;
             gen = c->loop_gen;
-            seq1 = enqueue_context_iteration(c, divergence, dt, nullptr, 1, gen, out_warm);
+            seq1 = enqueue_context_iteration(c, divergence, dt, nullptr, 1, gen, out_warm, count_ok);
             q = 1;
         }
-        while (q < std::min(prev, cap)) enqueue_context_iteration(c, divergence, dt, nullptr, ++q, gen, out_warm);
+        while (q < std::min(prev, cap)) enqueue_context_iteration(c, divergence, dt, nullptr, ++q, gen, out_warm, count_ok);
         if (run_ahead && c->run_ahead) enqueue_run_ahead(c, dt, false);
         uint32_t w = q;  // the iteration whose verdict the host waits for: the last predicted one first
         for (;;) {
@@ -1468,7 +1397,7 @@ int solver_loop(sphx_ctx* c, bool divergence, float dt, uint32_t* out_iters, flo
             c->ahead.valid = false;  // more iterations follow: the pass queued above has read velocities that were not final
             // iteration w has published without meeting the test: the prediction was too low.  From here on keep one full iteration
             // queued behind the one that is running (the host then never sits on the device's critical path).
-            while (q < w + 2) enqueue_context_iteration(c, divergence, dt, nullptr, ++q, gen, out_warm);
+            while (q < w + 2) enqueue_context_iteration(c, divergence, dt, nullptr, ++q, gen, out_warm, count_ok);
             w += 1;
         }
         iters = c->mbox->loop_iters;
@@ -1489,7 +1418,7 @@ int solver_loop(sphx_ctx* c, bool divergence, float dt, uint32_t* out_iters, flo
             if (k == iters) *io_flags |= fl;
         }
     } else {
-        uint32_t seq = pre_seq ? pre_seq : enqueue_context_iteration(c, divergence, dt, nullptr, 1, 0, out_warm);
+        uint32_t seq = pre_seq ? pre_seq : enqueue_context_iteration(c, divergence, dt, nullptr, 1, 0, out_warm, count_ok);
         for (;;) {
             iters += 1;
             // the residual was published by compute_error; the correction kernel runs while the host reads it
@@ -1500,7 +1429,7 @@ int solver_loop(sphx_ctx* c, bool divergence, float dt, uint32_t* out_iters, flo
                 c->quiet_hint[divergence ? 1 : 0] = c->mbox->quiet_seq == seq;
                 break;
             }
-            seq = enqueue_context_iteration(c, divergence, dt, nullptr, iters + 1, 0, out_warm);
+            seq = enqueue_context_iteration(c, divergence, dt, nullptr, iters + 1, 0, out_warm, count_ok);
         }
     }
     *out_iters = iters;
@@ -1976,20 +1905,18 @@ int sphx_step_begin_law(sphx_ctx* c, float dt_prev, const sphx_timer_law* law, f
         const PredArgs* const pred = fuse_pred ? &pa : nullptr;
         if (!fuse_pred)
             launch_predict(c, "velocity_prediction", 1.0f, va, tl);
-        c->fuse_count_ok = true;
         if (device_loop(c)) {
             // as many constant-density iterations as the previous step needed, all reading the device's dt; the device stops the loop
             if (++c->loop_gen == 0) c->loop_gen = 1;
             c->pre_gen = c->loop_gen;
             const uint32_t want = std::min(std::max(1u, c->num_density_iters), c->P.max_density_iterations + 1);
-            c->pre_seq = enqueue_context_iteration(c, false, 1.0f, dt_dev, 1, c->pre_gen, &c->pre_warm, pred);
-            for (c->pre_queued = 1; c->pre_queued < want;) enqueue_context_iteration(c, false, 1.0f, dt_dev, ++c->pre_queued, c->pre_gen, &c->pre_warm);
+            c->pre_seq = enqueue_context_iteration(c, false, 1.0f, dt_dev, 1, c->pre_gen, &c->pre_warm, true, pred);
+            for (c->pre_queued = 1; c->pre_queued < want;) enqueue_context_iteration(c, false, 1.0f, dt_dev, ++c->pre_queued, c->pre_gen, &c->pre_warm, true);
         } else {
             c->pre_gen = 0;
             c->pre_queued = 1;
-            c->pre_seq = enqueue_context_iteration(c, false, 1.0f, dt_dev, 1, 0, &c->pre_warm, pred);
+            c->pre_seq = enqueue_context_iteration(c, false, 1.0f, dt_dev, 1, 0, &c->pre_warm, true, pred);
         }
-        c->fuse_count_ok = false;
         c->law_active = true;
     }
     if ((rc = wait_mailbox(c, seq))) return rc;
@@ -2035,8 +1962,7 @@ int sphx_step_finish(sphx_ctx* c, float dt, sphx_step_stats* out) {
         }
         drop_fused_count(c);  // (a count of the next build made by this step's density correction: that build does not come)
         c->ahead.valid = false;
-        c->div_error_fused = c->div_warm_fused = false;
-        c->fuse_count_ok = false;
+        c->handoff.clear();
         c->law_active = false;
         return code;
     };
@@ -2060,17 +1986,15 @@ int sphx_step_finish(sphx_ctx* c, float dt, sphx_step_stats* out) {
             launch_predict(c, "velocity_prediction", dt);
         }
         c->law_active = false;
-        c->fuse_count_ok = true;
-        rc = solver_loop(c, false, dt, &s.density_iterations, &s.avg_density_error, &s.warmstart_density, &c->step_flags, pre, pre_q, pre_gen);
-        c->fuse_count_ok = false;
-        if (rc) return broken(rc);
+        if ((rc = solver_loop(c, false, dt, &s.density_iterations, &s.avg_density_error, &s.warmstart_density, &c->step_flags, true, pre, pre_q, pre_gen)))
+            return broken(rc);
         // advect (dfsph.rs:499-510) fused into the re-grid (dfsph.rs:512); densities + alpha (dfsph.rs:516-518) fused into the
         // neighbour build
         // (no warm start in front of the divergence loop <=> the previous one took a single iteration, dfsph.rs:354)
         const bool fuse_div = c->fuse_div && !c->tile_mode && c->num_divergence_iters <= 1;
         const bool fuse_warm = c->fuse_div && c->fuse_warm && !c->tile_mode && c->num_divergence_iters > 1;
         if ((rc = update_neighborhood(c, false, dt, true, fuse_div, fuse_warm))) return broken(rc);
-        if ((rc = solver_loop(c, true, dt, &s.divergence_iterations, &s.avg_divergence, &s.warmstart_divergence, &c->step_flags, 0, 0, 0, true)))
+        if ((rc = solver_loop(c, true, dt, &s.divergence_iterations, &s.avg_divergence, &s.warmstart_divergence, &c->step_flags, false, 0, 0, 0, true)))
             return broken(rc);
         // dfsph.rs:524: the predicted velocities in vel[] ARE the new velocities (no copy)
         s.neighbor_entries = c->nb_last;
@@ -2376,7 +2300,7 @@ int sphx_reserve(sphx_ctx* c, uint32_t capacity) {
 // corner neighbours, at most 8), in the order the caller will pass the send / receive buffers.
 int sphx_tile_configure_rect(sphx_ctx* c, const sphx_tile_rect* own, uint32_t halo_cells, const sphx_tile_rect* peers, uint32_t n_peers) {
     if (!c || !own || halo_cells == 0 || n_peers > MAX_TILE_PEERS || (n_peers && !peers)) return SPHX_ERR_INVALID_ARGUMENT;
-    c->tile_class_done = false;
+    c->pending.bar_take_over();
     c->ahead.valid = false;
     auto bad = [](const sphx_tile_rect& r) { return r.x0 >= r.x1 || r.y0 >= r.y1 || r.x1 > 65536 || r.y1 > 65536; };
     if (bad(*own)) return c->fail(SPHX_ERR_INVALID_ARGUMENT, "tile rectangle must be non-empty and inside the u16 cell range");
@@ -2414,7 +2338,7 @@ int sphx_tile_configure(sphx_ctx* c, int axis, uint32_t cell_lo, uint32_t cell_h
 
 int sphx_tile_upload(sphx_ctx* c, const float* pos_xy, const float* vel_xy, const uint32_t* ids, uint32_t n) {
     if (!c || !c->tile_mode) return SPHX_ERR_INVALID_ARGUMENT;
-    c->tile_class_done = false;
+    c->pending.bar_take_over();
     c->ahead.valid = false;
     int rc = sphx_upload(c, pos_xy, vel_xy, n);
     if (rc) return rc;
@@ -2461,15 +2385,10 @@ static int tile_pack_impl(sphx_ctx* c, float advect_dt, void* const* d_send, uin
         return SPHX_OK;
     }
     const uint32_t nb = nblocks(n);
-    uint32_t dt_bits;
-    std::memcpy(&dt_bits, &advect_dt, 4);
-    if (c->tile_class_done && c->count_done && c->count_n == n && c->tile_class_n == n && advect_dt > 0 && dt_bits == c->tile_class_dt_bits &&
-        !(c->tile_pending_dt > 0.0f)) {
+    if (advect_dt > 0 && !(c->tile_pending_dt > 0.0f) && c->pending.take_over_class(n, advect_dt)) {
         // the loop's last density correction has counted the kept particles' cells and the records to send: the advection is left to
         // the re-grid's gather (as is the owner bit of particles that stay as ghosts), and only the workgroups that send anything are
-        // visited again
-        c->tile_class_done = false;
-        c->count_from_class = false;  // (taken over: the pending advection and the owner fix below complete it)
+        // visited again.  (Taken over: the pending advection and the owner fix below complete the count.)
         c->tile_band_packs += 1;
         c->tile_pending_dt = advect_dt;
         c->tile_pending_n = n;
@@ -2484,7 +2403,6 @@ static int tile_pack_impl(sphx_ctx* c, float advect_dt, void* const* d_send, uin
         if (!c->external_stream) SPHX_HIP(c, hipStreamSynchronize(st));
         return SPHX_OK;
     }
-    c->tile_class_done = false;
     // the packing pass ends with the first pass of the re-grid that follows the exchange — cell and histogram of the particles the
     // tile keeps (build_grid then counts the arrivals only); not when the directory is about to change
     CountArgs ca{};
@@ -2492,12 +2410,8 @@ static int tile_pack_impl(sphx_ctx* c, float advect_dt, void* const* d_send, uin
     if (!c->no_fused_count && c->gdyn.len() && !c->boundary_changed && !c->need_expand && !c->need_recover && !c->recover_streak && !c->tails_dirty &&
         c->builds_since_cover + 1 < COVER_PERIOD) {
         drop_fused_count(c);
-        ca.g = c->gdyn.view();
-        ca.hist = c->gdyn.hist;
-        ca.cidx = c->key;
-        ca.slot = c->slot;
-        c->count_done = true;
-        c->count_n = n;
+        ca = count_args(c, 0.0f);
+        c->pending.made_by_pack(n);
     }
     // with the count fused in, nothing reads the kept particles' records before the re-grid's gather moves them: that gather applies
     // the advection (the same two operations) on the way, and this pass does not write the 24 bytes per particle
@@ -2548,7 +2462,7 @@ int sphx_tile_send_counts(sphx_ctx* c, void* const* d_send, uint32_t n_send, uin
 // count becomes an upper bound until sphx_sub_regrid.
 int sphx_tile_apply_n(sphx_ctx* c, const void* const* d_recv, uint32_t n_recv, uint32_t cap_records) {
     if (!c || !c->tile_mode || n_recv != c->tile_npeers || (n_recv && !d_recv)) return SPHX_ERR_INVALID_ARGUMENT;
-    c->tile_class_done = false;
+    c->pending.bar_take_over();
     c->ahead.valid = false;
     SPHX_HIP(c, hipSetDevice(c->device));
     const uint32_t n = c->N;
@@ -2593,21 +2507,20 @@ int sphx_tile_apply(sphx_ctx* c, const void* d_from_left, const void* d_from_rig
 // the cell directory is about to change (the re-grid counts everything itself then).
 int sphx_tile_count_kept(sphx_ctx* c) {
     if (!c || !c->tile_mode) return SPHX_ERR_INVALID_ARGUMENT;
-    c->tile_class_done = false;
+    c->pending.bar_take_over();
     c->ahead.valid = false;
     SPHX_HIP(c, hipSetDevice(c->device));
     const uint32_t n = c->N;
     if (!n || !c->gdyn.len() || c->boundary_changed || c->need_expand || c->need_recover || c->recover_streak || c->tails_dirty) return SPHX_OK;
     drop_class_count(c);
-    if (c->count_done && c->count_n == n) return SPHX_OK;  // counted already by the packing pass; a deferred advection stays deferred
+    if (c->pending.is_for(n)) return SPHX_OK;  // counted already by the packing pass; a deferred advection stays deferred
     flush_pending_advect(c);
     drop_fused_count(c);
     launch(c, "cell_count", (8.0 + 4 + 4) * n, [&] {
         hipLaunchKernelGGL(k_key_count<false>, dim3(std::max(1u, nblocks(n))), dim3(256), 0, c->stream, PVr{nullptr, nullptr}, (const float2*)c->posA, n, 0.0f,
                            c->K, c->gdyn.view(), c->gdyn.hist, c->key, c->slot, 1u, c->d_scal, 0u);
     });
-    c->count_done = true;
-    c->count_n = n;
+    c->pending.made_by_pack(n);
     return SPHX_OK;
 }
 
@@ -2667,10 +2580,8 @@ int sphx_tile_carry_warmstart(sphx_ctx* c, int kappa, int stiffness) {
 
 int sphx_sub_nonpressure(sphx_ctx* c, float dt_prev, float* out_vmax_sq) {
     if (!c || !out_vmax_sq) return SPHX_ERR_INVALID_ARGUMENT;
-    c->tile_class_done = false;
     const bool ahead_ok = c->ahead.queued && c->ahead.valid;
-    c->ahead.valid = false;
-    flush_pending_advect(c);
+    sub_step_enter(c);
     SPHX_HIP(c, hipSetDevice(c->device));
     const uint32_t n = c->N;
     *out_vmax_sq = 0.0f;
@@ -2699,9 +2610,7 @@ int sphx_sub_nonpressure(sphx_ctx* c, float dt_prev, float* out_vmax_sq) {
 
 int sphx_sub_predict(sphx_ctx* c, float dt) {
     if (!c) return SPHX_ERR_INVALID_ARGUMENT;
-    c->tile_class_done = false;
-    c->ahead.valid = false;
-    flush_pending_advect(c);
+    sub_step_enter(c);
     SPHX_HIP(c, hipSetDevice(c->device));
     const uint32_t n = c->N;
     if (n) launch_predict(c, "velocity_prediction", dt);
@@ -2710,15 +2619,10 @@ int sphx_sub_predict(sphx_ctx* c, float dt) {
 
 int sphx_sub_warmstart(sphx_ctx* c, int divergence, float dt) {
     if (!c) return SPHX_ERR_INVALID_ARGUMENT;
-    c->tile_class_done = false;
-    c->ahead.valid = false;
-    flush_pending_advect(c);
-    if (c->div_error_fused) return c->fail(SPHX_ERR_NOT_READY, "warm start after sphx_sub_regrid_div (that pass has zeroed the warm-start values)");
-    if (c->div_warm_fused) {  // sphx_sub_regrid_warm: the neighbour build has applied the divergence loop's warm start
-        c->div_warm_fused = false;
-        if (!divergence) return c->fail(SPHX_ERR_NOT_READY, "sphx_sub_regrid_warm must be followed by the divergence loop");
-        return SPHX_OK;
-    }
+    sub_step_enter(c);
+    if (c->handoff.first_errors_pending()) return c->fail(SPHX_ERR_NOT_READY, "warm start after sphx_sub_regrid_div (that pass has zeroed the warm-start values)");
+    if (c->handoff.take_warm())  // sphx_sub_regrid_warm: the neighbour build has applied the divergence loop's warm start
+        return divergence ? SPHX_OK : c->fail(SPHX_ERR_NOT_READY, "sphx_sub_regrid_warm must be followed by the divergence loop");
     SPHX_HIP(c, hipSetDevice(c->device));
     const uint32_t n = c->N;
     if (!n) return SPHX_OK;
@@ -2748,17 +2652,16 @@ int sphx_sub_predict_iteration(sphx_ctx* c, float dt, double* out_err_sum, uint6
 }
 static int sub_iteration_impl(sphx_ctx* c, int divergence, float dt, int first, double* out_err_sum, uint64_t* out_n_owned, bool with_predict) {
     if (!c || !out_err_sum) return SPHX_ERR_INVALID_ARGUMENT;
-    c->ahead.valid = false;
-    c->tile_class_done = false;
-    flush_pending_advect(c);
+    sub_step_enter(c);
     SPHX_HIP(c, hipSetDevice(c->device));
     const uint32_t n = c->N;
     *out_err_sum = 0.0;
     if (out_n_owned) *out_n_owned = 0;
     if (!n) return SPHX_OK;
-    c->div_warm_fused = false;
-    if (c->div_error_fused && !(divergence && first)) {  // sphx_sub_regrid_div has done a loop's first compute_density_change
-        c->div_error_fused = false;
+    // what a re-grid left is for the first divergence iteration behind it (enqueue_iteration takes it), and for nobody else
+    const bool refused = c->handoff.first_errors_pending() && !(divergence && first);  // sphx_sub_regrid_div has done a loop's first compute_density_change
+    if (refused || !c->handoff.first_errors_pending()) c->handoff.clear();
+    if (refused) {
         ++c->seq, ++c->res_seq;  // (the numbers this iteration would have published under stay taken)
         return c->fail(SPHX_ERR_NOT_READY, "sphx_sub_regrid_div must be followed by the first divergence iteration");
     }
@@ -2781,12 +2684,6 @@ static int sub_iteration_impl(sphx_ctx* c, int divergence, float dt, int first, 
         for (uint32_t k = 0; k < c->tile_npeers; ++k) s.tc.rect[k] = c->tile_peer[k];
     }
     const uint32_t seq = enqueue_iteration(c, s);
-    if (s.drop_count) {  // (the tile-class count was made)
-        c->tile_class_done = true;
-        c->count_from_class = true;
-        c->tile_class_n = n;
-        std::memcpy(&c->tile_class_dt_bits, &dt, 4);
-    }
     if (c->sub_ahead_dt > 0.0f) {
         const float dtn = c->sub_ahead_dt;
         c->sub_ahead_dt = 0.0f;
@@ -2809,9 +2706,7 @@ static int sub_iteration_impl(sphx_ctx* c, int divergence, float dt, int first, 
 
 int sphx_sub_advect(sphx_ctx* c, float dt) {
     if (!c) return SPHX_ERR_INVALID_ARGUMENT;
-    c->tile_class_done = false;
-    c->ahead.valid = false;
-    flush_pending_advect(c);
+    sub_step_enter(c);
     SPHX_HIP(c, hipSetDevice(c->device));
     const uint32_t n = c->N;
     if (n) launch(c, "advect", 24.0 * n, [&] { hipLaunchKernelGGL(k_advect, dim3(nblocks(n)), dim3(256), 0, c->stream, c->posA, (const float2*)c->vel, n, dt); });

@@ -265,7 +265,7 @@ int sphx_state_load(sphx_ctx* c, const void* buf, uint64_t bytes, uint32_t flags
     c->num_divergence_iters = h.s.num_divergence_iters;
     c->set_changed = h.s.set_changed != 0;
     c->in_wcsph = false;
-    c->div_error_fused = c->div_warm_fused = false;
+    c->handoff.clear();
     c->need_expand = c->need_recover = false;  // (they described the particles that were here before)
     c->recover_streak = c->recover_cooldown = 0;
     c->uploaded = true;
