@@ -587,6 +587,16 @@ int sphx_debug_quiet_counts(sphx_ctx* ctx, uint64_t out[2]);
  * SPHX_THIN_GRID=n (workgroups of a thin launch; default 2 048). */
 int sphx_debug_takeover_counts(sphx_ctx* ctx, uint64_t out[3]);
 
+/* Test aid for the rigid-motion form of the non-pressure pass: out[0] = passes queued in the rigid form,
+ * out[1] = of those, the ones that found no mark and stored the uniform acceleration, out[2] = the ones that found a mark and ran
+ * the full pass; cumulative since the context was created.  Waits for the stream.  Switch, read by sphx_create: SPHX_RIGID_SKIP=0
+ * (never: the launches from before) / 1 (at every context size; default: from 4 M particles, where the flags exist) / force
+ * (whatever the hint says). */
+int sphx_debug_rigid_counts(sphx_ctx* ctx, uint64_t out[3]);
+/* Test aid: the acceleration array as the latest non-pressure pass left it, in sorted order — between two DFSPH steps the pass that
+ * ran ahead for the next one.  out_xy holds 2 * N floats.  Waits for the stream. */
+int sphx_debug_download_accel(sphx_ctx* ctx, float* out_xy);
+
 /* ---- Solver trait (solver/mod.rs:12-18) ---------------------------------------------------------------------- */
 /* Solver::clear_cached_data (dfsph.rs:406-412) */
 int sphx_clear_cached(sphx_ctx* ctx);

@@ -643,6 +643,19 @@ class SphxContext:
         self._chk(self.L.sphx_debug_takeover_counts(self.h, out))
         return int(out[0]), int(out[1]), int(out[2])
 
+    def rigid_counts(self):
+        """sphx_debug_rigid_counts -> (non-pressure passes queued in the rigid form, those that found no mark and stored the uniform
+        acceleration, those that found a mark and ran the full pass): cumulative since the context was created."""
+        out = (C.c_uint64 * 3)()
+        self._chk(self.L.sphx_debug_rigid_counts(self.h, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def download_accel(self):
+        """sphx_debug_download_accel -> float32 [N, 2]: accel[] as the latest non-pressure pass left it (sorted order)."""
+        out = np.zeros((self.n, 2), np.float32)
+        self._chk(self.L.sphx_debug_download_accel(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def grid_info(self, which=0):
         """Cell table behind the grid: covered blocks, table entries, directory extent (sphx_grid_info)."""
         out = (C.c_uint32 * 4)()

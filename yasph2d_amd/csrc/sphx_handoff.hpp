@@ -1,6 +1,7 @@
-// sphx_handoff.hpp — what one launch of the host step path promises a later one (sphx_ctx::handoff, sphx_ctx::pending):
-// two value types with one producer side, one taking call per consumer and one reset each.  Plain C++ (no HIP include, no HIP call):
-// tests/handoff_driver.cpp compiles it with the sanitizers and compares it with the loose context members it replaced.
+// sphx_handoff.hpp — what one launch of the host step path promises a later one (sphx_ctx::handoff, sphx_ctx::pending,
+// sphx_ctx::velmarks): value types with one producer side, one taking call per consumer and one reset each.  Plain C++
+// (no HIP include, no HIP call): tests/handoff_driver.cpp compiles it with the sanitizers and compares it with the loose context
+// members it replaced; tests/rigid_record_driver.cpp does the same for VelMarks against a model of the velocity array.
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -100,6 +101,38 @@ class PendingCount {
     Maker maker_ = Maker::Nobody;
     bool takeable_ = false;
     uint32_t n_ = 0, dt_bits_ = 0;
+};
+
+// Rigid motion: the fluid gather of a step's build (k_rank_gather) has compared every velocity it moved with vel_in[0]
+// and left, under the sequence number `tag`, a mark in MarkStripe::vmix_mark wherever one differed.  While this record is valid those
+// marks describe vel[]: nothing queued since can have written a velocity, except thin corrections on their marked path — which the
+// host cannot know of when it queues them; the record keeps the reduction sequence number the (one) thin correction published under,
+// and the consumer reads that iteration's knz_mark words beside the gather's.
+//   made        build_grid, the fluid build inside a single context's step
+//   thin        launch_correct queued a k_correct_thin behind the gather (a second one voids: one knz tag travels)
+//   wrote       anything else that can write a velocity: k_neighbor_build<3>, a warm start, a correction in any other form, the
+//               prediction, an upload, an edit, sphx_state_load, lists_went_stale, a failed call
+//   take        the run-ahead non-pressure launch, once; leaves the record void whatever it finds
+struct VelMarks {
+    bool valid = false, thin_seen = false;
+    uint32_t tag = 0, knz_tag = 0;
+    struct Taken {
+        bool usable, check_knz;
+        uint32_t tag, knz_tag;
+    };
+    void made(uint32_t gather_tag) { *this = VelMarks{true, false, gather_tag, 0u}; }
+    void thin(uint32_t rseq) {
+        if (!valid) return;
+        if (thin_seen) return wrote();
+        thin_seen = true;
+        knz_tag = rseq;
+    }
+    void wrote() { *this = VelMarks{}; }
+    Taken take() {
+        const Taken t{valid, valid && thin_seen, tag, knz_tag};
+        wrote();
+        return t;
+    }
 };
 
 }  // namespace sphx

@@ -196,10 +196,16 @@ struct alignas(128) VmaxStripe {
 // On lines of its own, for the reason VmaxStripe is: a first form kept the word in Stripe's padding, where the plain stores of a
 // disturbed scene's wavefronts met the residual atomics of the same launch — compute_density_error 198.9 -> 253.6 us and
 // compute_density_change 135.9 -> 164.5 us at 16 M, 2500 steps in (profiles/quiet_scene/ab_16M_1M.txt).
+// vmix_mark (rigid motion): the sequence number of the latest fluid gather in which a wavefront of a workgroup with this
+// stripe number moved a velocity whose bits differ from vel_in[0]'s (or found vel_in[0] not finite).  The same scheme: a tag unique to
+// the launch, no reset, an accidental match reads as "mixed".  It shares knz_mark's line: plain stores only, by a kernel (the gather)
+// that runs while nobody reads or writes the other word.
 struct alignas(128) MarkStripe {
     uint32_t knz_mark;
-    uint32_t pad[31];
+    uint32_t vmix_mark;
+    uint32_t pad[30];
 };
+static_assert(sizeof(MarkStripe) == 128, "one stripe, one cache line");
 // Quiet take-over of the density loop: the cell count compute_density_error makes ahead of its correction is
 // speculative — right iff the correction turns out to be the identity — and so are the DF_* flags that count raises.  They wait
 // here, on a line no residual, mark or sticky flag shares, until the thin correction merges them into DevScalars::flags (quiet) or
@@ -218,7 +224,8 @@ struct DevScalars {
     uint32_t loop_done;    // solver loop run by the device (LoopArgs): 0 while it iterates, else the iteration that met the residual test
     uint32_t pad0;
     unsigned long long snap_hi[2], snap_lo[2];  // cumulative residual sums after the iteration with reduction sequence number r at [r & 1]
-    uint32_t pad[18];
+    uint32_t rigid_exits, rigid_marked;  // rigid non-pressure launches that found no mark / a mark (one add per launch; sphx_debug_rigid_counts)
+    uint32_t pad[16];
     Stripe stripe[STRIPES];
     VmaxStripe vstripe[STRIPES];
     MarkStripe mstripe[STRIPES];
@@ -245,6 +252,10 @@ struct Mailbox {
     uint32_t loop_iters;              // ... after this many iterations
     double loop_hist[LOOP_HIST];      // residual sum of iteration k of the running loop at [k % LOOP_HIST] (the host re-derives every decision)
     uint32_t send_counts[MAX_TILE_PEERS];  // sphx_tile_send_counts: landing place of the headers' record counts (host copies, no kernel writes here)
+    // rigid-motion hint: the wavefront that judges the marks for a non-pressure pass (k_nonpressure_rigid's workgroup 0,
+    // k_rigid_judge) writes the gather's tag here when no stripe carries a mark, else 0.  Read behind the seq of the kernel queued
+    // behind the pass (the velocity prediction publishes its maximum).
+    uint32_t rigid_tag;
 };
 
 // A solver loop (dfsph.rs:195-247 / :346-402) whose termination test runs on the device: the last workgroup of compute_error
@@ -411,6 +422,25 @@ struct sphx_ctx {
         return !tile_mode && (divergence || quiet_takeover_density) && (quiet_takeover == 2 || (quiet_takeover == 1 && quiet_hint[divergence ? 1 : 0]));
     }
     unsigned long long thin_launches = 0, takeover_producers = 0;  // sphx_debug_takeover_counts
+    // Rigid motion: while every fluid velocity carries the bits of vel[0] the XSPH / viscosity sum of the non-pressure
+    // pass adds exact zeros, and the pass is a fill (k_nonpressure_rigid).  SPHX_RIGID_SKIP=0: never (the parent's launches); 1: at
+    // every size; -1: by size, where the flags exist (4 M); force = 2: whatever the hint says (test aid — both forms compute the same bits).
+    int rigid_skip = -1;
+    bool rigid_on() const { return !tile_mode && (rigid_skip < 0 ? N >= 4000000u : rigid_skip != 0); }
+    // What the latest fluid gather's marks say about vel[] (sphx_handoff.hpp).  made: build_grid; thin: launch_correct; wrote: every
+    // launch or entry point that can write a velocity behind the gather; take: enqueue_run_ahead.
+    sphx::VelMarks velmarks;
+    uint32_t gather_seq = 0;       // sequence number of the fluid gathers that write marks (never 0)
+    // The hint (quiet_hint's pattern): the latest judged non-pressure launch found no mark.  rigid_judged: the tag of a judged launch
+    // whose report the next sphx_step_begin_law reads from the mailbox.  Dropped by whatever drops quiet_hint.
+    bool rigid_hint = false;
+    uint32_t rigid_judged = 0;
+    void rigid_forget() {
+        velmarks.wrote();
+        rigid_hint = false;
+        rigid_judged = 0;
+    }
+    unsigned long long rigid_launches = 0;     // non-pressure passes queued in the rigid form (sphx_debug_rigid_counts)
     float2* accel = nullptr;                   // [N]
     float *density = nullptr, *alpha = nullptr, *alpha2 = nullptr, *kappa = nullptr, *stiff = nullptr;  // [N]
     float *kappa2 = nullptr, *stiff2 = nullptr;  // gather targets (tile mode only)
@@ -540,6 +570,7 @@ struct sphx_ctx {
 
     int fail(int code, const char* what, const char* detail = nullptr) {
         quiet_hint[0] = quiet_hint[1] = false;  // (a failed call: the next corrections decide behind the head again)
+        rigid_forget();
         err = what;
         if (detail) {
             err += ": ";

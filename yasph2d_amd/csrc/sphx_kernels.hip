@@ -845,6 +845,10 @@ struct GatherArgs {
     // so "previous index" means something else on every tile)
     uint32_t rank_by_id;
     uint32_t nt_cold;  // Consts::nt_cold
+    // Rigid motion (!= 0: the fluid build inside a single context's step, this gather's sequence number): a wavefront that
+    // moves a velocity whose bits differ from vel_in[0]'s — or finds vel_in[0] not finite — stores the number into
+    // MarkStripe::vmix_mark of its workgroup's stripe (knz_store's scheme).  -0 against +0 and anything against a NaN count as different.
+    uint32_t vmix_tag;
 };
 #ifndef SPHX_GATHER_PER_LANE
 #define SPHX_GATHER_PER_LANE 1
@@ -865,6 +869,9 @@ __global__ __launch_bounds__(256) void k_rank_gather(const uint32_t* __restrict_
     // (profiles/r05_experiments/regrid.txt).
     const uint32_t b0 = xcd_bid(xcd_packed_rev(rev), xcd_packed_shift(rev)) * (256u * GATHER_PER_LANE);  // (rev: xcd_pack)
     if (b0 >= n) return;
+    uint2 vref = make_uint2(0u, 0u);  // (vmix_tag: the reference velocity's bits, one scalar load per workgroup)
+    if (a.vmix_tag) vref = *(const uint2*)a.vel_in;
+    bool vmix = false;
     // The words of order[] around p: a cell holds three or four particles, so the cell mates the ranking below looks at are almost
     // always among them — and so are the two ends of the cell (ORDER_HEAD; round 5: the cell index of the record and the cell's range
     // in the fine table — two dependent round trips and 4 + 2.5 bytes of HBM traffic per particle — are only fetched by a lane whose
@@ -971,6 +978,7 @@ __global__ __launch_bounds__(256) void k_rank_gather(const uint32_t* __restrict_
                 qd.y = qd.y + v[u].y * a.advect_dt;
             }
             a.vel_out[dst] = v[u];
+            vmix = vmix || __float_as_uint(v[u].x) != vref.x || __float_as_uint(v[u].y) != vref.y;
         }
         a.pos_out[dst] = qd;
         if (a.r_in) a.r_out[dst] = r1[u];
@@ -989,6 +997,13 @@ __global__ __launch_bounds__(256) void k_rank_gather(const uint32_t* __restrict_
                     atomicAdd(&a.count_owned->stripe[blockIdx.x % STRIPES].owned, (unsigned long long)__popcll(m));
             }
         }
+    }
+    if (a.vmix_tag) {
+        // (an exponent of all ones: infinite or NaN — f (v_j - v_i) would not be a zero.  Belt and braces: a step whose velocities are
+        // not finite fails in sphx_step_begin, on its maximum velocity, before it reaches a gather — no caller and no test gets here)
+        const bool ref_bad = (vref.x & 0x7f800000u) == 0x7f800000u || (vref.y & 0x7f800000u) == 0x7f800000u;
+        const unsigned long long m = __ballot(vmix || ref_bad);
+        if (m && (threadIdx.x & 63) == (uint32_t)(__ffsll((long long)__ballot(1)) - 1)) a.flags->mstripe[blockIdx.x % STRIPES].vmix_mark = a.vmix_tag;
     }
 }
 
@@ -2591,71 +2606,83 @@ __global__ NONP_BOUNDS void k_nonpressure(PVr PV, const float* __restrict__ dens
                                                       ViscArg<VM> V) {
     __shared__ Stage<2, 1> rec;  // position, velocity; density
     const uint32_t blk = xcd_bid(K.rev, K.xcd_shift);
-    const uint32_t i = blk * 256 + threadIdx.x;
-    NbHead h = nb_head(nb, blk, i, n);
-    struct StageRec {
-        float4 pv;
-        float rho;
-    };
-    nb_stage(
-        h, nb, blk, i, n, [&](uint32_t g) { return StageRec{ldpv(PV, g), gat(density, g < soff ? g : 0u)}; },  // density[] has no boundary tail (XSPH: dynamic neighbours only, dfsph.rs:456)
-        [&](uint32_t g) {
-            const Pair<float4> pv = ldpv2(PV, g);
-            const Pair<float> rho = gat2(density, g < soff ? g : 0u);  // (a pair that straddles soff: the second record is a boundary particle's, its density is not used)
-            return Pair<StageRec>{StageRec{pv.a, rho.a}, StageRec{pv.b, rho.b}};
-        },
-        [&](uint32_t slot, const StageRec& r) {
-            rec.put_vec01(slot, r.pv);
-            rec.put_scal<0>(slot, r.rho);
-        });
-    __syncthreads();
-    float vsq = 0.0f;
-    if (i < n) {
-        const uint32_t oi = (i - h.lw0) * 4u;
-        const float4 pvi = h.wide ? ldpv(PV, i) : rec.vec01(oi);
-        const uint32_t cd = h.cd;
-        float ax = K.ax, ay = K.ay;
-        struct Rec {
-            float4 pv;
-            float rho;
-        };
-        if constexpr (VM == SPHX_VISCOSITY_PHYSICAL) {
-            // the same walk with r = sqrt(r_sq) (dfsph.rs:461): only ALU is added, the staged record already holds everything
-            const float mu_m = V.mu * K.mass;
-            auto walk = [&](auto fast) {
-                auto consume = [&](const Rec& r, uint32_t) {
-                    const float dx = r.pv.x - pvi.x, dy = r.pv.y - pvi.y;
-                    const float r_sq = dx * dx + dy * dy;
-                    const float f = physical_visc(K, V, mu_m, sqrt_dist<decltype(fast)::value>(r_sq), r.rho);
-                    ax = ax + f * (r.pv.z - pvi.z);
-                    ay = ay + f * (r.pv.w - pvi.w);
-                };
-                nb_traverse(
-                    h, cd, [&](uint32_t o) { return Rec{rec.vec01(o), rec.scal<0>(o)}; },
-                    [&](uint32_t g) { return Rec{ldpv(PV, g), gat(density, g)}; }, consume);
-            };
-            if (K.q_noclamp)  // (kernel argument: a scalar branch; sqrt_dist)
-                walk(std::true_type{});
-            else
-                walk(std::false_type{});
-        } else {
-            const float em = K.xsph_eps * K.mass;
-            auto consume = [&](const Rec& r, uint32_t) {
-                const float dx = r.pv.x - pvi.x, dy = r.pv.y - pvi.y;
-                const float r_sq = dx * dx + dy * dy;
-                const float f = em * poly6_eval(K, r_sq) / (r.rho * dt);
-                ax = ax + f * (r.pv.z - pvi.z);
-                ay = ay + f * (r.pv.w - pvi.w);
-            };
-            nb_traverse(
-                h, cd, [&](uint32_t o) { return Rec{rec.vec01(o), rec.scal<0>(o)}; },
-                [&](uint32_t g) { return Rec{ldpv(PV, g), gat(density, g)}; }, consume);
-        }
-        accel[i] = make_float2(ax, ay);
-        const float px = pvi.z + ax * dt, py = pvi.w + ay * dt;
-        vsq = tile_owns(K, pvi.x, pvi.y) ? px * px + py * py : 0.0f;  // ghosts of a tile are somebody else's particles
-    }
+#include "sphx_nonpressure_body.inc"
     block_vmax_add(vsq, scal, vslot, (uint32_t*)&rec.raw[0]);
+}
+
+// Rigid motion.  For a particle whose dynamic neighbours all carry its own velocity bits, finite, every v_j - v_i is
+// +0, every f (v_j - v_i) is +-0 for a finite f, and a + (+-0) = a unless a is -0: the pass above walks the lists to store K.a.  The
+// fluid gather (k_rank_gather, GatherArgs::vmix_tag) has compared every velocity it moved with vel_in[0]; the only launch that can
+// have written one since is a thin correction on its marked path, which then carries its iteration's knz_mark.  The host queues this
+// form only with K.a finite and not -0, the lists current (K.q_noclamp: every kernel value finite), finite model constants and no tile.
+struct RigidArgs {
+    uint32_t vmix_tag;   // the gather's sequence number (MarkStripe::vmix_mark)
+    uint32_t knz_tag;    // check_knz: the reduction sequence number of the thin correction queued behind the gather (MarkStripe::knz_mark)
+    uint32_t check_knz;
+    uint32_t vgrid;      // blocks of the full grid
+    Mailbox* mb;         // Mailbox::rigid_tag
+};
+// Called by a whole wavefront: some stripe carries a mark — or dt is not a step for which f = em W / (rho_j dt) stays finite
+// (rho_j >= rho0: a denormal rho0 dt could make it infinite, and inf * 0 is NaN).  The host tests the same where it knows dt.
+__device__ __forceinline__ bool rigid_marked(const DevScalars* __restrict__ scal, float rho0, float dt, const RigidArgs& ra) {
+    uint32_t vm = ~ra.vmix_tag, km = ~ra.knz_tag;
+    if ((threadIdx.x & 63u) < STRIPES) {  // plain loads: the marks were left by kernels that have finished
+        vm = scal->mstripe[threadIdx.x & 63u].vmix_mark;
+        km = scal->mstripe[threadIdx.x & 63u].knz_mark;
+    }
+    const float rd = rho0 * dt;
+    const bool dt_ok = dt > 0.0f && dt <= 3.402823466e38f && rd >= 1.175494351e-38f && rd <= 3.402823466e38f;
+    return __any(vm == ra.vmix_tag || (ra.check_knz != 0u && km == ra.knz_tag)) != 0 || !dt_ok;
+}
+// The rigid form of the pass: min(vgrid, 2 048) workgroups stand for the vgrid blocks of the full grid, k_correct_thin's shape.  Each
+// looks at the 64 mark words once.  No mark: accel[i] = K.a for its blocks' particles, and one lane adds |v_ref + K.a dt|^2 — today's
+// operations on v_ref = vel[0], the velocity of every particle — to the max-velocity reduction; no list word, window or density is
+// requested.  A mark: today's body over its blocks, with a barrier between two blocks for the staged records.  Workgroup 0 reports
+// what it saw (Mailbox::rigid_tag: the hint for the next step's launch; DevScalars::rigid_exits / rigid_marked).
+template <int VM>
+__global__ NONP_BOUNDS void k_nonpressure_rigid(PVr PV, const float* __restrict__ density, uint32_t n, uint32_t soff, Consts K,
+                                                            float dt, NbView nb, float2* __restrict__ accel, DevScalars* __restrict__ scal, uint32_t vslot,
+                                                            ViscArg<VM> V, RigidArgs ra) {
+    __shared__ Stage<2, 1> rec;  // position, velocity; density
+    uint32_t* const wm = (uint32_t*)&rec.raw[0];  // (the verdict travels through the staging area: not a byte of LDS more, block_vmax_add)
+    if (threadIdx.x < 64) {
+        const bool m = rigid_marked(scal, K.rho0, dt, ra);
+        if (threadIdx.x == 0) wm[0] = m ? 1u : 0u;
+    }
+    __syncthreads();
+    const bool marked = wm[0] != 0u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        __hip_atomic_store(&ra.mb->rigid_tag, marked ? 0u : ra.vmix_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        atomicAdd(marked ? &scal->rigid_marked : &scal->rigid_exits, 1u);
+    }
+    if (!marked) {
+        const float2 a = make_float2(K.ax, K.ay);
+        for (uint32_t vblk = blockIdx.x; vblk < ra.vgrid; vblk += gridDim.x) {
+            const uint32_t i = xcd_map(vblk, ra.vgrid, K.rev, K.xcd_shift) * 256u + threadIdx.x;
+            if (i < n) accel[i] = a;
+        }
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            const float2 v = PV.vel[0];
+            const float px = v.x + a.x * dt, py = v.y + a.y * dt;
+            const uint32_t m = __float_as_uint(px * px + py * py);  // (a single context owns every particle: tile_owns)
+            if (m) atomicMax(&scal->vstripe[0].vmax[vslot & 3u], m);
+        }
+        return;
+    }
+    uint32_t vbits = 0u;  // max |v + a dt|^2 over the workgroup's blocks, as bits (block_vmax_add)
+    for (uint32_t vblk = blockIdx.x; vblk < ra.vgrid; vblk += gridDim.x) {
+        __syncthreads();  // (the verdict has been read; the walk of the block before reads the records this block stages)
+        const uint32_t blk = xcd_map(vblk, ra.vgrid, K.rev, K.xcd_shift);
+#include "sphx_nonpressure_body.inc"
+        vbits = max(vbits, __float_as_uint(vsq));
+    }
+    block_vmax_add(__uint_as_float(vbits), scal, vslot, wm);
+}
+// The marks judged for a pass queued in today's form (the record is valid, the hint is not): one wavefront reports what the rigid
+// form would have seen, so that the next step's launch can be rigid.
+__global__ __launch_bounds__(64) void k_rigid_judge(const DevScalars* __restrict__ scal, float rho0, float dt, RigidArgs ra) {
+    const bool marked = rigid_marked(scal, rho0, dt, ra);
+    if (threadIdx.x == 0) __hip_atomic_store(&ra.mb->rigid_tag, marked ? 0u : ra.vmix_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // a12: dfsph.rs:484-492 — vel[] becomes the predicted velocity (the old velocity is dead from here on, dfsph.rs:524).

@@ -600,7 +600,8 @@ void sub_step_enter(sphx_ctx* c) {
 // update x += v* dt is fused into the first kernel.  5 launches.
 // tile_n != nullptr (multi-GPU tile re-grid): `n` is an upper bound that includes dropped (NaN) slots; the number of particles
 // that actually received a cell is published to the mailbox under the sequence number returned through *tile_n.
-int build_grid(sphx_ctx* c, Grid& g, const float2* pos, uint32_t n, const GatherArgs& ga, float advect_dt, bool ring, uint32_t* tile_n = nullptr) {
+int build_grid(sphx_ctx* c, Grid& g, const float2* pos, uint32_t n, const GatherArgs& ga, float advect_dt, bool ring, uint32_t* tile_n = nullptr,
+               bool mark_velocities = false) {
     hipStream_t st = c->stream;
     DevScalars* ds = c->d_scal;
     const uint32_t len = g.len();
@@ -609,6 +610,7 @@ int build_grid(sphx_ctx* c, Grid& g, const float2* pos, uint32_t n, const Gather
     // tile path: the packing pass or sphx_tile_count_kept has counted the first so many particles while the halo exchange was in flight
     const bool partial = &g == &c->gdyn && tile_n && advect_dt == 0.0f && !counted && c->pending.is_for_first_of(n);
     const uint32_t first = partial ? c->pending.n() : 0u;
+    if (&g == &c->gdyn) c->velmarks.wrote();  // (the gather below moves every velocity: an earlier gather's marks describe the old array)
     if (counted || partial)
         c->pending.forget();  // consumed: k_scatter counts the histogram back down to zero, as behind any count (the scan leaves it as it is)
     else
@@ -668,11 +670,18 @@ int build_grid(sphx_ctx* c, Grid& g, const float2* pos, uint32_t n, const Gather
         if (ga.r2_in) gbytes += 8;
         if (ga.r3_in) gbytes += 8;
         if (ga.u_in) gbytes += 8;
+        // rigid motion (mark_velocities: update_neighborhood's decision): the gather says which velocities differ from vel_in[0] (VelMarks)
+        GatherArgs gm = ga;
+        if (mark_velocities && &g == &c->gdyn && !tile_n && ga.vel_in) {
+            if (++c->gather_seq == 0) c->gather_seq = 1;  // 0 is what fresh mark words hold
+            gm.vmix_tag = c->gather_seq;
+        }
         if (ng)
             launch(c, "gather_attributes", gbytes * ng, [&] {
                 hipLaunchKernelGGL(k_rank_gather, dim3(gb2), dim3(256), 0, st, (const uint32_t*)c->order, (const uint32_t*)c->key, ng, n,
-                                   (const uint2*)g.fine, ga, tile_n ? (const uint32_t*)&ds->sort_total : (const uint32_t*)nullptr, g.cbits(), xcd_pack(c->K.rev, xcd_shift_of(c)));
+                                   (const uint2*)g.fine, gm, tile_n ? (const uint32_t*)&ds->sort_total : (const uint32_t*)nullptr, g.cbits(), xcd_pack(c->K.rev, xcd_shift_of(c)));
             });
+        if (ng && gm.vmix_tag) c->velmarks.made(gm.vmix_tag);
     }
     return SPHX_OK;
 }
@@ -726,6 +735,7 @@ static inline void lists_went_stale(sphx_ctx* c) {
     c->K.q_noclamp = 0u;
     c->lists_current = false;
     c->quiet_hint[0] = c->quiet_hint[1] = false;  // (another scene, for all the corrections know)
+    c->rigid_forget();
     if (c->d_scal) hipMemsetAsync(&c->d_scal->spec.flags, 0, sizeof(uint32_t), c->stream);  // (... and no speculative flag of the old one)
     // (a caller that has already dropped the sampling state keeps its own, more specific message)
     if (c->sample_ready) sample_went_stale(c, "the positions changed since the last neighbour build: run a step, or sphx_update_neighborhood + sphx_update_densities");
@@ -940,7 +950,14 @@ int update_neighborhood(sphx_ctx* c, bool extra_alpha, float advect_dt, bool fus
             flush_pending_advect(c);
         }
     }
-    if ((rc = build_grid(c, c->gdyn, c->posA, c->N, ga, advect_dt, true, c->tile_mode ? &tile_n : nullptr))) return rc;
+    // Take-over of the divergence loop (below): the fused build stores the warm-start sums and the loop's first correction is thin.
+    // Decided here, once, because the gather's marks (rigid motion) are worth writing exactly where that correction follows: no warm
+    // start in front of the loop, nothing but a thin correction between the gather and the run-ahead pass.  A disturbed scene has no
+    // quiet hint, so its gather writes no mark (250 k wavefronts storing into 32 lines: +5 ... +9 us per step at 16 M, 2500 steps in,
+    // profiles/rigid_skip/ab_16M_1M.txt).
+    const bool take_div = fuse && fuse_div && !fuse_warm && zero_skip_flags(c) && c->take_over(true);
+    if ((rc = build_grid(c, c->gdyn, c->posA, c->N, ga, advect_dt, true, c->tile_mode ? &tile_n : nullptr, take_div && advect_dt > 0.0f && c->rigid_on())))
+        return rc;
     if (carry_kappa) std::swap(c->kappa, c->kappa2);
     if (carry_stiff) std::swap(c->stiff, c->stiff2);
     std::swap(c->vel, c->vel2);
@@ -965,6 +982,7 @@ int update_neighborhood(sphx_ctx* c, bool extra_alpha, float advect_dt, bool fus
             dv.lim = -0.5f * c->K.rho0 * c->K.rho0;
             launch(c, "neighbor_build+density_alpha+divergence_warmstart", (8.0 + list_bytes(c) + 8.0 + 8.0 + 8.0 + 4.0) * n, [&] { go(k_neighbor_build<3>, dv); });
             c->handoff = BuildHandoff::warm_applied();
+            c->velmarks.wrote();  // (the warm start corrects velocities behind the gather)
         } else if (fuse && fuse_div) {
             DivArgs dv{};
             dv.vel = (const float2*)c->vel;
@@ -975,7 +993,7 @@ int update_neighborhood(sphx_ctx* c, bool extra_alpha, float advect_dt, bool fus
             dv.knz_tag = c->res_seq + 1u;
             // take-over: the loop's first correction stores 0 + k into the stiffness whatever path it takes, and nothing reads the
             // array between this build and that correction — under the quiet hint the build stores it, and the correction can be thin
-            const bool take = dv.knz && c->take_over(true);
+            const bool take = take_div;
             if (take) {
                 dv.warm = c->stiff;
                 c->takeover_producers += 1;
@@ -1077,6 +1095,7 @@ inline bool device_loop(const sphx_ctx* c) { return !c->tile_mode && !c->host_lo
 // v* = v + a dt (dfsph.rs:484-492).  va / tl: the kernel reads the non-pressure pass's maximum and derives dt itself (sphx_step_begin_law).
 void launch_predict(sphx_ctx* c, const char* label, float dt, const VmaxArgs& va = VmaxArgs{}, const TimerLaw& tl = TimerLaw{}) {
     const uint32_t n = c->N;
+    c->velmarks.wrote();
     launch(c, label, 24.0 * n, [&] { hipLaunchKernelGGL(k_predict, dim3(nblocks(n)), dim3(256), 0, c->stream, c->vel, (const float2*)c->accel, n, dt, c->d_scal, va, tl); });
 }
 
@@ -1088,6 +1107,7 @@ void launch_compute_error(sphx_ctx* c, bool divergence, float dt, const float* d
                           const CountArgs& take_count = CountArgs{}) {
     const uint32_t n = c->N;
     const double lb = list_bytes(c);
+    if (pred) c->velmarks.wrote();  // (the prediction folded in: vel2[] becomes the velocities)
     // warm: where a take-over producer stores the warm-start sums 0 + k; take: NoTake{}, or the speculative cell count that goes out with them
     auto go = [&](auto kernel, float* warm, const PredArgs& pa, auto take) {
         hipLaunchKernelGGL(kernel, dim3(nblocks(n)), dim3(256), 0, c->stream, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt,
@@ -1143,6 +1163,8 @@ void launch_correct(sphx_ctx* c, bool divergence, float dt, const float* dt_dev,
     // will be thin, so that every speculative count meets the kernel that confirms or corrects it)
     const bool thin = first && warm_taken && zs.knz && (divergence || ca.hist);
     if ((quiet_first || thin) && c->zero_skip_count) c->qf_launches += 1;
+    // (rigid motion: a thin correction writes velocities only with its iteration's mark set, which the consumer reads; any other form voids)
+    thin ? c->velmarks.thin(ra.rseq) : c->velmarks.wrote();
     if (thin) {
         c->thin_launches += 1;
         const uint32_t vblocks = nblocks(n);
@@ -1173,6 +1195,7 @@ void launch_correct(sphx_ctx* c, bool divergence, float dt, const float* dt_dev,
 // launch() — no label, no profile record, and K.rev / K.xcd_shift / K.nt_cold stay as the launch before it left them.
 void launch_warmstart(sphx_ctx* c, bool divergence, float dt, const float* dt_dev, bool labelled) {
     const uint32_t n = c->N;
+    c->velmarks.wrote();
     const float inv_dt = 1.0f / dt, lim = -0.5f * c->K.rho0 * c->K.rho0;
     auto one = [&](auto kernel, float* warm) {
         hipLaunchKernelGGL(kernel, dim3(nblocks(n)), dim3(256), 0, c->stream, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K, inv_dt,
@@ -1337,11 +1360,43 @@ uint32_t take_vmax_slot(sphx_ctx* c) {
 }
 
 // The non-pressure pass of dfsph.rs:436-477 (accelerations + max |v + a dt_prev|^2 into vmax slot `vslot`).
-void enqueue_nonpressure(sphx_ctx* c, float dt_prev, uint32_t vslot) {
+// marks (the run-ahead launch only): what the latest fluid gather's marks say about vel[] (VelMarks).  With the record usable and the
+// identity's conditions met the pass is judged: queued in the rigid form under the hint (k_nonpressure_rigid reports itself), else in
+// today's form with k_rigid_judge behind it.  A launch that is not judged drops the hint.
+inline bool finite_not_neg_zero(float f) {
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    return std::isfinite(f) && u != 0x80000000u;
+}
+// DESIGN.md §4, "Rigid motion": K.a + (+0) = K.a; every f finite (current lists, a normal rho0 dt, finite model constants)
+inline bool rigid_conditions(const sphx_ctx* c, float dt) {
+    const float rd = c->K.rho0 * dt;
+    const float fc = c->VK.visc_model == SPHX_VISCOSITY_PHYSICAL ? c->VK.mu * c->K.mass * c->VK.vis_nlap * c->K.h : c->K.xsph_eps * c->K.mass * c->K.p6_norm;
+    return c->rigid_on() && c->K.q_noclamp && c->lists_current && finite_not_neg_zero(c->K.ax) && finite_not_neg_zero(c->K.ay) && dt > 0.0f &&
+           std::isfinite(dt) && std::isfinite(rd) && rd >= 1.175494351e-38f && std::isfinite(fc);
+}
+void enqueue_nonpressure(sphx_ctx* c, float dt_prev, uint32_t vslot, const VelMarks::Taken& marks = VelMarks::Taken{}) {
     const uint32_t n = c->N;
+    const bool judged = marks.usable && rigid_conditions(c, dt_prev);
+    const RigidArgs ra{marks.tag, marks.knz_tag, marks.check_knz ? 1u : 0u, nblocks(n), c->mbox_dev};
+    c->rigid_judged = judged ? marks.tag : 0u;
+    if (!judged) c->rigid_hint = false;
+    if (judged && (c->rigid_skip == 2 || c->rigid_hint)) {
+        c->rigid_launches += 1;
+        auto go_rigid = [&](auto kernel, auto visc) {
+            hipLaunchKernelGGL(kernel, dim3(std::min(ra.vgrid, c->thin_grid ? c->thin_grid : 2048u)), dim3(256), 0, c->stream, c->pv(), (const float*)c->density, n,
+                               c->soff(), c->K, dt_prev, c->nbv(), c->accel, c->d_scal, vslot, visc, ra);
+        };
+        // (sweeps = false: the fill ends where the build's sweep ended, which is where the kernel behind it starts)
+        return launch(c, "nonpressure_accel_vmax", 8.0 * n, [&] {
+            if (c->VK.visc_model == SPHX_VISCOSITY_PHYSICAL) return go_rigid(k_nonpressure_rigid<SPHX_VISCOSITY_PHYSICAL>, ViscArg<SPHX_VISCOSITY_PHYSICAL>{c->VK});
+            go_rigid(k_nonpressure_rigid<SPHX_VISCOSITY_XSPH>, ViscArg<SPHX_VISCOSITY_XSPH>{});
+        }, false);
+    }
     auto go = [&](auto kernel, auto visc) {
         hipLaunchKernelGGL(kernel, dim3(nblocks(n)), dim3(256), 0, c->stream, c->pv(), (const float*)c->density, n, c->soff(), c->K, dt_prev, c->nbv(), c->accel,
                            c->d_scal, vslot, visc);
+        if (judged) hipLaunchKernelGGL(k_rigid_judge, dim3(1), dim3(64), 0, c->stream, (const DevScalars*)c->d_scal, c->K.rho0, dt_prev, ra);
     };
     launch(c, "nonpressure_accel_vmax", (16.0 + 8 + 4 + list_bytes(c)) * n, [&] {
         if (c->VK.visc_model == SPHX_VISCOSITY_PHYSICAL) return go(k_nonpressure<SPHX_VISCOSITY_PHYSICAL>, ViscArg<SPHX_VISCOSITY_PHYSICAL>{c->VK});
@@ -1359,7 +1414,7 @@ void enqueue_run_ahead(sphx_ctx* c, float dt, bool publish) {
     c->ahead.seq = 0;
     c->ahead.n = c->N;
     std::memcpy(&c->ahead.dt_bits, &dt, 4);
-    enqueue_nonpressure(c, dt, vslot);
+    enqueue_nonpressure(c, dt, vslot, publish ? VelMarks::Taken{} : c->velmarks.take());  // (publish: a tile sub-step)
     if (publish) {
         c->ahead.seq = ++c->seq;
         hipLaunchKernelGGL(k_publish_vmax, dim3(1), dim3(64), 0, c->stream, c->d_scal, VmaxArgs{1u, vslot, c->mbox_dev, c->ahead.seq});
@@ -1502,6 +1557,26 @@ int sphx_debug_takeover_counts(sphx_ctx* c, uint64_t out[3]) {
     return SPHX_OK;
 }
 
+int sphx_debug_rigid_counts(sphx_ctx* c, uint64_t out[3]) {
+    if (!c || !out) return SPHX_ERR_INVALID_ARGUMENT;
+    out[0] = c->rigid_launches;
+    SPHX_HIP(c, hipSetDevice(c->device));
+    SPHX_HIP(c, hipStreamSynchronize(c->stream));
+    uint32_t dev[2] = {0u, 0u};
+    SPHX_HIP(c, hipMemcpy(dev, &c->d_scal->rigid_exits, sizeof(dev), hipMemcpyDeviceToHost));
+    out[1] = dev[0];
+    out[2] = dev[1];
+    return SPHX_OK;
+}
+
+int sphx_debug_download_accel(sphx_ctx* c, float* out_xy) {
+    if (!c || (c->N && !out_xy)) return SPHX_ERR_INVALID_ARGUMENT;
+    SPHX_HIP(c, hipSetDevice(c->device));
+    SPHX_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->N) SPHX_HIP(c, hipMemcpy(out_xy, c->accel, (size_t)c->N * 8, hipMemcpyDeviceToHost));
+    return SPHX_OK;
+}
+
 int sphx_debug_quiet_counts(sphx_ctx* c, uint64_t out[2]) {
     if (!c || !out) return SPHX_ERR_INVALID_ARGUMENT;
     SPHX_HIP(c, hipSetDevice(c->device));
@@ -1552,6 +1627,7 @@ int sphx_create(const sphx_params* params, sphx_ctx** out) {
     if (const char* e = std::getenv("SPHX_ZERO_SKIP_COUNT")) c->zero_skip_count = e[0] == '1';  // (test aid: sphx_debug_correction_counts)
     if (const char* e = std::getenv("SPHX_QUIET_TAKEOVER")) c->quiet_takeover = std::strcmp(e, "force") == 0 ? 2 : (e[0] != '0' ? 1 : 0);  // (0: the A/B switch)
     if (const char* e = std::getenv("SPHX_QUIET_TAKEOVER_DENSITY")) c->quiet_takeover_density = e[0] != '0';  // (0: divergence loop only — the per-part A/B)
+    if (const char* e = std::getenv("SPHX_RIGID_SKIP")) c->rigid_skip = std::strcmp(e, "force") == 0 ? 2 : (e[0] != '0' ? 1 : 0);  // (0: the A/B switch; unset: from 4 M particles)
     if (const char* e = std::getenv("SPHX_THIN_GRID")) c->thin_grid = (uint32_t)std::max(0, std::atoi(e));  // (test aid: small scenes run the block loop)
     if (const char* e = std::getenv("SPHX_FUSE_WARM")) c->fuse_warm = e[0] != '0';  // (A/B: the divergence warm start as a walk of its own behind k_neighbor_build<1>)
     c->P = *params;
@@ -1742,6 +1818,7 @@ int sphx_set_boundary(sphx_ctx* c, const float* xy, uint32_t n) {
     }
     c->h_boundary.assign(xy, xy + 2 * (size_t)n);
     c->quiet_hint[0] = c->quiet_hint[1] = false;
+    c->rigid_forget();
     c->boundary_changed = true;  // fluidparticleworld.rs:194 (the static grid is rebuilt lazily, :247-252)
     return ensure_index_scratch(c);
 }
@@ -1920,6 +1997,10 @@ int sphx_step_begin_law(sphx_ctx* c, float dt_prev, const sphx_timer_law* law, f
         c->law_active = true;
     }
     if ((rc = wait_mailbox(c, seq))) return rc;
+    if (c->rigid_judged) {  // the hint for the next non-pressure launch: the judged one (behind this seq on the stream) saw no mark
+        c->rigid_hint = c->mbox->rigid_tag == c->rigid_judged;
+        c->rigid_judged = 0;
+    }
     const uint32_t vbits = c->mbox->vmax_sq_bits;
     float vsq;
     std::memcpy(&vsq, &vbits, 4);
@@ -1963,6 +2044,7 @@ int sphx_step_finish(sphx_ctx* c, float dt, sphx_step_stats* out) {
         drop_fused_count(c);  // (a count of the next build made by this step's density correction: that build does not come)
         c->ahead.valid = false;
         c->handoff.clear();
+        c->rigid_forget();
         c->law_active = false;
         return code;
     };
