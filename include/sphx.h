@@ -65,7 +65,9 @@ extern "C" {
                             *    sphx_track_status, SPHX_TRACK_*
                             * 5 (additive): sphx_particle_fields, sphx_fields_out, SPHX_FIELDS_DEVICE_POINTERS
                             * 5 (additive): sphx_fluid_stats, sphx_stats_record / _get_status / _read, sphx_stats_rec, sphx_stats_frame,
-                            *    sphx_stats_status, SPHX_STATS_* */
+                            *    sphx_stats_status, SPHX_STATS_*
+                            * 5 (additive): sphx_multi_append, sphx_multi_remove, sphx_tile_remove_mark / _fetch, sphx_tile_append,
+                            *    sphx_tile_grow */
 
 /* ---- status codes ---- */
 enum {
@@ -323,7 +325,8 @@ int sphx_render(sphx_ctx* ctx, const sphx_render_view* view, uint32_t flags, con
  *     step or sphx_update_neighborhood + sphx_update_densities); sphx_render and sphx_download work at once on the new set.
  *   Refusals: SPHX_ERR_NOT_READY between a step_begin and its step_finish (either solver) and before the first sphx_upload (an upload of
  *     zero particles counts); SPHX_ERR_INVALID_ARGUMENT on a tile context (sphx_tile_*, sphx_multi_tile_ctx: it holds ghosts) and in
- *     tiling-invariant mode (sphx_set_tiling_invariant).  sphx_multi_* has no counterpart.
+ *     tiling-invariant mode (sphx_set_tiling_invariant).  A tiled run is edited through sphx_multi_append / sphx_multi_remove ("emitting
+ *     and draining fluid in a tiled run" below), which work in either mode.
  * Cost: sphx_remove reads 8 bytes per particle for the predicate and moves 40 bytes per survivor only when something goes; one 4-byte
  * count comes back to the host (the call's only synchronisation).  sphx_append copies the new records and nothing else while they fit. */
 typedef struct sphx_rect { float x0, y0, x1, y1; } sphx_rect; /* [x0, x1) x [y0, y1) in world units */
@@ -1017,6 +1020,63 @@ int sphx_multi_state_load(sphx_multi* m, const void* const* parts /* host */, co
 int sphx_multi_state_digest(sphx_multi* m, uint64_t* out /* [SPHX_MULTI_STATE_SECTIONS]: the whole run; collective in rank mode */);
 int sphx_multi_state_save_file(sphx_multi* m, const char* path); /* rank mode: path + ".rRRRofWWW" */
 int sphx_multi_state_load_file(sphx_multi* m, const char* path); /* the one file, or the complete set of part files */
+
+/* ---- emitting and draining fluid in a tiled run (csrc/sphx_multi_edit.inc, csrc/sphx_multi_edit.hpp, csrc/sphx_tiles.cpp) ---------------------
+ * sphx_append / sphx_remove for a sphx_multi: an inflow, an outflow or a keep-box without the round trip sphx_multi_download, edit on the
+ * host, sphx_multi_upload (36 bytes per particle over PCIe, a fresh decomposition on every rank, renumbered ids, warm-start sums and
+ * iteration counts lost).  Both calls are COLLECTIVE in rank mode: every rank calls with the same arguments.  The contract:
+ *   Predicate and arguments (sphx_multi_remove): exactly sphx_remove's — the same fp32 comparisons, a NaN coordinate is in no rectangle,
+ *     SPHX_REMOVE_OUTSIDE makes the rectangles a keep-box, at most SPHX_REMOVE_MAX_RECTS rectangles; a NaN bound, too many rectangles,
+ *     rects NULL with n_rects > 0 or unknown flag bits: SPHX_ERR_INVALID_ARGUMENT.  The predicate looks at positions only: an owner and
+ *     every tile that holds a ghost of its particle see the same bits, so no tile has to tell another which particles went.
+ *   Remove: every tile retires those of the records it OWNS (bit 31 of its id word) that the predicate removes — position x becomes NaN,
+ *     the form in which the halo exchange already drops a record — and counts them.  A record whose x is NaN already was retired before: it
+ *     is not counted (and no particle with a NaN x is ever counted, whatever SPHX_REMOVE_OUTSIDE says).  The counts are summed over all
+ *     tiles (rank mode: one all-reduce); *out_removed (may be NULL) is that sum, the same on every rank, and whether anything was removed
+ *     is decided from it alone.
+ *       sum == 0: the multi is untouched — no exchange, no re-grid, sphx_multi_info().exchanges unchanged; lists, recorders and a queued
+ *         run-ahead pass stay valid.
+ *       sum > 0: every tile runs one halo exchange and one re-grid (exchanges grows by exactly 1).  The survivors keep position, velocity,
+ *         id, kappa and stiffness bit for bit; density and alpha are recomputed for the whole local set.
+ *   Append: in rank mode every rank is handed the same n_new records, as sphx_multi_upload is.  A non-finite position is
+ *     SPHX_ERR_INVALID_ARGUMENT before anything changes (a NaN x is the retired mark).  Record k gets the id first_id + k, where first_id =
+ *     *out_first_id (may be NULL) = the multi's id counter: n after sphx_multi_upload with ids == NULL, 1 + the greatest id after one with
+ *     ids and after sphx_multi_state_load (1 + the greatest id in the checkpoint); it grows by n_new.  An id at or above 2^31 is
+ *     SPHX_ERR_CAPACITY with nothing changed.  The checkpoint format has no field for the counter: ids are unique among the LIVE particles
+ *     always, and never reused within a run that does not load a checkpoint — after a load, the id of a particle removed before the save may
+ *     be handed out again.  Each record goes to the tile whose rectangle holds its cell under the CURRENT layout (after rebalances), the
+ *     rule of the upload's decomposition; the owner stores it behind its local set with the owner bit, the velocity (vel_xy NULL: zero) and
+ *     kappa = stiffness = +0.0.  A tile whose capacity does not hold its local set, the routed records and the room of one halo exchange
+ *     grows its arrays by half (at least to what is needed), the present records and their warm-start sums copied on the device.  Then every
+ *     tile runs one halo exchange and one re-grid: the ghosts of the new particles appear on the neighbours in that same exchange.
+ *     n_new == 0 leaves the multi untouched and still reports first_id.  The caller's arrays are borrowed for the duration of the call.
+ *   Both calls keep the iteration counts (warm starts), the step count, the layout, the halo width in use and the recorders
+ *     (sphx_multi_stats_record).  sphx_multi_num_owned and the global count are exact after the call (no particle migrates in an edit's
+ *     exchange: positions have not moved since the step's own).  sphx_multi_download, _render, _fluid_stats, _state_save and _state_digest
+ *     work at once on the new set.  No flag is raised: there is no SPHX_FLAG_WARMUP, the re-grid of the exchange is the warm-up block.
+ *   Equivalence: the state after an edit is the state that sphx_multi_state_save, dropping the removed particles from the sections (or
+ *     adding the new records with kappa = stiffness = 0), sphx_multi_state_load leaves in a multi with the same tiling.  In tiling-invariant
+ *     mode with fixed iteration counts every later step is bit-identical to that run's, and the run does not depend on the tiling.  In
+ *     default mode the edit holds the surviving particles bit for bit and the run continues as a valid run of that state (the wording of
+ *     the checkpoint's contract).
+ *   Refusals: SPHX_ERR_NOT_READY between sphx_multi_step_begin and _finish, before the first sphx_multi_upload or sphx_multi_state_load,
+ *     after a load that did not complete and after a failed collective step.  A refused call leaves the multi untouched.
+ *   Limit: the halo buffers keep the capacity the upload estimated from its scene (1.5 x the estimate + 1 024 records, or
+ *     sphx_multi_options.cap_records).  An emitter that fills a send band beyond it raises the halo-capacity condition in the step, as
+ *     a compression wave would; the buffers are not re-sized after an edit — cap_records is the knob.
+ * Cost: a removal reads 12 bytes per local record (id + position) and writes 4 per removed one; one 4-byte count per tile comes back.
+ * Nothing removed: that is all.  Otherwise one halo exchange + re-grid, what a step pays once.
+ * INTERNAL seam (the tile loop, and drivers in the style of tests/tiles_reference.py).  sphx_tile_remove_mark enqueues the pass on the
+ * tile's stream and waits for nothing; sphx_tile_remove_fetch brings the one word back (the pair lets tiles on different devices
+ * overlap).  sphx_tile_append stores owned records (ids below 2^31, finite positions) behind the local set, growing the arrays when they do
+ * not fit; sphx_tile_grow makes room for `capacity` records in all (the halo's room included) ahead of it.  After a fetch that returned
+ * > 0 and after an append the tile is between a halo exchange and its re-grid: sphx_tile_pack_n ... sphx_sub_regrid come next. */
+int sphx_multi_append(sphx_multi* m, const float* pos_xy, const float* vel_xy /* NULL = 0 */, uint32_t n_new, uint32_t* out_first_id /* may be NULL */);
+int sphx_multi_remove(sphx_multi* m, const sphx_rect* rects, uint32_t n_rects, uint32_t flags, uint64_t* out_removed /* may be NULL */);
+int sphx_tile_remove_mark(sphx_ctx* tile_ctx, const sphx_rect* rects, uint32_t n_rects, uint32_t flags);
+int sphx_tile_remove_fetch(sphx_ctx* tile_ctx, uint32_t* out_removed_owned);
+int sphx_tile_append(sphx_ctx* tile_ctx, const float* pos_xy, const float* vel_xy /* NULL = 0 */, const uint32_t* ids, uint32_t n_new);
+int sphx_tile_grow(sphx_ctx* tile_ctx, uint32_t capacity);
 
 /* ---- single-node scalar reductions through POSIX shared memory ---------------------------------------------------------------
  * The three per-step scalars of the tile driver (vmax, two residual sums) already sit in host memory (pinned mailbox) on every

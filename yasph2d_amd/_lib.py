@@ -245,6 +245,12 @@ SIGNATURES = {
     "sphx_multi_state_digest": (_i, [_vp, C.POINTER(_u64)]),
     "sphx_multi_state_save_file": (_i, [_vp, C.c_char_p]),
     "sphx_multi_state_load_file": (_i, [_vp, C.c_char_p]),
+    "sphx_multi_append": (_i, [_vp, _vp, _vp, _u32, C.POINTER(_u32)]),
+    "sphx_multi_remove": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32, C.POINTER(_u64)]),
+    "sphx_tile_remove_mark": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32]),
+    "sphx_tile_remove_fetch": (_i, [_vp, C.POINTER(_u32)]),
+    "sphx_tile_append": (_i, [_vp, _vp, _vp, _vp, _u32]),
+    "sphx_tile_grow": (_i, [_vp, _u32]),
     "sphx_debug_correction_counts": (_i, [_vp, _vp]),
     "sphx_debug_quiet_counts": (_i, [_vp, _vp]),
     "sphx_debug_takeover_counts": (_i, [_vp, _vp]),

@@ -505,6 +505,51 @@ int HipDfsphSolver::remove(FluidParticleWorld& w, const sphx_rect* rects, uint32
     return edit_done(w, sync, sphx_remove(ctx_, rects, n_rects, flags, out_removed));
 }
 
+// ... and behind the multi-GPU solver object: sphx_multi_append / sphx_multi_remove
+int HipDfsphMultiSolver::multi_edit_ready(const FluidParticleWorld& w) {
+    if (!multi_) return last_status = SPHX_ERR_NO_DEVICE;
+    if (uploaded_n_ == (size_t)-1 || w.particles.positions.size() != uploaded_n_ || w.fluid_generation != uploaded_generation_) {
+        last_error = uploaded_n_ == (size_t)-1 ? "append / remove before the solver's first step: the tiles hold no state of this world yet"
+                                                : "the host world was edited since the last step: step (or sync_world) before append / remove";
+        return last_status = SPHX_ERR_NOT_READY;
+    }
+    return SPHX_OK;
+}
+int HipDfsphMultiSolver::multi_edit_done(FluidParticleWorld& w, bool sync, int rc) {
+    if (rc) {
+        last_error = sphx_multi_last_error(multi_);
+        return last_status = rc;
+    }
+    if (sync) {
+        if ((rc = sync_world(w))) {
+            last_error = sphx_multi_last_error(multi_);
+            return last_status = rc;
+        }
+    } else {
+        // the count follows the tiles, the contents are behind them (as after a headless step): the next simulation_step does not upload
+        const size_t n = (size_t)sphx_multi_num_owned(multi_);
+        w.particles.positions.resize(n);
+        w.particles.velocities.resize(n, Vector{0, 0});
+        w.particles.densities.resize(n, 0.0f);
+        w.particles.particle_ids.clear();
+        w.stale_prefix = n;
+        uploaded_n_ = n;
+        uploaded_generation_ = w.fluid_generation;
+    }
+    return last_status = SPHX_OK;
+}
+int HipDfsphMultiSolver::append(FluidParticleWorld& w, const float* pos_xy, const float* vel_xy, uint32_t m, bool sync, uint32_t* out_first_id) {
+    if (int rc = multi_edit_ready(w)) return rc;
+    return multi_edit_done(w, sync, sphx_multi_append(multi_, pos_xy, vel_xy, m, out_first_id));
+}
+int HipDfsphMultiSolver::remove(FluidParticleWorld& w, const sphx_rect* rects, uint32_t n_rects, uint32_t flags, bool sync, uint32_t* out_removed) {
+    if (out_removed) *out_removed = 0;
+    if (int rc = multi_edit_ready(w)) return rc;
+    uint64_t removed = 0;
+    const int rc = sphx_multi_remove(multi_, rects, n_rects, flags, &removed);
+    if (out_removed) *out_removed = (uint32_t)std::min<uint64_t>(removed, 0xFFFFFFFFull);
+    return multi_edit_done(w, sync, rc);
+}
 
 // ---- the run in one file: {SolverFileHeader with the timer's state, the context's blob} -------------------------------------------------
 int HipDfsphSolver::save(const FluidParticleWorld& w, const TimeManager& tm, const char* path) {

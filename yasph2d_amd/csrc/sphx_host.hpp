@@ -192,8 +192,10 @@ class HipDfsphMultiSolver : public HipDfsphSolver {
     void clear_cached_data() override;
     void simulation_step(FluidParticleWorld& fluid_world, TimeManager& time_manager) override;
     int sync_world(FluidParticleWorld& fluid_world) override;
-    int append(FluidParticleWorld&, const float*, const float*, uint32_t, bool, uint32_t*) override { return no_edit(); }
-    int remove(FluidParticleWorld&, const sphx_rect*, uint32_t, uint32_t, bool, uint32_t*) override { return no_edit(); }
+    // sphx_multi_append / sphx_multi_remove on the tiles (the contract is in sphx.h): the world follows as for the single context, with
+    // the count of sphx_multi_num_owned.  *out_removed saturates at 2^32 - 1 (the tiles' own count is 64 bits wide).
+    int append(FluidParticleWorld& fluid_world, const float* pos_xy, const float* vel_xy, uint32_t m, bool sync, uint32_t* out_first_id) override;
+    int remove(FluidParticleWorld& fluid_world, const sphx_rect* rects, uint32_t n_rects, uint32_t flags, bool sync, uint32_t* out_removed) override;
     int save(const FluidParticleWorld&, const TimeManager&, const char*) override { return no_edit("save / load"); }
     int load(FluidParticleWorld&, TimeManager&, const char*) override { return no_edit("save / load"); }
     // The tiled run put down into one file and picked up from it (sphx_solver_multi_checkpoint / _restore in sphx.h): the part(s) of
@@ -203,7 +205,9 @@ class HipDfsphMultiSolver : public HipDfsphSolver {
     sphx_multi* multi() { return multi_; }
 
    private:
-    int no_edit(const char* what = "append / remove") {
+    int multi_edit_ready(const FluidParticleWorld& fluid_world);
+    int multi_edit_done(FluidParticleWorld& fluid_world, bool sync, int rc);
+    int no_edit(const char* what) {
         last_error = std::string(what) + " are not available on the multi-GPU solver";
         return last_status = SPHX_ERR_INVALID_ARGUMENT;
     }

@@ -350,6 +350,10 @@ struct sphx_ctx {
     uint64_t ids_issued = 0;   // particles uploaded or appended since the last sphx_upload: the first id sphx_append hands out
     uint32_t* edit_buf = nullptr;  // sphx_remove: survivors per workgroup, then their exclusive scan and the total; grown on demand
     uint32_t edit_cap = 0;         // ... in 4-byte words
+    // sphx_tile_remove_mark (sphx_multi_edit.inc) shares the buffer: the workgroups' words of the pass in flight, whose total
+    // sphx_tile_remove_fetch reads at edit_buf[edit_mark]; sphx_tile_append stages its records there
+    static constexpr uint32_t MARK_NONE = 0xFFFFFFFFu, MARK_EMPTY = 0xFFFFFFFEu;  // no pass in flight / a pass over zero records
+    uint32_t edit_mark = MARK_NONE;
     // particle tracking (sphx_track_*, sphx_download_by_id: sphx_track.inc).  Belongs to the context, not to the particle state.
     struct Track {
         uint32_t m = 0, unique = 0, log2_bits = 0;  // caller ids, distinct ids, log2 of the filter's bits

@@ -3149,3 +3149,5 @@ __global__ __launch_bounds__(64) void k_publish(DevScalars* scal, Mailbox* mb, u
 #include "sphx_stats.inc"
 // a tiled run's checkpoint, device half: the owned particles compacted into sections with id-keyed digests (kernels + the tile seam)
 #include "sphx_multi_state.inc"
+// an edit of a tiled run, device half: owned records retired by the removal predicate, new owned records behind the local set (kernels + the tile seam)
+#include "sphx_multi_edit.inc"

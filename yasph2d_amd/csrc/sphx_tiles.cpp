@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "../../include/sphx.h"
+#include "sphx_multi_edit.hpp"
 #include "sphx_multi_state_format.hpp"
 #include "sphx_render_merge.hpp"
 #include "sphx_render_window.hpp"
@@ -1086,6 +1087,52 @@ struct TileDriver {
         if (hipSetDevice(device) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return fail(SPHX_ERR_HIP, "waiting for the checkpoint sections");
         return SPHX_OK;
     }
+
+    // sphx_multi_remove, first half: the marking pass over this tile's records goes onto its stream; nothing is waited for
+    int edit_remove_enqueue(const sphx_rect* rects, uint32_t n_rects, uint32_t flags) {
+        const int rc = sphx_tile_remove_mark(ctx, rects, n_rects, flags);
+        if (rc) err = std::string("sphx_tile_remove_mark: ") + sphx_last_error(ctx);  // (an argument or state error of one call: nobody is waiting in an all-reduce)
+        return rc;
+    }
+    // ... second half: the number of owned records the pass retired comes back
+    uint32_t edit_removed = 0;
+    int edit_remove_fetch() {
+        const int rc = sphx_tile_remove_fetch(ctx, &edit_removed);
+        if (rc) err = std::string("sphx_tile_remove_fetch: ") + sphx_last_error(ctx);
+        return rc;
+    }
+    // ... and, once the sum over ALL tiles is known to be positive (the same decision on every tile): the counts follow, and one halo
+    // exchange + re-grid drops the retired records and the ghosts of those that other tiles retired
+    int edit_remove_finish(uint64_t total) {
+        n_owned_local -= std::min<uint64_t>(n_owned_local, edit_removed);
+        n_owned_global -= std::min<uint64_t>(n_owned_global, total);
+        return refresh();
+    }
+    // sphx_multi_append: the records this tile owns under the current layout go behind its local set; then the exchange + re-grid.
+    // owner[k]: the tile of record k (sphx_multi_edit::route, the same on every tile)
+    int edit_append(const float* pos, const float* vel, uint32_t n_new, uint32_t first_id, const std::vector<int>& owner) {
+        std::vector<float> p, v;
+        std::vector<uint32_t> id;
+        for (uint32_t k = 0; k < n_new; ++k) {
+            if (owner[k] != comm->rank) continue;
+            p.push_back(pos[2 * (size_t)k]);
+            p.push_back(pos[2 * (size_t)k + 1]);
+            if (vel) {
+                v.push_back(vel[2 * (size_t)k]);
+                v.push_back(vel[2 * (size_t)k + 1]);
+            }
+            id.push_back(first_id + k);
+        }
+        const uint32_t routed = (uint32_t)id.size();
+        // room for the local set, the routed records and what one exchange appends (sphx_tile_apply_n: cap_now() slots per peer)
+        const uint64_t room = (uint64_t)sphx_num_particles(ctx) + routed + (uint64_t)peers.size() * cap;
+        if (room >= (1ull << 28)) return fail(SPHX_ERR_CAPACITY, "sphx_multi_append: more than 2^28 slots in one tile: use more tiles");
+        TCHK(sphx_tile_grow(ctx, (uint32_t)room));
+        TCHK(sphx_tile_append(ctx, p.data(), vel ? v.data() : nullptr, id.data(), routed));
+        n_owned_local += routed;
+        n_owned_global += n_new;
+        return refresh();
+    }
 };
 
 // which layout for `world` tiles over these particles: 2x2 (2 x N/2) on 4 tiles, strips along the longer side otherwise
@@ -1140,6 +1187,7 @@ struct sphx_multi {
     Layout explicit_layout;
     bool uploaded = false;  // a sphx_multi_upload has succeeded: the contexts are tiles and hold a re-gridded particle set
     bool state_broken = false;  // a sphx_multi_state_load found a digest mismatch after the copy: the multi asks for an upload or a load
+    uint64_t next_id = 0;  // sphx_multi_append: the id the next appended record gets (sphx_multi_edit::counter_after; the same on every rank)
 
     // run f(tile, index) on every tile, each on its own host thread (the tiles meet in barriers); returns the first error
     int each(const std::function<int(TileDriver&, size_t)>& f) {
@@ -1289,6 +1337,7 @@ int sphx_multi_upload(sphx_multi* m, const float* pos_xy, const float* vel_xy, c
     if (!rc) {
         m->uploaded = true;
         m->state_broken = false;
+        m->next_id = sphx_multi_edit::counter_after(ids, n);
     }
     return rc;
 }
@@ -1930,6 +1979,7 @@ int sphx_multi_state_load(sphx_multi* m, const void* const* parts, const uint64_
     if (rc) return broken(rc);
     m->uploaded = true;
     m->state_broken = false;
+    m->next_id = sphx_multi_edit::counter_after(ids.data(), n);
     // what arrived, digested where it now lives
     uint64_t got[7];
     if ((rc = multi_state_pack(m)) || (rc = multi_state_sum(m, true, got))) return broken(rc);
@@ -2002,6 +2052,97 @@ int sphx_multi_state_load_file(sphx_multi* m, const char* path) {
         }
     }
     return sphx_multi_state_load(m, parts.data(), bytes.data(), (uint32_t)parts.size(), 0u);
+}
+
+}  // extern "C"
+
+// ---- emitting and draining fluid in a tiled run (include/sphx.h; the device passes are csrc/sphx_multi_edit.inc) ------------------------------
+extern "C" {
+
+int sphx_multi_remove(sphx_multi* m, const sphx_rect* rects, uint32_t n_rects, uint32_t flags, uint64_t* out_removed) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    if (out_removed) *out_removed = 0;
+    auto bad = [&](const std::string& what) {
+        m->err = "sphx_multi_remove: " + what;
+        return SPHX_ERR_INVALID_ARGUMENT;
+    };
+    // sphx_remove's argument rules, checked here so that a refused call has touched no tile
+    if (n_rects > SPHX_REMOVE_MAX_RECTS) return bad("n_rects is larger than SPHX_REMOVE_MAX_RECTS");
+    if (n_rects && !rects) return bad("rects is NULL with n_rects > 0");
+    if (flags & ~(uint32_t)SPHX_REMOVE_OUTSIDE) return bad("unknown flags bits");
+    for (uint32_t k = 0; k < n_rects; ++k)
+        if (std::isnan(rects[k].x0) || std::isnan(rects[k].y0) || std::isnan(rects[k].x1) || std::isnan(rects[k].y1)) return bad("a rectangle bound is NaN");
+    int rc;
+    if ((rc = multi_state_ready(m, "sphx_multi_remove", true))) return rc;
+    // every local tile enqueues on its own stream and device first, then the counts are collected: the tiles' passes overlap.  A failure
+    // here is this process's own (the arguments and the state rules are the same everywhere): it is kept until the ranks have met
+    int local_rc = SPHX_OK;
+    for (size_t k = 0; k < m->tiles.size() && !local_rc; ++k)
+        if ((local_rc = m->tiles[k]->edit_remove_enqueue(rects, n_rects, flags))) m->err = "tile " + std::to_string(k) + ": " + m->tiles[k]->err;
+    double local = 0.0, total = 0.0;
+    for (size_t k = 0; k < m->tiles.size() && !local_rc; ++k) {
+        if ((local_rc = m->tiles[k]->edit_remove_fetch())) m->err = "tile " + std::to_string(k) + ": " + m->tiles[k]->err;
+        local += (double)m->tiles[k]->edit_removed;
+    }
+    if (m->rank_mode) {
+        // the one collective of the decision, reached by every rank whatever its own count and whether or not its own pass failed (the
+        // second word says so: then every rank returns an error together)
+        TileDriver& t = *m->tiles[0];
+        double in[2] = {local, local_rc ? 1.0 : 0.0}, out[2] = {0.0, 0.0};
+        if ((rc = t.comm->allreduce(in, 2, 0, out))) {
+            m->err = "sphx_multi_remove: the removed counts could not be summed over the ranks";
+            return t.fail(rc, m->err);
+        }
+        if (out[1] > 0.0) {
+            if (!local_rc) m->err = "sphx_multi_remove: another rank's marking pass failed";
+            return local_rc ? local_rc : SPHX_ERR_HIP;  // (every rank has left the all-reduce: nobody is waiting for this one)
+        }
+        total = out[0];
+    } else {
+        if (local_rc) return local_rc;
+        total = local;
+    }
+    const uint64_t removed = (uint64_t)total;
+    if (out_removed) *out_removed = removed;
+    if (removed == 0) return SPHX_OK;  // the multi is as it was
+    return m->each([&](TileDriver& t, size_t) { return t.edit_remove_finish(removed); });
+}
+
+int sphx_multi_append(sphx_multi* m, const float* pos_xy, const float* vel_xy, uint32_t n_new, uint32_t* out_first_id) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    if (n_new && !pos_xy) {
+        m->err = "sphx_multi_append: pos_xy is NULL with n_new > 0";
+        return SPHX_ERR_INVALID_ARGUMENT;
+    }
+    int rc;
+    if ((rc = multi_state_ready(m, "sphx_multi_append", true))) return rc;
+    const uint32_t bad_at = sphx_multi_edit::first_nonfinite(pos_xy, n_new);
+    if (bad_at != n_new) {
+        m->err = "sphx_multi_append: the position of record " + std::to_string(bad_at) + " is not finite (a NaN x is the mark of a retired record)";
+        return SPHX_ERR_INVALID_ARGUMENT;
+    }
+    uint32_t first_id = 0;
+    uint64_t counter = m->next_id;
+    if (!sphx_multi_edit::take_ids(counter, n_new, &first_id)) {
+        if (out_first_id) *out_first_id = first_id;
+        m->err = "sphx_multi_append: a particle id would reach 2^31 (ids are not reused within a run; bit 31 marks the owner inside a tile)";
+        return SPHX_ERR_CAPACITY;
+    }
+    if (out_first_id) *out_first_id = first_id;
+    if (n_new == 0) return SPHX_OK;
+    // the owner of every record under the CURRENT layout (the same on every tile and rank: the layout is)
+    const TileDriver& t0 = *m->tiles[0];
+    std::vector<sphx_multi_edit::CellRect> rects;
+    for (const Rect& r : t0.layout.rects()) rects.push_back(sphx_multi_edit::CellRect{r.x0, r.x1, r.y0, r.y1});
+    std::vector<int> owner;
+    sphx_multi_edit::route(pos_xy, n_new, t0.grid_min, t0.cell_inv, rects.data(), (int)rects.size(), owner);
+    for (uint32_t k = 0; k < n_new; ++k)
+        if (owner[k] < 0) {  // (cannot happen: a layout's rectangles cover the cell range)
+            m->err = "sphx_multi_append: no tile's rectangle holds record " + std::to_string(k);
+            return SPHX_ERR_INVALID_ARGUMENT;
+        }
+    m->next_id = counter;
+    return m->each([&](TileDriver& t, size_t) { return t.edit_append(pos_xy, vel_xy, n_new, first_id, owner); });
 }
 
 }  // extern "C"

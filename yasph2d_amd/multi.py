@@ -208,6 +208,29 @@ class MultiSolver:
         d["transport"] = i.transport.decode()
         return d
 
+    # ---- emitting and draining fluid (the contract is in include/sphx.h, "emitting and draining fluid in a tiled run") ----
+    def append(self, pos, vel=None):
+        """sphx_multi_append: add particles to the tiled run on the device (vel None = zero): each record goes to the tile that owns its
+        cell, one halo exchange + re-grid follows.  Ids, warm-start sums and iteration counts of the run survive. -> the id of the first
+        new particle.  Collective in rank mode (every rank passes the same records)."""
+        from . import _append_arrays
+
+        pos, vel = _append_arrays(pos, vel)
+        first = C.c_uint32()
+        self._chk(self.L.sphx_multi_append(self.h, _p(pos), _p(vel), len(pos), C.byref(first)))
+        return first.value
+
+    def remove(self, rects, outside=False):
+        """sphx_multi_remove: drop the particles inside any of the rectangles (SphxContext.remove's predicate; outside=True: a keep-box)
+        from the tiled run -> the number removed over all tiles.  Nothing removed: the run is untouched; else one halo exchange + re-grid.
+        Collective in rank mode (every rank gets the same count)."""
+        from . import _rect_array
+
+        arr, k = _rect_array(rects)
+        removed = C.c_uint64()
+        self._chk(self.L.sphx_multi_remove(self.h, arr, k, _lib.REMOVE_OUTSIDE if outside else 0, C.byref(removed)))
+        return removed.value
+
     # ---- fluid statistics of the tiled run (the contract is in include/sphx.h, "fluid statistics of a tiled run") ----
     def stats(self, rects=(), per_tile=False):
         """sphx_multi_fluid_stats: the records of SphxContext.stats() over the particles the tiles own, folded over the tiles in ascending
