@@ -67,7 +67,10 @@ extern "C" {
                             * 5 (additive): sphx_fluid_stats, sphx_stats_record / _get_status / _read, sphx_stats_rec, sphx_stats_frame,
                             *    sphx_stats_status, SPHX_STATS_*
                             * 5 (additive): sphx_multi_append, sphx_multi_remove, sphx_tile_remove_mark / _fetch, sphx_tile_append,
-                            *    sphx_tile_grow */
+                            *    sphx_tile_grow
+                            * 5 (additive): sphx_multi_track_set / _fetch / _record / _get_status / _read, sphx_multi_download_by_id,
+                            *    sphx_multi_track_out, sphx_track_merge, sphx_track_merge_frames, sphx_tile_track_install / _fetch_enqueue /
+                            *    _fetch / _window_enqueue / _window_fetch / _record / _frame / _read */
 
 /* ---- status codes ---- */
 enum {
@@ -429,7 +432,8 @@ int sphx_state_load_file(sphx_ctx* ctx, const char* path);
  * When allowed: fetch and sphx_download_by_id wherever sphx_download is, and before any upload (N = 0: everything is absent).  Fetch, read,
  *   sphx_download_by_id, set and record return SPHX_ERR_NOT_READY between a step_begin and its step_finish (either solver).  A tile context
  *   (sphx_tile_*, sphx_multi_tile_ctx) is refused with SPHX_ERR_INVALID_ARGUMENT: it holds ghosts and its ids need not be unique.
- *   sphx_multi_* has NO counterpart: a multi-GPU run is followed through sphx_multi_download.
+ *   sphx_multi_* has NO counterpart that takes a sphx_ctx: THESE calls never serve a tile.  A tiled run is followed through calls of its
+ *   own, sphx_multi_track_* and sphx_multi_download_by_id ("following particles by id in a tiled run" below), not through sphx_multi_download.
  * Argument errors (SPHX_ERR_INVALID_ARGUMENT, the message names the argument): ctx, out or status NULL, every output NULL, ids NULL with
  *   m > 0, m > SPHX_TRACK_MAX_IDS, unknown flag bits.
  * Cost: the look-up streams particle_id[] once (4 bytes per particle; a bit filter in LDS keeps all but ~6 % of the other particles away
@@ -859,6 +863,87 @@ int sphx_multi_stats_record(sphx_multi* m, const sphx_rect* rects /* host */, ui
 int sphx_multi_stats_get_status(const sphx_multi* m, sphx_stats_status* out);
 int sphx_multi_stats_read(sphx_multi* m, uint32_t first_frame, uint32_t n_frames, sphx_stats_rec* out /* host, [n_frames][1 + n_rects] */,
                           sphx_stats_frame* info /* host, [n_frames], may be NULL */);
+/* ---- following particles by id in a tiled run (csrc/sphx_tiles.cpp; device pass csrc/sphx_track.inc, host merge csrc/sphx_track_merge.hpp) ----
+ * sphx_track_* / sphx_download_by_id for a sphx_multi, without sphx_multi_download: every tile streams its particle_id[] once on its own
+ * device and answers for the particles it OWNS; the host folds the tiles' parts.
+ * Rule for one tile: a particle answers for id i iff bit 31 of its particle_id word is set (the tile owns it) and the other 31 bits are i.
+ *   A ghost never answers; an id >= 2^31 is always absent.  Within a tile the HIGHEST slot answers (sphx_track_*'s rule); if several tiles
+ *   hold an id — only a state loaded with repeated ids has that — the greatest (tile rank, slot) wins.
+ * Values: sphx_multi_track_set hands over m ids (host memory, copied; any order; duplicates allowed and answered alike; m == 0 clears the
+ *   set).  sphx_multi_track_fetch gives for the k-th id in the caller's order: tile[k] = the global rank of the tile that owns it, slot[k] =
+ *   its index in that tile's sphx_download order, pos / vel / density = the exact bits that tile's arrays hold — the bits
+ *   sphx_multi_download returns for that id.  An absent id has tile = slot = SPHX_TRACK_ABSENT and the word 0x7FC00000 in every float.  Any
+ *   subset of the outputs gives the same bits.  An empty set is a successful no-op.
+ * sphx_multi_download_by_id: the same for the ids first_id + k, k < count; *out_present = the ids found.  first_id + count may reach 2^32
+ *   and no more; count == 0 is a successful no-op (*out_present = 0).  After an unedited sphx_multi_upload with ids == NULL, first_id = 0
+ *   and count = n give the particles in upload order.  A tile appends one packed 32-byte record per owned particle of the window to a
+ *   buffer sized from its owned count (the order in the buffer is undefined, the scattered result is not): about 32 bytes per particle of
+ *   the window cross the bus in all, not world * count * 28.
+ * In-process (sphx_multi_create): the answer is complete.  Rank mode (sphx_multi_create_rank): every call is LOCAL and communicates
+ *   nothing; it returns this rank's part — an id another rank owns is absent, tile[] says which are present — and every rank must make
+ *   the same set and record calls.  The caller moves the parts with its own transport and folds them with sphx_track_merge /
+ *   sphx_track_merge_frames (the pattern of sphx_multi_render_layer / sphx_render_merge).
+ * sphx_track_merge(m, parts, n_parts, out, out_present): pure host code, no GPU.  Every part is a sphx_multi_track_out of m entries with
+ *   tile and slot present (SPHX_ERR_INVALID_ARGUMENT otherwise, or if out asks for an array a part lacks); entry k of out is taken from
+ *   the part with the greatest (tile[k], slot[k]) among those whose tile[k] is not SPHX_TRACK_ABSENT (equal pairs: the earlier part), or
+ *   is absent.  n_parts == 0 gives an all-absent answer.  sphx_track_merge_frames(n, parts, parts_tile, n_parts, out, out_tile): the same
+ *   for n = n_frames * m frame entries {x, y, vx, vy} and their tile words (the greatest tile wins; out_tile may be NULL).
+ * Recording: after sphx_multi_track_record(max_frames, every) every every-th SUCCESSFULLY finished multi step (sphx_multi_step_finish, and
+ *   each step inside sphx_multi_simulation_step(s); counted from the call) makes every tile enqueue one frame behind that step's kernels:
+ *   per distinct tracked id {x, y, vx, vy} and a presence word (the slot, or SPHX_TRACK_ABSENT — never inferred from the floats: a
+ *   particle may carry 0x7FC00000), 20 bytes.  Nothing comes back to the host and nothing is synchronised; a failed step takes no frame
+ *   and does not count.  max_frames * (distinct ids) * 20 bytes per tile may not exceed 1 GiB (SPHX_ERR_CAPACITY); frames beyond
+ *   max_frames are counted in `dropped`; max_frames == 0 stops and frees; every == 0 is SPHX_ERR_INVALID_ARGUMENT; recording with an
+ *   empty set is SPHX_ERR_NOT_READY.  sphx_multi_track_set and _record discard an earlier recording on every tile or on none.
+ *   sphx_multi_track_read folds the frames [first_frame, first_frame + n_frames) into out[n_frames][m][4] (caller's order, absent = four
+ *   0x7FC00000 words) and out_tile[n_frames][m] (owning tile or SPHX_TRACK_ABSENT; may be NULL); a range beyond `frames` is
+ *   SPHX_ERR_INVALID_ARGUMENT.  A frame equals the sphx_multi_track_fetch made at that moment.
+ * Lifetime: the set and the recording belong to the MULTI.  They survive migration, re-partitioning, sphx_multi_append / _remove (a removed
+ *   id becomes absent, an appended id that is in the set is found), sphx_multi_state_load and sphx_multi_upload (the set keeps its numbers).
+ * When allowed: after the first sphx_multi_upload or sphx_multi_state_load; SPHX_ERR_NOT_READY before it, between sphx_multi_step_begin
+ *   and _finish and on a multi whose collective step has failed.  SPHX_ERR_INVALID_ARGUMENT (sphx_multi_last_error names the argument):
+ *   m > SPHX_TRACK_MAX_IDS, ids NULL with m > 0, out NULL or every pointer in it NULL, any flags bit, first_id + count > 2^32, out of
+ *   sphx_multi_track_read NULL with n_frames > 0.  A refused call touches no tile.
+ * No side effects: only reads.  Every sphx_multi_state_digest word, every sphx_step_stats field and the timer are the same with and without
+ *   a set, fetches, by-id downloads and a recording; a queued run-ahead pass stays valid, the sweep direction is put back.
+ * One tile (INTERNAL, like the other sphx_tile_* calls; a plain context is refused with SPHX_ERR_INVALID_ARGUMENT): sphx_tile_track_install
+ *   takes the tables of ONE track_build (csrc/sphx_track_set.hpp) — the same for every tile; unique == 0 clears — and drops the tile's
+ *   recording.  _fetch_enqueue queues look-up and gather on the tile's stream, _fetch copies back per distinct id the slot word, {x, y, vx,
+ *   vy} and the density.  _window_enqueue(first_id, count <= 2^22, cap_records) queues the append pass into a buffer of cap_records
+ *   records behind one counter; _window_fetch copies counter and records in one transfer, *out_n = records stored; more matches than
+ *   cap_records are never written and reported as SPHX_ERR_CAPACITY.  Record: {id - first_id, slot, x, y, vx, vy, density, 0}.
+ *   _record / _frame / _read are the recorder's seam; a frame of _read is [unique] x 16 bytes, then [unique] presence words.
+ * Cost: per tile 4 bytes per local particle scanned, 24 bytes per distinct id (fetch) or 32 per owned particle of the window back to the
+ *   host; DESIGN.md section 4m. */
+typedef struct sphx_multi_track_out {
+    uint32_t* tile;    /* [m] global tile rank that owns the id, or SPHX_TRACK_ABSENT; or NULL */
+    uint32_t* slot;    /* [m] index in that tile's sphx_download order, or SPHX_TRACK_ABSENT; or NULL */
+    float* pos;        /* [2m] or NULL */
+    float* vel;        /* [2m] or NULL */
+    float* density;    /* [m] or NULL */
+} sphx_multi_track_out;   /* host pointers; not all NULL */
+int sphx_multi_track_set(sphx_multi* m, const uint32_t* ids /* host */, uint32_t n_ids);
+int sphx_multi_track_fetch(sphx_multi* m, uint32_t flags /* 0 */, const sphx_multi_track_out* out);
+int sphx_multi_track_record(sphx_multi* m, uint32_t max_frames, uint32_t every);
+int sphx_multi_track_get_status(const sphx_multi* m, sphx_track_status* out);
+int sphx_multi_track_read(sphx_multi* m, uint32_t first_frame, uint32_t n_frames, uint32_t flags /* 0 */,
+                          float* out /* [n_frames][m][4] */, uint32_t* out_tile /* [n_frames][m], may be NULL */);
+int sphx_multi_download_by_id(sphx_multi* m, uint32_t first_id, uint32_t count, uint32_t flags /* 0 */,
+                              const sphx_multi_track_out* out, uint32_t* out_present /* may be NULL */);
+int sphx_track_merge(uint32_t m, const sphx_multi_track_out* parts, uint32_t n_parts, const sphx_multi_track_out* out, uint32_t* out_present /* may be NULL */);
+int sphx_track_merge_frames(uint64_t n /* n_frames * m */, const float* const* parts /* [n_parts] of [n][4] */, const uint32_t* const* parts_tile /* [n_parts] of [n] */,
+                            uint32_t n_parts, float* out /* [n][4] */, uint32_t* out_tile /* [n], may be NULL */);
+int sphx_tile_track_install(sphx_ctx* tile_ctx, const uint32_t* table /* host, [unique] ascending */, const uint32_t* filter /* host, 2^log2_bits bits */,
+                            uint32_t unique, uint32_t log2_bits);
+int sphx_tile_track_fetch_enqueue(sphx_ctx* tile_ctx);
+int sphx_tile_track_fetch(sphx_ctx* tile_ctx, uint32_t* slot /* host, [unique] */, float* xyvv /* host, [unique][4] */, float* density /* host, [unique] */);
+int sphx_tile_track_window_enqueue(sphx_ctx* tile_ctx, uint32_t first_id, uint32_t count, uint32_t cap_records);
+int sphx_tile_track_window_fetch(sphx_ctx* tile_ctx, uint32_t* records /* host, [4 + 8 * cap_records]: the counter's 16 bytes, then the records */,
+                                 uint32_t* out_n);
+int sphx_tile_track_record(sphx_ctx* tile_ctx, uint32_t max_frames, uint32_t every);
+int sphx_tile_track_frame(sphx_ctx* tile_ctx); /* one finished step: a frame if the recording is due */
+int sphx_tile_track_read(sphx_ctx* tile_ctx, uint32_t first_frame, uint32_t n_frames, float* xyvv /* host, [n_frames][unique][4] */,
+                         uint32_t* slot /* host, [n_frames][unique] */);
 /* Solver::simulation_step(&mut world, &mut time_manager) (solver/mod.rs:17) in ONE call: phase A, the TimeManager mirror
  * (simulation_step() dfsph.rs:433, update_simulation_step dfsph.rs:478-480), phase B */
 struct sphx_timer;

@@ -16,7 +16,7 @@ from ._lib import (FLAG_DENSITY_ITER_CAP, FLAG_DIVERGENCE_ITER_CAP, FLAG_DENSE_C
 
 __all__ = ["SphxContext", "FluidParticleWorld", "TimeManager", "DFSPHSolver", "DFSPHMultiSolver", "default_params", "duration_from_secs_f32",
            "duration_as_secs_f32", "SphxError", "WCSPHSolver", "VISCOSITY_XSPH", "VISCOSITY_PHYSICAL", "SAMPLE_FIELDS", "gauge_elevation",
-           "render_fit", "render_merge", "write_png", "SCENE_RECT", "TRACK_FIELDS", "FIELD_NAMES", "STATS_DTYPE", "STATS_FRAME_DTYPE"]
+           "render_fit", "render_merge", "track_merge", "track_merge_frames", "write_png", "SCENE_RECT", "TRACK_FIELDS", "MULTI_TRACK_FIELDS", "FIELD_NAMES", "STATS_DTYPE", "STATS_FRAME_DTYPE"]
 
 
 def _p(a):
@@ -106,6 +106,73 @@ def _track_struct(outs):
     for f, a in outs.items():
         setattr(o, f, a.ctypes.data or 1)  # (an empty array: a non-NULL dummy still names the field; nothing is written)
     return o
+
+
+MULTI_TRACK_FIELDS = ("tile", "slot", "pos", "vel", "density")  # sphx_multi_track_out
+
+
+def _multi_track_outputs(fields, m):
+    fields = MULTI_TRACK_FIELDS if fields is None else ((fields,) if isinstance(fields, str) else tuple(fields))
+    bad = [f for f in fields if f not in MULTI_TRACK_FIELDS]
+    if bad or not fields:
+        raise ValueError("fields must be a non-empty subset of %s, not %r" % (MULTI_TRACK_FIELDS, fields))
+    return {f: np.zeros((m, 2) if f in ("pos", "vel") else (m,), np.uint32 if f in ("tile", "slot") else np.float32) for f in fields}
+
+
+def _multi_track_struct(outs):
+    o = _lib.SphxMultiTrackOut()
+    for f in MULTI_TRACK_FIELDS:
+        if f in outs:
+            setattr(o, f, outs[f].ctypes.data or 1)  # (an empty array: a non-NULL dummy still names the field; nothing is written)
+    return o
+
+
+def track_merge(parts):
+    """sphx_track_merge: the parts the ranks of one run returned from MultiSolver.track_fetch() or download_by_id() (dicts with "tile",
+    "slot" and the same other fields, all of one length) folded into the answer of the whole run: per id the part that holds it (the
+    greatest (tile, slot) if several do), else absent.  -> the dict of the common fields plus "present".  Host code; no GPU needed."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("track_merge needs at least one part (the number of ids is the parts')")
+    fields = [f for f in MULTI_TRACK_FIELDS if all(f in p for p in parts)]
+    m = len(parts[0]["tile"]) if "tile" in parts[0] else 0
+    kept = []
+    arr = (_lib.SphxMultiTrackOut * len(parts))()
+    for k, p in enumerate(parts):
+        a = {f: np.ascontiguousarray(p[f], np.uint32 if f in ("tile", "slot") else np.float32) for f in fields}
+        if any(a[f].size != m * (2 if f in ("pos", "vel") else 1) for f in fields):
+            raise ValueError("track_merge: the parts differ in length")
+        kept.append(a)
+        for f in fields:
+            setattr(arr[k], f, a[f].ctypes.data or 1)
+    outs = _multi_track_outputs(fields or ("tile",), m)
+    present = C.c_uint32()
+    L = _lib.lib()
+    rc = L.sphx_track_merge(m, arr, len(parts), C.byref(_multi_track_struct(outs)), C.byref(present))
+    if rc:
+        raise SphxError(rc, L.sphx_multi_last_error(None).decode())
+    outs["present"] = present.value
+    return outs
+
+
+def track_merge_frames(parts):
+    """sphx_track_merge_frames: the (frames [n_frames, m, 4], tiles [n_frames, m]) pairs the ranks of one run returned from
+    MultiSolver.track_frames(tiles=True), folded -> the pair of the whole run.  Host code; no GPU needed."""
+    parts = [(np.ascontiguousarray(f, np.float32), np.ascontiguousarray(t, np.uint32)) for f, t in parts]
+    if not parts:
+        raise ValueError("track_merge_frames needs at least one part (the shape of the frames is the parts')")
+    shape = parts[0][1].shape
+    if any(t.shape != shape or f.shape != shape + (4,) for f, t in parts):
+        raise ValueError("track_merge_frames: every part is (float32 [n_frames, m, 4], uint32 [n_frames, m]) of one shape")
+    n = int(np.prod(shape))
+    fp = (C.c_void_p * len(parts))(*[f.ctypes.data or 1 for f, _ in parts])
+    tp = (C.c_void_p * len(parts))(*[t.ctypes.data or 1 for _, t in parts])
+    out, til = np.zeros(shape + (4,), np.float32), np.zeros(shape, np.uint32)
+    L = _lib.lib()
+    rc = L.sphx_track_merge_frames(n, fp, tp, len(parts), out.ctypes.data or 1, til.ctypes.data or 1)
+    if rc:
+        raise SphxError(rc, L.sphx_multi_last_error(None).decode())
+    return out, til
 
 
 FIELD_NAMES = ("vel_grad", "divergence", "vorticity", "color_grad")
@@ -1148,6 +1215,25 @@ class DFSPHMultiSolver(DFSPHSolver):
 
     def stats_frames(self, first=0, count=None):
         return self.multi().stats_frames(first, count)
+
+    # following particles by id (MultiSolver.track and friends; the recorder fires behind every step of simulation_steps(k))
+    def track(self, ids):
+        self.multi().track(ids)
+
+    def track_fetch(self, fields=None):
+        return self.multi().track_fetch(fields)
+
+    def track_record(self, max_frames, every=1):
+        self.multi().track_record(max_frames, every)
+
+    def track_status(self):
+        return self.multi().track_status()
+
+    def track_frames(self, first=0, count=None, tiles=False):
+        return self.multi().track_frames(first, count, tiles)
+
+    def download_by_id(self, first=0, count=None, fields=None):
+        return self.multi().download_by_id(first, count, fields)
 
     # the picture of the tiled run (MultiSolver.render / render_layer: drawn by the tiles, merged on the host; owners are particle ids)
     def render(self, view=None, *, owner=False, rgba=True, **view_fields):

@@ -131,6 +131,10 @@ class SphxTrackOut(C.Structure):
     _fields_ = [("slot", C.c_void_p), ("pos", C.c_void_p), ("vel", C.c_void_p), ("density", C.c_void_p)]
 
 
+class SphxMultiTrackOut(C.Structure):  # sphx_multi_track_out: host pointers
+    _fields_ = [("tile", C.c_void_p), ("slot", C.c_void_p), ("pos", C.c_void_p), ("vel", C.c_void_p), ("density", C.c_void_p)]
+
+
 class SphxTrackStatus(C.Structure):
     _fields_ = [("m", C.c_uint32), ("recording", C.c_uint32), ("max_frames", C.c_uint32), ("every", C.c_uint32), ("frames", C.c_uint32),
                 ("dropped", C.c_uint32), ("reserved", C.c_uint32 * 2)]
@@ -223,6 +227,22 @@ SIGNATURES = {
     "sphx_track_get_status": (_i, [_vp, C.POINTER(SphxTrackStatus)]),
     "sphx_track_read": (_i, [_vp, _u32, _u32, _u32, _vp]),
     "sphx_particle_fields": (_i, [_vp, _u32, C.POINTER(SphxFieldsOut)]),
+    "sphx_multi_track_set": (_i, [_vp, _vp, _u32]),
+    "sphx_multi_track_fetch": (_i, [_vp, _u32, C.POINTER(SphxMultiTrackOut)]),
+    "sphx_multi_track_record": (_i, [_vp, _u32, _u32]),
+    "sphx_multi_track_get_status": (_i, [_vp, C.POINTER(SphxTrackStatus)]),
+    "sphx_multi_track_read": (_i, [_vp, _u32, _u32, _u32, _vp, _vp]),
+    "sphx_multi_download_by_id": (_i, [_vp, _u32, _u32, _u32, C.POINTER(SphxMultiTrackOut), C.POINTER(_u32)]),
+    "sphx_track_merge": (_i, [_u32, C.POINTER(SphxMultiTrackOut), _u32, C.POINTER(SphxMultiTrackOut), C.POINTER(_u32)]),
+    "sphx_track_merge_frames": (_i, [_u64, C.POINTER(_vp), C.POINTER(_vp), _u32, _vp, _vp]),
+    "sphx_tile_track_install": (_i, [_vp, _vp, _vp, _u32, _u32]),
+    "sphx_tile_track_fetch_enqueue": (_i, [_vp]),
+    "sphx_tile_track_fetch": (_i, [_vp, _vp, _vp, _vp]),
+    "sphx_tile_track_window_enqueue": (_i, [_vp, _u32, _u32, _u32]),
+    "sphx_tile_track_window_fetch": (_i, [_vp, _vp, C.POINTER(_u32)]),
+    "sphx_tile_track_record": (_i, [_vp, _u32, _u32]),
+    "sphx_tile_track_frame": (_i, [_vp]),
+    "sphx_tile_track_read": (_i, [_vp, _u32, _u32, _vp, _vp]),
     "sphx_fluid_stats": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32, _vp]),
     "sphx_stats_record": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32, _u32]),
     "sphx_stats_get_status": (_i, [_vp, C.POINTER(SphxStatsStatus)]),

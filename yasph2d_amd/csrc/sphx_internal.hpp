@@ -355,6 +355,8 @@ struct sphx_ctx {
     static constexpr uint32_t MARK_NONE = 0xFFFFFFFFu, MARK_EMPTY = 0xFFFFFFFEu;  // no pass in flight / a pass over zero records
     uint32_t edit_mark = MARK_NONE;
     // particle tracking (sphx_track_*, sphx_download_by_id: sphx_track.inc).  Belongs to the context, not to the particle state.
+    // A tile (sphx_tile_track_*) keeps the shared tables of its multi here: table | filter | found, no map, m == unique; its rec is
+    // [max_frames][unique] {x, y, vx, vy}, then [max_frames][unique] presence words.
     struct Track {
         uint32_t m = 0, unique = 0, log2_bits = 0;  // caller ids, distinct ids, log2 of the filter's bits
         uint32_t* set_buf = nullptr;  // device: table[unique] | map[m] | filter[2^log2_bits / 32] | found[unique]
@@ -363,6 +365,7 @@ struct sphx_ctx {
         uint32_t recording = 0, max_frames = 0, every = 0, frames = 0, dropped = 0, steps = 0;  // steps: finished since sphx_track_record
         uint32_t* scratch = nullptr;  // window index of sphx_download_by_id + the outputs' device copies on the host-pointer paths
         size_t scratch_cap = 0;       // ... in 4-byte words
+        uint32_t window_cap = 0;      // a tile (sphx_tile_track_window_*): the record capacity of the window pass in flight
     } track;
     // fluid statistics (sphx_fluid_stats, sphx_stats_*: sphx_stats.inc).  Belongs to the context, not to the particle state.
     struct Stats {

@@ -45,6 +45,8 @@
 #include "sphx_render_merge.hpp"
 #include "sphx_render_window.hpp"
 #include "sphx_stats_merge.hpp"
+#include "sphx_track_merge.hpp"
+#include "sphx_track_set.hpp"
 
 namespace {
 
@@ -1005,6 +1007,8 @@ struct TileDriver {
         s.neighbor_entries = 0;
         // sphx_multi_stats_record: a frame of this tile's owned particles behind the step's kernels (a flag test without a recording)
         TCHK(sphx_tile_stats_frame(ctx, dt, (uint32_t)n_owned_global));
+        // sphx_multi_track_record: a frame of the tracked ids this tile owns, likewise
+        TCHK(sphx_tile_track_frame(ctx));
         if (st) *st = s;
         return SPHX_OK;
     }
@@ -1187,6 +1191,7 @@ struct sphx_multi {
     Layout explicit_layout;
     bool uploaded = false;  // a sphx_multi_upload has succeeded: the contexts are tiles and hold a re-gridded particle set
     bool state_broken = false;  // a sphx_multi_state_load found a digest mismatch after the copy: the multi asks for an upload or a load
+    sphx::TrackSet track;  // sphx_multi_track_set: the host tables of the set every local tile has installed (the map to the caller's order lives here only)
     uint64_t next_id = 0;  // sphx_multi_append: the id the next appended record gets (sphx_multi_edit::counter_after; the same on every rank)
 
     // run f(tile, index) on every tile, each on its own host thread (the tiles meet in barriers); returns the first error
@@ -2250,6 +2255,212 @@ int sphx_multi_render(sphx_multi* m, const sphx_render_view* view, uint32_t flag
     if (!out->owner) owner.resize(npix);
     const sphx_render_layer acc{key.data(), out->owner ? out->owner : owner.data(), out->rgba};
     return multi_render_layers(m, fn, view, acc);
+}
+
+}  // extern "C"
+
+// ---- following particles by id in a tiled run (include/sphx.h, "following particles by id in a tiled run"; the device passes are
+// csrc/sphx_track.inc, the fold is csrc/sphx_track_merge.hpp) ---------------------------------------------------------------------------
+namespace {
+
+namespace th = sphx_track_host;
+
+uint32_t track_tile_rank(const sphx_multi* m, size_t k) { return m->rank_mode ? (uint32_t)m->tiles[0]->comm->rank : (uint32_t)k; }
+
+int track_bad(sphx_multi* m, const char* fn, const char* what) {
+    m->err = std::string(fn) + ": " + what;
+    return SPHX_ERR_INVALID_ARGUMENT;
+}
+int track_tile_failed(sphx_multi* m, size_t k, int rc) {
+    m->err = "tile " + std::to_string(k) + ": " + sphx_last_error(m->tiles[k]->ctx);
+    return rc;
+}
+const char* track_out_error(const sphx_multi_track_out* out, uint32_t flags) {
+    if (!out) return "out is NULL";
+    if (!out->tile && !out->slot && !out->pos && !out->vel && !out->density) return "out requests no output (every pointer is NULL)";
+    if (flags) return "unknown flags bits";
+    return nullptr;
+}
+
+// the caller's arrays from entry `at` on as the accumulator of the fold; tile and slot are lent where the caller has none
+struct TrackAcc {
+    std::vector<uint32_t> tile, slot;
+    th::Acc acc;
+    TrackAcc(const sphx_multi_track_out& o, size_t at, size_t n) {
+        if (!o.tile) tile.resize(n);
+        if (!o.slot) slot.resize(n);
+        acc.tile = o.tile ? o.tile + at : tile.data();
+        acc.slot = o.slot ? o.slot + at : slot.data();
+        acc.pos = o.pos ? (uint32_t*)o.pos + 2 * at : nullptr;
+        acc.vel = o.vel ? (uint32_t*)o.vel + 2 * at : nullptr;
+        acc.density = o.density ? (uint32_t*)o.density + at : nullptr;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int sphx_track_merge(uint32_t n, const sphx_multi_track_out* parts, uint32_t n_parts, const sphx_multi_track_out* out, uint32_t* out_present) {
+    if (const char* b = th::merge_error(n, parts, n_parts, out)) {
+        g_multi_error = std::string("sphx_track_merge: ") + b;  // (no object to hang the message on: sphx_multi_last_error(NULL))
+        return SPHX_ERR_INVALID_ARGUMENT;
+    }
+    TrackAcc a(*out, 0, n);
+    th::merge(n, parts, n_parts, a.acc);
+    if (out_present) *out_present = th::count_present(a.acc.tile, n);
+    return SPHX_OK;
+}
+
+int sphx_track_merge_frames(uint64_t n, const float* const* parts, const uint32_t* const* parts_tile, uint32_t n_parts, float* out, uint32_t* out_tile) {
+    if (const char* b = th::merge_frames_error(n, parts, parts_tile, n_parts, out)) {
+        g_multi_error = std::string("sphx_track_merge_frames: ") + b;
+        return SPHX_ERR_INVALID_ARGUMENT;
+    }
+    std::vector<uint32_t> tile;
+    if (!out_tile) tile.resize((size_t)n);
+    th::merge_frames(n, parts, parts_tile, n_parts, out, out_tile ? out_tile : tile.data());
+    return SPHX_OK;
+}
+
+int sphx_multi_track_set(sphx_multi* m, const uint32_t* ids, uint32_t n_ids) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    const char* const fn = "sphx_multi_track_set";
+    if (const char* b = sphx::track_check_ids(ids, n_ids)) return track_bad(m, fn, b);
+    int rc;
+    if ((rc = multi_state_ready(m, fn, true))) return rc;
+    sphx::TrackSet s = sphx::track_build(ids, n_ids);  // built once: every tile gets the same tables
+    for (size_t k = 0; k < m->tiles.size(); ++k)
+        if ((rc = sphx_tile_track_install(m->tiles[k]->ctx, s.table.data(), s.filter.data(), s.unique(), s.log2_bits))) {
+            track_tile_failed(m, k, rc);
+            for (auto& t : m->tiles) sphx_tile_track_install(t->ctx, nullptr, nullptr, 0, 0);  // no half-made set
+            m->track = sphx::TrackSet();
+            return rc;
+        }
+    m->track = std::move(s);
+    return SPHX_OK;
+}
+
+int sphx_multi_track_fetch(sphx_multi* m, uint32_t flags, const sphx_multi_track_out* out) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    const char* const fn = "sphx_multi_track_fetch";
+    if (const char* b = track_out_error(out, flags)) return track_bad(m, fn, b);
+    int rc;
+    if ((rc = multi_state_ready(m, fn, true))) return rc;
+    const uint32_t n = m->track.m(), u = m->track.unique();
+    if (!n) return SPHX_OK;
+    // every local tile enqueues on its own stream and device first, then the parts are collected: the tiles' passes overlap
+    for (size_t k = 0; k < m->tiles.size(); ++k)
+        if ((rc = sphx_tile_track_fetch_enqueue(m->tiles[k]->ctx))) return track_tile_failed(m, k, rc);
+    // the answer over the distinct ids, with the arrays the caller asked for
+    std::vector<uint32_t> a_tile(u), a_slot(u), a_pos(out->pos ? 2 * (size_t)u : 0), a_vel(out->vel ? 2 * (size_t)u : 0), a_den(out->density ? u : 0);
+    const th::Acc au{a_tile.data(), a_slot.data(), out->pos ? a_pos.data() : nullptr, out->vel ? a_vel.data() : nullptr, out->density ? a_den.data() : nullptr};
+    th::fill_absent(au, u);
+    std::vector<uint32_t> slot(u), xyvv(4 * (size_t)u), den(u);
+    for (size_t k = 0; k < m->tiles.size(); ++k) {
+        if ((rc = sphx_tile_track_fetch(m->tiles[k]->ctx, slot.data(), (float*)xyvv.data(), (float*)den.data()))) return track_tile_failed(m, k, rc);
+        th::fold_unique(au, track_tile_rank(m, k), u, slot.data(), xyvv.data(), den.data());
+    }
+    TrackAcc a(*out, 0, n);
+    th::expand(a.acc, au, m->track.map.data(), n);
+    return SPHX_OK;
+}
+
+int sphx_multi_download_by_id(sphx_multi* m, uint32_t first_id, uint32_t count, uint32_t flags, const sphx_multi_track_out* out, uint32_t* out_present) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    const char* const fn = "sphx_multi_download_by_id";
+    if (const char* b = track_out_error(out, flags)) return track_bad(m, fn, b);
+    if (const char* b = sphx::track_check_range(first_id, count)) return track_bad(m, fn, b);
+    int rc;
+    if ((rc = multi_state_ready(m, fn, true))) return rc;
+    if (out_present) *out_present = 0;
+    uint32_t present = 0;
+    std::vector<uint32_t> records;
+    std::vector<uint32_t> caps(m->tiles.size());
+    for (uint64_t w0 = 0; w0 < count; w0 += th::WINDOW) {
+        const uint32_t wc = (uint32_t)std::min<uint64_t>(count - w0, th::WINDOW);
+        const uint32_t wfirst = first_id + (uint32_t)w0;
+        // a tile's buffer follows what it owns, not the window: the tiles together return about one record per particle of the window
+        for (size_t k = 0; k < m->tiles.size(); ++k) {
+            caps[k] = (uint32_t)std::min<uint64_t>(wc, m->tiles[k]->n_owned_local);
+            if ((rc = sphx_tile_track_window_enqueue(m->tiles[k]->ctx, wfirst, wc, caps[k]))) return track_tile_failed(m, k, rc);
+        }
+        TrackAcc a(*out, (size_t)w0, wc);
+        th::fill_absent(a.acc, wc);
+        for (size_t k = 0; k < m->tiles.size(); ++k) {
+            records.resize(th::HEADER_WORDS + (size_t)caps[k] * th::RECORD_WORDS);
+            uint32_t n_rec = 0;
+            if ((rc = sphx_tile_track_window_fetch(m->tiles[k]->ctx, records.data(), &n_rec))) return track_tile_failed(m, k, rc);
+            if (th::scatter_records(a.acc, track_tile_rank(m, k), wc, records.data() + th::HEADER_WORDS, n_rec)) {
+                m->err = std::string(fn) + ": tile " + std::to_string(k) + " returned a record outside the window";
+                return SPHX_ERR_HIP;
+            }
+        }
+        present += th::count_present(a.acc.tile, wc);
+    }
+    if (out_present) *out_present = present;
+    return SPHX_OK;
+}
+
+int sphx_multi_track_record(sphx_multi* m, uint32_t max_frames, uint32_t every) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    const char* const fn = "sphx_multi_track_record";
+    int rc;
+    if ((rc = multi_state_ready(m, fn, true))) return rc;
+    if (max_frames) {  // (checked before any tile is touched: all tiles keep the old recording or all get the new one)
+        if (every == 0) return track_bad(m, fn, "every is 0");
+        if ((uint64_t)max_frames * m->track.unique() * th::FRAME_ENTRY_BYTES > th::RECORD_MAX_BYTES) {
+            m->err = std::string(fn) + ": max_frames * (distinct ids) * 20 bytes is more than 1 GiB per tile";
+            return SPHX_ERR_CAPACITY;
+        }
+        if (!m->track.m()) {
+            m->err = std::string(fn) + ": the tracked set is empty (call sphx_multi_track_set first)";
+            return SPHX_ERR_NOT_READY;
+        }
+    }
+    for (size_t k = 0; k < m->tiles.size(); ++k)
+        if ((rc = sphx_tile_track_record(m->tiles[k]->ctx, max_frames, every))) {
+            track_tile_failed(m, k, rc);
+            for (auto& t : m->tiles) sphx_tile_track_record(t->ctx, 0, 1);  // no half-made recording
+            return rc;
+        }
+    return SPHX_OK;
+}
+
+// (every tile counts the same steps and stores the same number of frames: the first local tile speaks for all; m is the caller's)
+int sphx_multi_track_get_status(const sphx_multi* m, sphx_track_status* out) {
+    if (!m || !out) return SPHX_ERR_INVALID_ARGUMENT;
+    const int rc = sphx_track_get_status(m->tiles[0]->ctx, out);
+    out->m = m->track.m();
+    return rc;
+}
+
+int sphx_multi_track_read(sphx_multi* m, uint32_t first_frame, uint32_t n_frames, uint32_t flags, float* out, uint32_t* out_tile) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    const char* const fn = "sphx_multi_track_read";
+    if (flags) return track_bad(m, fn, "unknown flags bits");
+    int rc;
+    if ((rc = multi_state_ready(m, fn, true))) return rc;
+    sphx_track_status st;
+    sphx_track_get_status(m->tiles[0]->ctx, &st);
+    if ((uint64_t)first_frame + n_frames > st.frames) return track_bad(m, fn, "first_frame + n_frames is beyond the frames recorded (sphx_multi_track_get_status)");
+    if (n_frames == 0) return SPHX_OK;
+    if (!out) return track_bad(m, fn, "out is NULL");
+    const uint32_t n = m->track.m(), u = m->track.unique();
+    const size_t cnt = (size_t)n_frames * u;
+    std::vector<uint32_t> xyvv(4 * cnt, th::ABSENT_WORD), tile(cnt, th::ABSENT), slot(cnt, th::ABSENT), t_xyvv(4 * cnt), t_slot(cnt);
+    for (size_t k = 0; k < m->tiles.size(); ++k) {
+        if ((rc = sphx_tile_track_read(m->tiles[k]->ctx, first_frame, n_frames, (float*)t_xyvv.data(), t_slot.data()))) return track_tile_failed(m, k, rc);
+        th::fold_frames_unique(xyvv.data(), tile.data(), slot.data(), track_tile_rank(m, k), cnt, t_xyvv.data(), t_slot.data());
+    }
+    const uint32_t* const map = m->track.map.data();
+    for (uint32_t f = 0; f < n_frames; ++f)
+        for (uint32_t k = 0; k < n; ++k) {
+            const size_t src = (size_t)f * u + map[k], dst = (size_t)f * n + k;
+            std::memcpy(out + 4 * dst, xyvv.data() + 4 * src, 16);
+            if (out_tile) out_tile[dst] = tile[src];
+        }
+    return SPHX_OK;
 }
 
 }  // extern "C"

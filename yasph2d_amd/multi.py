@@ -273,6 +273,69 @@ class MultiSolver:
         self._chk(self.L.sphx_multi_stats_read(self.h, first, count, _p(rec) if count else None, _p(info) if count else None))
         return rec, info
 
+    # ---- following particles by id (the contract is in include/sphx.h, "following particles by id in a tiled run") ----
+    def track(self, ids):
+        """sphx_multi_track_set: the ids to follow (any order, duplicates allowed, at most _lib.TRACK_MAX_IDS; an empty sequence clears
+        the set).  Discards a recording.  The set belongs to the multi: it survives migration, re-partitioning, edits, uploads and
+        state loads."""
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        self._chk(self.L.sphx_multi_track_set(self.h, _p(ids) if len(ids) else None, len(ids)))
+
+    def track_status(self):
+        """sphx_multi_track_get_status -> dict(m, recording, max_frames, every, frames, dropped)."""
+        st = _lib.SphxTrackStatus()
+        self._chk(self.L.sphx_multi_track_get_status(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_ if k != "reserved"}
+
+    def track_fetch(self, fields=None):
+        """sphx_multi_track_fetch: where the tracked particles are now, in the order of track(ids), without a download of the tiles:
+        {"tile": uint32 [m] (the tile that owns the id), "slot": uint32 [m] (its index in tile_context(tile).download()), "pos":
+        float32 [m, 2], "vel": float32 [m, 2], "density": float32 [m]} (or the requested `fields`).  An id no tile owns has tile and
+        slot _lib.TRACK_ABSENT and NaN records (the word 0x7FC00000).  Rank mode: this rank's part, without communication — fold the
+        ranks' parts with yasph2d_amd.track_merge."""
+        from . import _multi_track_outputs, _multi_track_struct
+
+        outs = _multi_track_outputs(fields, self.track_status()["m"])
+        self._chk(self.L.sphx_multi_track_fetch(self.h, 0, C.byref(_multi_track_struct(outs))))
+        return outs
+
+    def track_record(self, max_frames, every=1):
+        """sphx_multi_track_record: from now on every `every`-th finished multi step makes each tile store one frame of the tracked ids
+        it owns on its device, up to max_frames frames (later ones are counted in track_status()["dropped"]); max_frames=0 stops and
+        frees.  Works inside steps(timer, k) too; nothing is synchronised and nothing comes back until track_frames()."""
+        self._chk(self.L.sphx_multi_track_record(self.h, max_frames, every))
+
+    def track_frames(self, first=0, count=None, tiles=False):
+        """sphx_multi_track_read -> float32 [count, m, 4] = x, y, vx, vy of the recorded frames [first, first + count) (count=None: all
+        from `first`), folded over the local tiles; tiles=True: (that, uint32 [count, m]: the tile that owned each id then, or
+        _lib.TRACK_ABSENT).  Rank mode: this rank's part — fold with yasph2d_amd.track_merge_frames."""
+        st = self.track_status()
+        if count is None:
+            count = max(st["frames"] - first, 0)
+        out = np.zeros((count, st["m"], 4), np.float32)
+        til = np.zeros((count, st["m"]), np.uint32) if tiles else None
+        self._chk(self.L.sphx_multi_track_read(self.h, first, count, 0, (out.ctypes.data or 1) if count else None,
+                                               (til.ctypes.data or 1) if tiles and count else None))
+        return (out, til) if tiles else out
+
+    def download_by_id(self, first=0, count=None, fields=None):
+        """sphx_multi_download_by_id: the particles with the ids first .. first + count - 1 in id order -> the dict of track_fetch()
+        plus "present", the number of ids found.  count=None: up to the largest id the local tiles own (one sphx_multi_download of the
+        ids; pass count where that matters).  After an unedited upload(pos) it is the particles in upload order, whatever the steps
+        and migrations since.  Every tile returns only the records it owns."""
+        from . import _multi_track_outputs, _multi_track_struct
+
+        if count is None:
+            n = C.c_uint64(self.L.sphx_multi_num_owned(self.h))
+            ids = np.zeros(n.value, np.uint32)
+            self._chk(self.L.sphx_multi_download(self.h, None, None, None, _p(ids) if n.value else None, C.byref(n)))
+            count = max(int(ids[:n.value].max()) + 1 - first, 0) if n.value else 0
+        outs = _multi_track_outputs(fields, count)
+        present = C.c_uint32()
+        self._chk(self.L.sphx_multi_download_by_id(self.h, first, count, 0, C.byref(_multi_track_struct(outs)), C.byref(present)))
+        outs["present"] = present.value
+        return outs
+
     # ---- picture of the tiled run (the contract is in include/sphx.h, "picture of a tiled run") ----
     @staticmethod
     def _view(view, view_fields):
