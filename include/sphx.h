@@ -21,12 +21,12 @@
  *       surface (sphx_set_boundary, sphx_upload, sphx_append, sphx_remove, sphx_download*, sphx_num_*, sphx_view_*, sphx_sample_*, sphx_render*, sphx_state_*, sphx_track_*, sphx_download_by_id, sphx_particle_fields, sphx_fluid_stats, sphx_stats_*), the Solver trait (sphx_clear_cached,
  *       sphx_step_begin[_law], sphx_step_finish, sphx_wcsph_step_*), the same trait over a device list (sphx_multi_create[_rank],
  *       sphx_multi_destroy, sphx_multi_set_boundary, sphx_multi_upload, sphx_multi_clear_cached, sphx_multi_step_begin/finish,
- *       sphx_multi_simulation_step[s], sphx_multi_download, sphx_multi_num_owned, sphx_multi_last_error, sphx_comm_ops) and
+ *       sphx_multi_simulation_step[s], sphx_multi_download, sphx_multi_sample_*, sphx_sample_merge, sphx_multi_num_owned, sphx_multi_last_error, sphx_comm_ops) and
  *       the status / flag codes.
  *   INSPECTION — parity tests and tools, not on the hot path, may change with the data layout:
  *       sphx_update_neighborhood, sphx_update_densities, sphx_compute_alpha (the pieces benches/ drives), sphx_download_solver_state,
  *       sphx_download_neighbors, sphx_download_cells, sphx_grid_info, sphx_get_constants, sphx_last_flags, sphx_build_stats,
- *       sphx_multi_info, sphx_multi_tile_ctx, sphx_multi_set_layout / _set_grid_layout, sphx_profile_*, sphx_synchronize,
+ *       sphx_multi_info, sphx_multi_tile_ctx, sphx_multi_tile_rects, sphx_multi_ghost_rings, sphx_multi_set_layout / _set_grid_layout, sphx_profile_*, sphx_synchronize,
  *       sphx_set_tiling_invariant (a comparison mode: a run that does not depend on how the domain is tiled).
  *   INTERNAL — the seam between the tile loop (csrc/sphx_tiles.cpp) and a tile's context, exported so that the tests can drive the
  *       same sub-steps from the reference implementation of that loop (tests/tiles_reference.py); no stability promise:
@@ -70,7 +70,10 @@ extern "C" {
                             *    sphx_tile_grow
                             * 5 (additive): sphx_multi_track_set / _fetch / _record / _get_status / _read, sphx_multi_download_by_id,
                             *    sphx_multi_track_out, sphx_track_merge, sphx_track_merge_frames, sphx_tile_track_install / _fetch_enqueue /
-                            *    _fetch / _window_enqueue / _window_fetch / _record / _frame / _read */
+                            *    _fetch / _window_enqueue / _window_fetch / _record / _frame / _read
+                            * 5 (additive): sphx_multi_sample_points, sphx_multi_sample_grid, sphx_multi_sample_out, sphx_sample_merge,
+                            *    sphx_multi_tile_rects, sphx_multi_ghost_rings, sphx_tile_sample_points / _points_fetch / _window /
+                            *    _window_fetch, SPHX_SAMPLE_FIELD_* */
 
 /* ---- status codes ---- */
 enum {
@@ -944,6 +947,81 @@ int sphx_tile_track_record(sphx_ctx* tile_ctx, uint32_t max_frames, uint32_t eve
 int sphx_tile_track_frame(sphx_ctx* tile_ctx); /* one finished step: a frame if the recording is due */
 int sphx_tile_track_read(sphx_ctx* tile_ctx, uint32_t first_frame, uint32_t n_frames, float* xyvv /* host, [n_frames][unique][4] */,
                          uint32_t* slot /* host, [n_frames][unique] */);
+/* ---- sampling the fields of a tiled run (csrc/sphx_tiles.cpp; device passes csrc/sphx_sample.inc, lattice windows and the fold
+ * csrc/sphx_sample_window.hpp) ---------------------------------------------------------------------------------------------------------
+ * sphx_sample_points / sphx_sample_grid for a sphx_multi, without sphx_multi_download and a second context.
+ * Who answers: the tile whose owned cell rectangle contains cell_of(q) — the grid's fp32 cell function of "field sampling" above
+ *   (saturating, a NaN coordinate goes to cell 0).  The rectangles of a layout partition [0, 65536)^2 ("picture of a tiled run"), so every
+ *   point has exactly one answering tile.
+ * What it computes: the contract of sphx_sample_points, word for word, over THAT TILE'S OWN ARRAYS — candidates, acceptance, kernels,
+ *   summation order and outputs; "device index" is the tile's local index (the order of sphx_download on sphx_multi_tile_ctx, ghosts
+ *   included), "boundary" the tile's clipped boundary set (sphx_download_boundary on it).  One device function walks a point in all
+ *   four calls.  Consequences: (a) the result is bit-identical to the restatement of that contract over the answering tile's own
+ *   downloads, in every mode; (b) in tiling-invariant mode (sphx_set_tiling_invariant: cell mates ordered by id in a tile and in a single
+ *   context alike; a clipped boundary keeps the caller's order) it is bit-identical to sphx_sample_points of a single context in the
+ *   same mode; (c) the lattice call is bit-identical to the points call at the same fp32 points.
+ * The ghost band: a point in an owned cell walks the 3 x 3 cells around it and, across a cut, reads position, velocity and density of
+ *   ring-1 ghosts.  Positions of ghosts are exact after every exchange (they only change with the advection that rides on one);
+ *   velocities are exact in `valid` rings, densities in `avalid` rings (the tile loop's ring budget: a halo exchange sets valid = kvalid =
+ *   halo and avalid = halo - 1, a warm start costs valid a ring, every solver iteration two).  valid >= 1 and avalid >= 1 therefore mean
+ *   "ring-1 ghosts hold final position, velocity and density", and need(min(avalid, valid) - 1) — the very test the next
+ *   sphx_multi_step_begin makes before its non-pressure pass — is the precondition of a query.  Both calls make it before any tile
+ *   enqueues:
+ *     a ring is left: nothing is exchanged, the call only reads (a queued run-ahead pass stays valid, the sweep direction is put back);
+ *     the band is spent: the halo exchange and re-grid the next step_begin owes happen NOW instead of then — the plain exchange of
+ *       the tile loop on the same state (after a finished step no advection is pending: the step's own exchange has applied it), so the
+ *       run is unchanged.  In this case alone sphx_multi_info().exchanges moves one earlier; after the next sphx_multi_step_begin the
+ *       count is the same either way.
+ *   Because of that exchange the calls are COLLECTIVE in rank mode: every rank calls at the same point of the run with the same points.
+ * In-process (sphx_multi_create): every point is answered; out->tile is optional.  Rank mode (sphx_multi_create_rank): the call fills
+ *   the points this rank's tile answers; every other entry of every requested array is written as zero with tile = -1, and out->tile is
+ *   required.  The caller moves the parts with its own transport and folds them with sphx_sample_merge(m, parts, n_parts, out): pure host
+ *   code; per point the part with tile >= 0, the lowest tile if several have one, zeros and -1 if none; every part carries tile and the
+ *   arrays out asks for (SPHX_ERR_INVALID_ARGUMENT otherwise); n_parts == 0 gives the all-absent answer; out may alias parts[0].
+ * A tile without any particle (it owns cells, perhaps walls, and no fluid) answers from its static grid alone: the density next to a wall
+ *   there equals the single context's.
+ * When allowed: after sphx_multi_upload (its warm-up block ends with the re-grid that computes the densities of the uploaded positions,
+ *   on owned particles and ghosts alike: density_valid of sphx_multi_fluid_stats) and after every finished step.  SPHX_ERR_NOT_READY
+ *   between sphx_multi_step_begin and _finish, before the first upload, on a multi a failed sphx_multi_state_load left broken and on one
+ *   whose collective step has failed.  SPHX_ERR_INVALID_ARGUMENT (sphx_multi_last_error names the argument): m, out NULL, xy NULL with
+ *   n > 0, n >= 2^31, out requesting none of the four fields, an unknown kernel_kind, any flags bit (there is no device-pointer path
+ *   across several devices), the lattice errors of sphx_sample_grid, more than 64 tiles, rank mode without out->tile.  n == 0 and
+ *   nx * ny == 0 are successful no-ops once the arguments pass.  A refused call touches no tile.
+ * Device work per tile.  Points: all n points go up (8 bytes each); a selection pass appends the indices of the points the tile owns to
+ *   a list (one atomic per wavefront), the walk runs over that list with every lane live and writes one packed 24-byte record {index,
+ *   density, fraction, vx, vy, count} per answered point; only those records come back and the host scatters them by index.  Lattice:
+ *   the points a tile owns form an index rectangle (the cell of x0 + (float)ix * dx is monotone in ix), found on the host by bisection
+ *   over the exact fp32 expression; the tile walks that window alone, the host copies its rows into the full arrays.  The points
+ *   the K tiles walk together are those of one query, not of K; their launches add up (every tile also reads all n points in its
+ *   selection pass), so the summed device time of a small query grows with K.  Figures: DESIGN.md section 4n.
+ * Inspection: sphx_multi_tile_rects writes the owned rectangles of ALL world tiles in rank order (*inout_n: capacity in, world out;
+ *   SPHX_ERR_CAPACITY if it was smaller, SPHX_ERR_NOT_READY before the first upload); sphx_multi_ghost_rings writes {valid, kvalid,
+ *   avalid} of local tile 0 (+INFINITY on a one-tile run).
+ * One tile (INTERNAL, like the other sphx_tile_* calls; accepted only on a tile context — sphx_sample_* keep refusing one):
+ *   sphx_tile_sample_points enqueues upload, selection and walk for the fields named by SPHX_SAMPLE_FIELD_* bits, _points_fetch copies
+ *   back *out_n records of six words (more than cap_records: SPHX_ERR_CAPACITY); sphx_tile_sample_window enqueues the walk over the
+ *   tile's window of the lattice and reports it as out_window = {ix0, ix1, iy0, iy1} (all zero: the tile owns no lattice point),
+ *   _window_fetch copies the window-sized arrays back, row after row (out names exactly the queued fields).  SPHX_ERR_NOT_READY between
+ *   a halo exchange and the tile's re-grid. */
+enum { SPHX_SAMPLE_FIELD_DENSITY = 1u, SPHX_SAMPLE_FIELD_FRACTION = 2u, SPHX_SAMPLE_FIELD_VELOCITY = 4u, SPHX_SAMPLE_FIELD_COUNT = 8u };
+typedef struct sphx_multi_sample_out {   /* host arrays; any non-empty subset of the first four */
+    float* density;    /* [m] or NULL */
+    float* fraction;   /* [m] or NULL */
+    float* velocity;   /* [2m] interleaved xy, or NULL */
+    uint32_t* count;   /* [m] or NULL */
+    int32_t* tile;     /* [m] or NULL: global rank of the tile that answered, -1: none of the local tiles */
+} sphx_multi_sample_out;
+int sphx_multi_sample_points(sphx_multi* m, const float* xy /* host */, uint32_t n, int kernel_kind, uint32_t flags /* 0 */, const sphx_multi_sample_out* out);
+int sphx_multi_sample_grid(sphx_multi* m, float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, int kernel_kind, uint32_t flags /* 0 */,
+                           const sphx_multi_sample_out* out);
+int sphx_sample_merge(uint32_t m, const sphx_multi_sample_out* parts, uint32_t n_parts, const sphx_multi_sample_out* out);
+int sphx_multi_tile_rects(const sphx_multi* m, sphx_tile_rect* out /* [*inout_n] */, uint32_t* inout_n);
+int sphx_multi_ghost_rings(const sphx_multi* m, double* out3);
+int sphx_tile_sample_points(sphx_ctx* tile_ctx, const float* xy /* host, [2m] */, uint32_t m, int kernel_kind, uint32_t fields);
+int sphx_tile_sample_points_fetch(sphx_ctx* tile_ctx, uint32_t* records /* host, [6 * cap_records] */, uint32_t cap_records, uint32_t* out_n);
+int sphx_tile_sample_window(sphx_ctx* tile_ctx, float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, int kernel_kind, uint32_t fields,
+                            uint32_t* out_window /* [4] */);
+int sphx_tile_sample_window_fetch(sphx_ctx* tile_ctx, const sphx_sample_out* out /* host, window-sized */);
 /* Solver::simulation_step(&mut world, &mut time_manager) (solver/mod.rs:17) in ONE call: phase A, the TimeManager mirror
  * (simulation_step() dfsph.rs:433, update_simulation_step dfsph.rs:478-480), phase B */
 struct sphx_timer;

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Cost of field sampling (sphx_sample_points / sphx_sample_grid) on the bench scene (the 16 M dam break), next to the step it reads.
 
-  tools/sample_bench.py [--particles 16000000] [--warmup 40] [--steps 40] [--calls 25]
+  tools/sample_bench.py [--particles 16000000] [--warmup 40] [--steps 40] [--calls 25] [--tiles K]
 
 As tools/viscosity_ab.py: a scratch context keeps the GPU busy until the context's first step is queued, then --warmup untimed
 steps settle the flow.  Measured on that settled state:
@@ -13,6 +13,9 @@ steps settle the flow.  Measured on that settled state:
     cell_of) on the host, density + fraction + velocity.
 Each configuration is called --calls times; device time per call = the hipEvent bracket of its one launch (median), minus nothing (the
 bracket's own cost is printed as event_overhead_us).  C also reports the host-path wall time of the whole call (copies included).
+--tiles K measures the tiled calls instead (sphx_multi_sample_grid / _points, K tiles on device 0): the frame of A and 2^20 points
+sorted by cell, as wall time of the whole host call (median, profiler off) and, in a second pass, as the device time of every tile's
+launches (sphx_profile_* of the tile contexts), next to the wall time of the sphx_multi_download the calls replace and the halo exchanges they caused.
 Prints one JSON line."""
 import argparse
 import json
@@ -69,13 +72,87 @@ def timed(ctx, label, calls, fn):
     return float(np.median(dev)), float(np.median(wall)), dev
 
 
+def wall_us(calls, fn):
+    out = []
+    for _ in range(calls):
+        t0 = time.perf_counter()
+        fn()
+        out.append((time.perf_counter() - t0) * 1e6)
+    return float(np.median(out))
+
+
+def tiled(args):
+    """the tiled calls on K tiles of device 0: host wall time per call, device time per tile and pass, the download they replace"""
+    from yasph2d_amd.multi import MultiSolver
+
+    scale = float(np.sqrt(args.particles / 4050.0))
+    w = scene(args.particles)
+    pos = np.ascontiguousarray(w.positions, np.float32)
+    p = y.default_params()
+    m = MultiSolver(p, devices=[0] * args.tiles)
+    m.set_boundary(w.boundary_particles)
+    m.upload(pos)
+    t = y.TimeManager()
+    m.steps(t, args.warmup)
+    m.synchronize()
+    t0 = time.perf_counter()
+    m.steps(t, args.steps)
+    m.synchronize()
+    ms_step = (time.perf_counter() - t0) * 1e3 / args.steps
+    tiles = [m.tile_context(k) for k in range(args.tiles)]
+    n = int(m.info()["owned_local"])
+    out = dict(particles=n, tiles=args.tiles, scale=scale, warmup=args.warmup, steps=args.steps, calls=args.calls, ms_per_step=ms_step,
+               ghost_rings=m.ghost_rings(), tile_rects=m.tile_rects().tolist())
+    d = m.download()
+    lo, hi = d["pos"].min(0), d["pos"].max(0)
+    out["multi_download_us"] = wall_us(max(3, args.calls // 5), m.download)
+    nx, ny = 1920, 1080
+    dx, dy = np.float32(2.0 * scale / nx), np.float32(2.5 * scale / ny)
+    rng = np.random.default_rng(1)
+    k = 1 << 20
+    pts = (lo + rng.random((k, 2), dtype=np.float32) * (hi - lo)).astype(np.float32)
+    cell = np.fmin(np.fmax((pts - np.array(p.grid_min[:], np.float32)) * np.float32(np.float32(1) / np.float32(p.smoothing_length)), 0), 65535).astype(np.uint32)
+    pts = np.ascontiguousarray(pts[np.argsort((part1by1(cell[:, 1]) << np.uint64(1)) | part1by1(cell[:, 0]), kind="stable")])
+    before = m.info()["exchanges"]
+    queries = (("frame_1920x1080", lambda: m.sample_grid((np.float32(0), np.float32(0)), (dx, dy), (ny, nx), fields=FIELDS), ("tile_sample_window",)),
+               ("points_2^20_sorted_by_cell", lambda: m.sample(pts, fields=FIELDS), ("tile_sample_select", "tile_sample_indexed")))
+    # pass 1, profiler off: the wall time of the whole host call
+    for name, fn, _ in queries:
+        fn()  # (grows the scratch)
+        out[name] = dict(host_call_us=wall_us(args.calls, fn))
+    # pass 2, profiler on: the device time of every tile's launches (the hipEvent brackets would be inside pass 1's wall time)
+    for c in tiles:
+        c.profile_reset()
+        c.profile_filter(None)
+        c.profile_enable(True)
+    for name, fn, labels in queries:
+        for c in tiles:
+            c.profile_reset()
+        for _ in range(args.calls):
+            fn()
+        m.synchronize()
+        per_tile = []
+        for c in tiles:
+            prof = c.profile_get()
+            per_tile.append({lab: prof[lab]["total_ms"] * 1e3 / prof[lab]["launches"] for lab in labels if lab in prof and prof[lab]["launches"]})
+        out[name].update(device_us_per_tile=per_tile, device_us_all_tiles=float(sum(sum(x.values()) for x in per_tile)))
+    for c in tiles:
+        c.profile_enable(False)
+    out["exchanges_caused"] = m.info()["exchanges"] - before
+    m.close()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--particles", type=int, default=16_000_000)
     ap.add_argument("--warmup", type=int, default=40)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--calls", type=int, default=25)
+    ap.add_argument("--tiles", type=int, default=0, help="measure sphx_multi_sample_* on this many tiles of device 0 instead")
     args = ap.parse_args()
+    if args.tiles:
+        return tiled(args)
     scale = float(np.sqrt(args.particles / 4050.0))
     stop = threading.Event()
     th = threading.Thread(target=busy, args=(stop, args.particles), daemon=True)
@@ -139,6 +216,10 @@ def main():
     c["random_over_sorted"] = c["random_order"]["us"] / c["sorted_by_cell"]["us"]
     out["C_1M_points"] = c
     ctx.profile_enable(False)
+    # the wall time of the whole host call once more with the profiler off (what --tiles K reports as host_call_us)
+    sorted_pts = np.ascontiguousarray(pts[order])
+    out["A_frame"]["host_call_us_profiler_off"] = wall_us(args.calls, lambda: ctx.sample_grid((np.float32(0), np.float32(0)), (dx, dy), (ny, nx), fields=FIELDS))
+    out["C_1M_points"]["sorted_by_cell"]["host_call_us_profiler_off"] = wall_us(args.calls, lambda: ctx.sample(sorted_pts, fields=FIELDS))
     s.close()
     print(json.dumps(out))
 

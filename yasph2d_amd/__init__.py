@@ -16,7 +16,7 @@ from ._lib import (FLAG_DENSITY_ITER_CAP, FLAG_DIVERGENCE_ITER_CAP, FLAG_DENSE_C
 
 __all__ = ["SphxContext", "FluidParticleWorld", "TimeManager", "DFSPHSolver", "DFSPHMultiSolver", "default_params", "duration_from_secs_f32",
            "duration_as_secs_f32", "SphxError", "WCSPHSolver", "VISCOSITY_XSPH", "VISCOSITY_PHYSICAL", "SAMPLE_FIELDS", "gauge_elevation",
-           "render_fit", "render_merge", "track_merge", "track_merge_frames", "write_png", "SCENE_RECT", "TRACK_FIELDS", "MULTI_TRACK_FIELDS", "FIELD_NAMES", "STATS_DTYPE", "STATS_FRAME_DTYPE"]
+           "sample_merge", "render_fit", "render_merge", "track_merge", "track_merge_frames", "write_png", "SCENE_RECT", "TRACK_FIELDS", "MULTI_TRACK_FIELDS", "FIELD_NAMES", "STATS_DTYPE", "STATS_FRAME_DTYPE"]
 
 
 def _p(a):
@@ -88,6 +88,40 @@ def _out_struct(outs, ptr):
     for f, a in outs.items():
         setattr(o, f, ptr(a) or 1)  # (an empty tensor has no storage: a non-NULL dummy still names the field; nothing is written)
     return o
+
+
+def sample_merge(parts):
+    """sphx_sample_merge: the parts the ranks of one run returned from MultiSolver.sample() or sample_grid() (dicts with "tile" and the
+    same other fields, all of one shape) folded into the answer of the whole run: per point the part whose tile is >= 0 (the lowest
+    tile if several are), zeros and tile -1 where none is.  -> the dict of the common fields, "tile" included.  Host code; no GPU."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("sample_merge needs at least one part (the shape of the answer is the parts')")
+    if any("tile" not in p for p in parts):
+        raise ValueError("sample_merge: every part needs its \"tile\" array")
+    shape = np.shape(parts[0]["tile"])
+    m = int(np.prod(shape))
+    fields = [f for f in SAMPLE_FIELDS if all(f in p for p in parts)]
+    dtype = dict(density=np.float32, fraction=np.float32, velocity=np.float32, count=np.uint32, tile=np.int32)
+    kept = []
+    arr = (_lib.SphxMultiSampleOut * len(parts))()
+    for k, p in enumerate(parts):
+        a = {f: np.ascontiguousarray(p[f], dtype[f]) for f in fields + ["tile"]}
+        if any(a[f].shape != shape + ((2,) if f == "velocity" else ()) for f in a):
+            raise ValueError("sample_merge: the parts differ in shape")
+        kept.append(a)
+        for f, v in a.items():
+            setattr(arr[k], f, v.ctypes.data or 1)
+    outs = _numpy_outputs(fields, shape)
+    outs["tile"] = np.full(shape, -1, np.int32)
+    o = _lib.SphxMultiSampleOut()
+    for f, v in outs.items():
+        setattr(o, f, v.ctypes.data or 1)
+    L = _lib.lib()
+    rc = L.sphx_sample_merge(m, arr, len(parts), C.byref(o))
+    if rc:
+        raise SphxError(rc, L.sphx_multi_last_error(None).decode())
+    return outs
 
 
 TRACK_FIELDS = ("slot", "pos", "vel", "density")
@@ -1215,6 +1249,14 @@ class DFSPHMultiSolver(DFSPHSolver):
 
     def stats_frames(self, first=0, count=None):
         return self.multi().stats_frames(first, count)
+
+    # sampling the fields of the tiled run (MultiSolver.sample / sample_grid: answered by the tiles, no download; gauge_elevation takes
+    # this solver or its multi() as it takes a SphxContext)
+    def sample(self, points, kernel=KERNEL_WENDLAND_C2, fields=SAMPLE_FIELDS, tiles=False):
+        return self.multi().sample(points, kernel, fields, tiles)
+
+    def sample_grid(self, origin, spacing, shape, kernel=KERNEL_WENDLAND_C2, fields=SAMPLE_FIELDS, tiles=False):
+        return self.multi().sample_grid(origin, spacing, shape, kernel, fields, tiles)
 
     # following particles by id (MultiSolver.track and friends; the recorder fires behind every step of simulation_steps(k))
     def track(self, ids):

@@ -89,6 +89,17 @@ class SphxSampleOut(C.Structure):
     _fields_ = [("density", C.c_void_p), ("fraction", C.c_void_p), ("velocity", C.c_void_p), ("count", C.c_void_p)]
 
 
+SAMPLE_FIELD_BITS = dict(density=1, fraction=2, velocity=4, count=8)  # SPHX_SAMPLE_FIELD_* (sphx_tile_sample_*)
+
+
+class SphxMultiSampleOut(C.Structure):  # sphx_multi_sample_out: host pointers
+    _fields_ = [("density", C.c_void_p), ("fraction", C.c_void_p), ("velocity", C.c_void_p), ("count", C.c_void_p), ("tile", C.c_void_p)]
+
+
+class SphxTileRect(C.Structure):  # sphx_tile_rect: cells, half-open
+    _fields_ = [("x0", C.c_uint32), ("x1", C.c_uint32), ("y0", C.c_uint32), ("y1", C.c_uint32)]
+
+
 RENDER_DEVICE_POINTERS = 1  # sphx_render flags
 RENDER_NONE, RENDER_BOUNDARY = 0xFFFFFFFF, 0xFFFFFFFE  # owner codes
 
@@ -283,6 +294,15 @@ SIGNATURES = {
     "sphx_num_boundary": (_u32, [_vp]),
     "sphx_sample_points": (_i, [_vp, _vp, _u32, _i, _u32, C.POINTER(SphxSampleOut)]),
     "sphx_sample_grid": (_i, [_vp, _f, _f, _f, _f, _u32, _u32, _i, _u32, C.POINTER(SphxSampleOut)]),
+    "sphx_multi_sample_points": (_i, [_vp, _vp, _u32, _i, _u32, C.POINTER(SphxMultiSampleOut)]),
+    "sphx_multi_sample_grid": (_i, [_vp, _f, _f, _f, _f, _u32, _u32, _i, _u32, C.POINTER(SphxMultiSampleOut)]),
+    "sphx_sample_merge": (_i, [_u32, C.POINTER(SphxMultiSampleOut), _u32, C.POINTER(SphxMultiSampleOut)]),
+    "sphx_multi_tile_rects": (_i, [_vp, C.POINTER(SphxTileRect), C.POINTER(_u32)]),
+    "sphx_multi_ghost_rings": (_i, [_vp, C.POINTER(C.c_double)]),
+    "sphx_tile_sample_points": (_i, [_vp, _vp, _u32, _i, _u32]),
+    "sphx_tile_sample_points_fetch": (_i, [_vp, _vp, _u32, C.POINTER(_u32)]),
+    "sphx_tile_sample_window": (_i, [_vp, _f, _f, _f, _f, _u32, _u32, _i, _u32, C.POINTER(_u32)]),
+    "sphx_tile_sample_window_fetch": (_i, [_vp, C.POINTER(SphxSampleOut)]),
     "sphx_render_fit": (_i, [_u32, _u32, _f, _f, _f, _f, C.POINTER(SphxRenderView)]),
     "sphx_render": (_i, [_vp, C.POINTER(SphxRenderView), _u32, C.POINTER(SphxRenderOut)]),
     "sphx_multi_render": (_i, [_vp, C.POINTER(SphxRenderView), _u32, C.POINTER(SphxRenderOut)]),

@@ -390,6 +390,15 @@ struct sphx_ctx {
     const char* sample_missing = "no neighbour build yet: run a step, or sphx_update_neighborhood + sphx_update_densities";
     float* sample_buf = nullptr;  // device scratch of the host-pointer queries (points + outputs), grown on demand
     size_t sample_cap = 0;        // ... in 4-byte words
+    // sphx_tile_sample_* (a tile context; sample_buf is its scratch too — sphx_sample_* refuse a tile): the query in flight between
+    // the enqueue half and the fetch half, and the null grid a tile without a dynamic (or static) grid walks instead
+    struct TileSample {
+        uint32_t m = 0;                    // points of the queued points query (0: none queued)
+        uint32_t fields = 0;               // SPHX_SAMPLE_* bits of the queued query
+        uint32_t win[4] = {0, 0, 0, 0};    // lattice window [0], [1]) x [2], [3]) of the queued window query (empty: nothing to fetch)
+        size_t rec_at = 0;                 // word offset of the records in sample_buf (points query)
+        uint32_t* null_grid = nullptr;     // device: BLOCK_CELLS empty ranges, then two one-entry directories (flagged / unflagged)
+    } tsample;
     uint32_t* render_buf = nullptr;  // sphx_render: one owner code per pixel (+ the outputs' device copies on the host-pointer path), grown on demand
     size_t render_cap = 0;           // ... in 4-byte words
     float* fields_buf = nullptr;  // sphx_particle_fields: the requested outputs' device copies on the host-pointer path, grown on demand

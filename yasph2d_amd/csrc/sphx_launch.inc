@@ -1741,7 +1741,7 @@ void sphx_destroy(sphx_ctx* c) {
     dev_free(&c->bpos); dev_free(&c->bpos2); dev_free(&c->bid); dev_free(&c->bid2); dev_free(&c->nb_list); dev_free(&c->nb_wave); dev_free(&c->nb_counts); dev_free(&c->nb_remote);
     dev_free(&c->scan_partials); dev_free(&c->scan_state); dev_free(&c->d_scal); dev_free(&c->tile_blk); dev_free(&c->sample_buf); dev_free(&c->render_buf); dev_free(&c->edit_buf); dev_free(&c->state_dig); dev_free(&c->mstate_buf);
     dev_free(&c->track.set_buf); dev_free(&c->track.rec); dev_free(&c->track.scratch); dev_free(&c->fields_buf);
-    dev_free(&c->stats.scratch); dev_free(&c->stats.rec);
+    dev_free(&c->stats.scratch); dev_free(&c->stats.rec); dev_free(&c->tsample.null_grid);
     free_grid(c->gdyn);
     free_grid(c->gstat);
     if (c->mbox) hipHostFree((void*)c->mbox);
@@ -2739,7 +2739,14 @@ static int sub_iteration_impl(sphx_ctx* c, int divergence, float dt, int first, 
     const uint32_t n = c->N;
     *out_err_sum = 0.0;
     if (out_n_owned) *out_n_owned = 0;
-    if (!n) return SPHX_OK;
+    if (!n) {
+        // A tile without a particle: its re-grid may still have launched a build — over the slots a halo exchange could have filled,
+        // an upper bound — and left that build's hand-off behind; the sorted count then came back as zero.  Nobody will take it: drop
+        // it here, or the warm start of a later loop finds a stale "first errors" and refuses (seen with fixed iteration counts on a
+        // strip that holds walls and no fluid).
+        c->handoff.clear();
+        return SPHX_OK;
+    }
     // what a re-grid left is for the first divergence iteration behind it (enqueue_iteration takes it), and for nobody else
     const bool refused = c->handoff.first_errors_pending() && !(divergence && first);  // sphx_sub_regrid_div has done a loop's first compute_density_change
     if (refused || !c->handoff.first_errors_pending()) c->handoff.clear();

@@ -44,6 +44,7 @@
 #include "sphx_multi_state_format.hpp"
 #include "sphx_render_merge.hpp"
 #include "sphx_render_window.hpp"
+#include "sphx_sample_window.hpp"
 #include "sphx_stats_merge.hpp"
 #include "sphx_track_merge.hpp"
 #include "sphx_track_set.hpp"
@@ -1137,6 +1138,49 @@ struct TileDriver {
         n_owned_global += n_new;
         return refresh();
     }
+
+    // sphx_multi_sample_*: a query reads position, velocity and density of ring-1 ghosts.  They are final iff valid >= 1 (velocities)
+    // and avalid >= 1 (densities) — the test step_begin() makes before its non-pressure pass.  With a ring left nothing happens; with
+    // the band spent the exchange + re-grid that step_begin() owes run now (pending_advect_dt is zero after a finished step: the
+    // step's own refresh() has applied it), and step_begin() then finds a full band.
+    int sample_band() { return need(std::min(avalid, valid) - 1); }
+    // first half: this tile's passes go onto its stream, into the context's sample scratch; nothing is waited for
+    int sample_points_enqueue(const float* xy, uint32_t n, int kind, uint32_t fields) {
+        const int rc = sphx_tile_sample_points(ctx, xy, n, kind, fields);
+        if (rc) err = std::string("sphx_tile_sample_points: ") + sphx_last_error(ctx);  // (an argument or state error of one call: nobody is waiting in an all-reduce)
+        return rc;
+    }
+    // ... second half: the records of the points this tile answered come back
+    int sample_points_fetch(uint32_t* records, uint32_t cap, uint32_t* out_n) {
+        const int rc = sphx_tile_sample_points_fetch(ctx, records, cap, out_n);
+        if (rc) err = std::string("sphx_tile_sample_points_fetch: ") + sphx_last_error(ctx);
+        return rc;
+    }
+    uint32_t sample_win[4] = {0, 0, 0, 0};  // lattice columns [0], [1]) and rows [2], [3]) of the window in flight; all zero: nothing to fetch
+    std::vector<uint32_t> sample_host;      // the window's arrays on the host (grown on demand)
+    int sample_window_enqueue(float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, int kind, uint32_t fields) {
+        const int rc = sphx_tile_sample_window(ctx, x0, y0, dx, dy, nx, ny, kind, fields, sample_win);
+        if (rc) err = std::string("sphx_tile_sample_window: ") + sphx_last_error(ctx);
+        return rc;
+    }
+    size_t sample_window_points() const { return (size_t)(sample_win[1] - sample_win[0]) * (sample_win[3] - sample_win[2]); }
+    // ... second half: the window-sized arrays come back, density | fraction | velocity | count in sample_host
+    int sample_window_fetch(uint32_t fields, sphx_sample_out* win) {
+        const size_t np = sample_window_points();
+        *win = sphx_sample_out{nullptr, nullptr, nullptr, nullptr};
+        if (!np) return SPHX_OK;
+        const size_t words = np * ((fields & SPHX_SAMPLE_FIELD_DENSITY ? 1u : 0u) + (fields & SPHX_SAMPLE_FIELD_FRACTION ? 1u : 0u) +
+                                   (fields & SPHX_SAMPLE_FIELD_VELOCITY ? 2u : 0u) + (fields & SPHX_SAMPLE_FIELD_COUNT ? 1u : 0u));
+        if (sample_host.size() < words) sample_host.resize(words);
+        uint32_t* p = sample_host.data();
+        if (fields & SPHX_SAMPLE_FIELD_DENSITY) win->density = (float*)p, p += np;
+        if (fields & SPHX_SAMPLE_FIELD_FRACTION) win->fraction = (float*)p, p += np;
+        if (fields & SPHX_SAMPLE_FIELD_VELOCITY) win->velocity = (float*)p, p += 2 * np;
+        if (fields & SPHX_SAMPLE_FIELD_COUNT) win->count = p;
+        const int rc = sphx_tile_sample_window_fetch(ctx, win);
+        if (rc) err = std::string("sphx_tile_sample_window_fetch: ") + sphx_last_error(ctx);
+        return rc;
+    }
 };
 
 // which layout for `world` tiles over these particles: 2x2 (2 x N/2) on 4 tiles, strips along the longer side otherwise
@@ -1192,6 +1236,7 @@ struct sphx_multi {
     bool uploaded = false;  // a sphx_multi_upload has succeeded: the contexts are tiles and hold a re-gridded particle set
     bool state_broken = false;  // a sphx_multi_state_load found a digest mismatch after the copy: the multi asks for an upload or a load
     sphx::TrackSet track;  // sphx_multi_track_set: the host tables of the set every local tile has installed (the map to the caller's order lives here only)
+    std::vector<uint32_t> sample_records;  // sphx_multi_sample_points: the tiles' packed records on the host (grown on demand, kept between calls)
     uint64_t next_id = 0;  // sphx_multi_append: the id the next appended record gets (sphx_multi_edit::counter_after; the same on every rank)
 
     // run f(tile, index) on every tile, each on its own host thread (the tiles meet in barriers); returns the first error
@@ -2460,6 +2505,174 @@ int sphx_multi_track_read(sphx_multi* m, uint32_t first_frame, uint32_t n_frames
             std::memcpy(out + 4 * dst, xyvv.data() + 4 * src, 16);
             if (out_tile) out_tile[dst] = tile[src];
         }
+    return SPHX_OK;
+}
+
+}  // extern "C"
+
+// ---- sampling the fields of a tiled run (include/sphx.h, "sampling the fields of a tiled run"; the device passes are
+// csrc/sphx_sample.inc, the lattice windows and the fold csrc/sphx_sample_window.hpp) ----------------------------------------------------
+namespace {
+
+namespace sh = sphx_sample_host;
+
+int sample_bad(sphx_multi* m, const char* fn, const char* what) {
+    m->err = std::string(fn) + ": " + what;
+    return SPHX_ERR_INVALID_ARGUMENT;
+}
+uint32_t sample_fields(const sphx_multi_sample_out* o) {
+    return (o->density ? (uint32_t)SPHX_SAMPLE_FIELD_DENSITY : 0u) | (o->fraction ? (uint32_t)SPHX_SAMPLE_FIELD_FRACTION : 0u) |
+           (o->velocity ? (uint32_t)SPHX_SAMPLE_FIELD_VELOCITY : 0u) | (o->count ? (uint32_t)SPHX_SAMPLE_FIELD_COUNT : 0u);
+}
+// the argument rules both calls share, in the order of the single-context calls; nullptr: they pass
+const char* sample_args_error(const sphx_multi* m, int kind, uint32_t flags, const sphx_multi_sample_out* out) {
+    if (!out) return "out is NULL";
+    if (!sample_fields(out)) return "out requests no output (density, fraction, velocity and count are NULL)";
+    if (kind != SPHX_KERNEL_WENDLAND_C2 && kind != SPHX_KERNEL_POLY6 && kind != SPHX_KERNEL_SPIKY) return "unknown kernel_kind";
+    if (flags) return "unknown flags bits (there is no device-pointer path across several devices)";
+    if (m->world > 64) return "more than 64 tiles";
+    if (m->rank_mode && !out->tile) return "out->tile is NULL in rank mode (it says which points this rank answered)";
+    return nullptr;
+}
+// every requested array zero, tile -1: the answer for a point none of the local tiles owns
+void sample_fill_absent(const sphx_multi_sample_out& o, size_t n) {
+    if (o.density) std::memset(o.density, 0, n * 4);
+    if (o.fraction) std::memset(o.fraction, 0, n * 4);
+    if (o.velocity) std::memset(o.velocity, 0, 2 * n * 4);
+    if (o.count) std::memset(o.count, 0, n * 4);
+    if (o.tile) std::fill(o.tile, o.tile + n, (int32_t)-1);
+}
+// the ghost band (TileDriver::sample_band), every tile on its own host thread: a refresh meets the other tiles in the exchange
+int sample_band(sphx_multi* m) { return m->each([](TileDriver& t, size_t) { return t.sample_band(); }); }
+int sample_tile_failed(sphx_multi* m, size_t k, int rc) {
+    m->err = "tile " + std::to_string(k) + ": " + m->tiles[k]->err;
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sphx_sample_merge(uint32_t n, const sphx_multi_sample_out* parts, uint32_t n_parts, const sphx_multi_sample_out* out) {
+    auto bad = [](const char* what) {
+        g_multi_error = std::string("sphx_sample_merge: ") + what;  // (no object to hang the message on: sphx_multi_last_error(NULL))
+        return SPHX_ERR_INVALID_ARGUMENT;
+    };
+    if (!out) return bad("out is NULL");
+    if (!sample_fields(out) && !out->tile) return bad("out requests no output (every pointer is NULL)");
+    if (n_parts && !parts) return bad("parts is NULL with n_parts > 0");
+    std::vector<sh::Part> ps(n_parts);
+    for (uint32_t p = 0; p < n_parts; ++p) {
+        const sphx_multi_sample_out& q = parts[p];
+        if (!q.tile) return bad("a part has no tile array");
+        if ((out->density && !q.density) || (out->fraction && !q.fraction) || (out->velocity && !q.velocity) || (out->count && !q.count))
+            return bad("out asks for an array a part lacks");
+        ps[p] = sh::Part{(const uint32_t*)q.density, (const uint32_t*)q.fraction, (const uint32_t*)q.velocity, q.count, q.tile};
+    }
+    sh::merge(n, ps.data(), n_parts, sh::Acc{(uint32_t*)out->density, (uint32_t*)out->fraction, (uint32_t*)out->velocity, out->count, out->tile});
+    return SPHX_OK;
+}
+
+int sphx_multi_tile_rects(const sphx_multi* m, sphx_tile_rect* out, uint32_t* inout_n) {
+    if (!m || !inout_n) return SPHX_ERR_INVALID_ARGUMENT;
+    if (!m->uploaded) return SPHX_ERR_NOT_READY;  // (the layout is made from the uploaded particles)
+    const auto rects = m->tiles[0]->layout.rects();
+    const uint32_t cap = *inout_n;
+    *inout_n = (uint32_t)rects.size();
+    if (cap < rects.size()) return SPHX_ERR_CAPACITY;
+    if (!out) return SPHX_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < rects.size(); ++k) out[k] = sphx_tile_rect{rects[k].x0, rects[k].x1, rects[k].y0, rects[k].y1};
+    return SPHX_OK;
+}
+
+int sphx_multi_ghost_rings(const sphx_multi* m, double* out3) {
+    if (!m || !out3) return SPHX_ERR_INVALID_ARGUMENT;
+    const TileDriver& t = *m->tiles[0];
+    out3[0] = t.valid, out3[1] = t.kvalid, out3[2] = t.avalid;
+    return SPHX_OK;
+}
+
+int sphx_multi_sample_points(sphx_multi* m, const float* xy, uint32_t n, int kernel_kind, uint32_t flags, const sphx_multi_sample_out* out) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    const char* const fn = "sphx_multi_sample_points";
+    if (const char* b = sample_args_error(m, kernel_kind, flags, out)) return sample_bad(m, fn, b);
+    if (n && !xy) return sample_bad(m, fn, "xy is NULL with n > 0");
+    if (n >= (1u << 31)) return sample_bad(m, fn, "n must be < 2^31");
+    if (n == 0) return SPHX_OK;
+    int rc;
+    if ((rc = multi_state_ready(m, fn, true))) return rc;
+    if ((rc = sample_band(m))) return rc;
+    const uint32_t fields = sample_fields(out);
+    // every local tile enqueues on its own stream and device first, then the records are collected: the tiles' passes overlap
+    for (size_t k = 0; k < m->tiles.size(); ++k)
+        if ((rc = m->tiles[k]->sample_points_enqueue(xy, n, kernel_kind, fields))) return sample_tile_failed(m, k, rc);
+    sample_fill_absent(*out, n);
+    if (m->sample_records.size() < 6 * (size_t)n) m->sample_records.resize(6 * (size_t)n);  // (a tile fills what it reports)
+    uint32_t* const records = m->sample_records.data();
+    for (size_t k = 0; k < m->tiles.size(); ++k) {
+        uint32_t n_rec = 0;
+        if ((rc = m->tiles[k]->sample_points_fetch(records, n, &n_rec))) return sample_tile_failed(m, k, rc);
+        const int32_t rank = (int32_t)track_tile_rank(m, k);
+        for (uint32_t r = 0; r < n_rec; ++r) {
+            const uint32_t* const w = records + 6 * (size_t)r;
+            const uint32_t i = w[0];
+            if (i >= n) {
+                m->err = std::string(fn) + ": tile " + std::to_string(k) + " returned a record outside the point set";
+                return SPHX_ERR_HIP;
+            }
+            if (out->density) std::memcpy(out->density + i, w + 1, 4);
+            if (out->fraction) std::memcpy(out->fraction + i, w + 2, 4);
+            if (out->velocity) std::memcpy(out->velocity + 2 * (size_t)i, w + 3, 8);
+            if (out->count) out->count[i] = w[5];
+            if (out->tile) out->tile[i] = rank;
+        }
+    }
+    return SPHX_OK;
+}
+
+int sphx_multi_sample_grid(sphx_multi* m, float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, int kernel_kind, uint32_t flags,
+                           const sphx_multi_sample_out* out) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    const char* const fn = "sphx_multi_sample_grid";
+    if (const char* b = sample_args_error(m, kernel_kind, flags, out)) return sample_bad(m, fn, b);
+    if (!std::isfinite(x0) || !std::isfinite(y0)) return sample_bad(m, fn, "x0 / y0 must be finite");
+    if (!std::isfinite(dx) || !(dx > 0.0f)) return sample_bad(m, fn, "dx must be finite and > 0");
+    if (!std::isfinite(dy) || !(dy > 0.0f)) return sample_bad(m, fn, "dy must be finite and > 0");
+    const uint64_t np = (uint64_t)nx * ny;
+    if (np >= (1ull << 31)) return sample_bad(m, fn, "nx * ny must be < 2^31");
+    if (np == 0) return SPHX_OK;
+    int rc;
+    if ((rc = multi_state_ready(m, fn, true))) return rc;
+    if ((rc = sample_band(m))) return rc;
+    const uint32_t fields = sample_fields(out);
+    for (size_t k = 0; k < m->tiles.size(); ++k)
+        if ((rc = m->tiles[k]->sample_window_enqueue(x0, y0, dx, dy, nx, ny, kernel_kind, fields))) return sample_tile_failed(m, k, rc);
+    if (m->rank_mode) sample_fill_absent(*out, (size_t)np);  // (in-process the windows of the tiles cover the lattice)
+    uint64_t covered = 0;
+    for (size_t k = 0; k < m->tiles.size(); ++k) {
+        TileDriver& t = *m->tiles[k];
+        sphx_sample_out win;
+        if ((rc = t.sample_window_fetch(fields, &win))) return sample_tile_failed(m, k, rc);
+        const uint32_t ix0 = t.sample_win[0], wnx = t.sample_win[1] - t.sample_win[0], iy0 = t.sample_win[2], wny = t.sample_win[3] - t.sample_win[2];
+        if (t.sample_win[1] > nx || t.sample_win[3] > ny) {
+            m->err = std::string(fn) + ": tile " + std::to_string(k) + " returned a window outside the lattice";
+            return SPHX_ERR_HIP;
+        }
+        covered += (uint64_t)wnx * wny;
+        const int32_t rank = (int32_t)track_tile_rank(m, k);
+        for (uint32_t r = 0; r < wny && wnx; ++r) {  // the window's rows into the full arrays
+            const size_t src = (size_t)r * wnx, dst = (size_t)(iy0 + r) * nx + ix0;
+            if (out->density) std::memcpy(out->density + dst, win.density + src, (size_t)wnx * 4);
+            if (out->fraction) std::memcpy(out->fraction + dst, win.fraction + src, (size_t)wnx * 4);
+            if (out->velocity) std::memcpy(out->velocity + 2 * dst, win.velocity + 2 * src, (size_t)wnx * 8);
+            if (out->count) std::memcpy(out->count + dst, win.count + src, (size_t)wnx * 4);
+            if (out->tile) std::fill(out->tile + dst, out->tile + dst + wnx, rank);
+        }
+    }
+    if (!m->rank_mode && covered != np) {  // (the rectangles partition the cell domain: the windows partition the lattice)
+        m->err = std::string(fn) + ": the tiles' windows do not cover the lattice";
+        return SPHX_ERR_HIP;
+    }
     return SPHX_OK;
 }
 

@@ -13,6 +13,8 @@ import numpy as np
 from . import _lib
 from ._lib import SphxError, SphxMultiInfo, SphxMultiOptions, SphxStepStats
 
+SAMPLE_FIELDS = ("density", "fraction", "velocity", "count")  # (yasph2d_amd.SAMPLE_FIELDS: the package imports this module lazily)
+
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
@@ -335,6 +337,60 @@ class MultiSolver:
         self._chk(self.L.sphx_multi_download_by_id(self.h, first, count, 0, C.byref(_multi_track_struct(outs)), C.byref(present)))
         outs["present"] = present.value
         return outs
+
+    # ---- sampling the fields of the tiled run (the contract is in include/sphx.h, "sampling the fields of a tiled run") ----
+    def _sample_outputs(self, fields, shape, tiles):
+        from . import _numpy_outputs, _sample_fields
+
+        outs = _numpy_outputs(_sample_fields(fields), shape)
+        if tiles or self.info()["local_tiles"] < self.info()["world"]:  # (a rank of a multi-process run: tile says what it answered)
+            outs["tile"] = np.full(shape, -1, np.int32)
+        o = _lib.SphxMultiSampleOut()
+        for f, a in outs.items():
+            setattr(o, f, a.ctypes.data or 1)  # (an empty array: a non-NULL dummy still names the field; nothing is written)
+        return outs, o
+
+    def sample(self, points, kernel=_lib.KERNEL_WENDLAND_C2, fields=SAMPLE_FIELDS, tiles=False):
+        """sphx_multi_sample_points: the fields at m query points (float32 [m, 2], numpy), each answered by the tile that owns the
+        point's cell, over that tile's own arrays — no download.  Returns {field: array} with the shapes and dtypes of
+        SphxContext.sample (host path); tiles=True adds "tile": int32 [m], the tile that answered.  If the ghost band is spent, the
+        halo exchange the next step owes happens now (collective in rank mode: every rank calls with the same points).  Rank mode:
+        this rank's part — zeros and tile -1 for the points other ranks answer ("tile" is always returned); fold the ranks' parts
+        with yasph2d_amd.sample_merge."""
+        pts = np.ascontiguousarray(points, np.float32)
+        if pts.ndim != 2 or pts.shape[1] != 2:
+            raise ValueError("points must be a float32 [m, 2] array, not shape %s" % (pts.shape,))
+        outs, o = self._sample_outputs(fields, (len(pts),), tiles)
+        self._chk(self.L.sphx_multi_sample_points(self.h, _p(pts), len(pts), kernel, 0, C.byref(o)))
+        return outs
+
+    def sample_grid(self, origin, spacing, shape, kernel=_lib.KERNEL_WENDLAND_C2, fields=SAMPLE_FIELDS, tiles=False):
+        """sphx_multi_sample_grid: the fields on the lattice origin + (ix * dx, iy * dy) (fp32, unfused), shape = (ny, nx), row 0 at
+        origin[1]; arguments and result as SphxContext.sample_grid, bit-identical to sample() at the same fp32 points.  Every tile
+        walks only the index rectangle of the lattice it owns.  tiles, the ghost band and rank mode: as sample()."""
+        dx, dy = (spacing, spacing) if np.ndim(spacing) == 0 else spacing
+        ny, nx = (int(v) for v in shape)
+        if nx < 0 or ny < 0:
+            raise ValueError("shape must be (ny, nx) with non-negative sizes")
+        outs, o = self._sample_outputs(fields, (ny, nx), tiles)
+        self._chk(self.L.sphx_multi_sample_grid(self.h, origin[0], origin[1], dx, dy, nx, ny, kernel, 0, C.byref(o)))
+        return outs
+
+    def tile_rects(self):
+        """sphx_multi_tile_rects -> uint32 [world, 4]: the owned cell rectangle (x0, x1, y0, y1), half-open, of every tile in rank order."""
+        n = C.c_uint32(self.info()["world"])
+        arr = (_lib.SphxTileRect * max(n.value, 1))()
+        rc = self.L.sphx_multi_tile_rects(self.h, arr, C.byref(n))
+        if rc:
+            raise SphxError(rc, "sphx_multi_tile_rects: no layout before the first upload" if rc == _lib.ERR_NOT_READY else "sphx_multi_tile_rects")
+        return np.array([(r.x0, r.x1, r.y0, r.y1) for r in arr[:n.value]], np.uint32).reshape(-1, 4)
+
+    def ghost_rings(self):
+        """sphx_multi_ghost_rings -> dict(valid, kvalid, avalid): the ring budget of local tile 0 (rings of ghosts, counted from the
+        owned region, in which velocities / warm-start sums / densities are still exact; inf on a one-tile run)."""
+        out = (C.c_double * 3)()
+        self._chk(self.L.sphx_multi_ghost_rings(self.h, out))
+        return dict(valid=out[0], kvalid=out[1], avalid=out[2])
 
     # ---- picture of the tiled run (the contract is in include/sphx.h, "picture of a tiled run") ----
     @staticmethod
