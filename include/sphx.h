@@ -73,7 +73,9 @@ extern "C" {
                             *    _fetch / _window_enqueue / _window_fetch / _record / _frame / _read
                             * 5 (additive): sphx_multi_sample_points, sphx_multi_sample_grid, sphx_multi_sample_out, sphx_sample_merge,
                             *    sphx_multi_tile_rects, sphx_multi_ghost_rings, sphx_tile_sample_points / _points_fetch / _window /
-                            *    _window_fetch, SPHX_SAMPLE_FIELD_* */
+                            *    _window_fetch, SPHX_SAMPLE_FIELD_*
+                            * 5 (additive): sphx_multi_particle_fields, sphx_multi_fields_out, sphx_tile_owned_count,
+                            *    sphx_tile_particle_fields_enqueue / _fetch, SPHX_FIELD_* */
 
 /* ---- status codes ---- */
 enum {
@@ -481,7 +483,8 @@ int sphx_download_by_id(sphx_ctx* ctx, uint32_t first_id, uint32_t count, uint32
  *   step of either solver that ran a neighbour build (not one over zero fluid particles), after sphx_update_neighborhood followed by
  *   sphx_update_densities, and after a sphx_state_load of such a state.  After sphx_upload, sphx_set_boundary, sphx_append / sphx_remove (that
  *   changed something), between a step_begin and its step_finish and after a failed step: SPHX_ERR_NOT_READY, with the messages of sampling.
- *   A tile context (sphx_tile_*, sphx_multi_tile_ctx) is refused with SPHX_ERR_INVALID_ARGUMENT; sphx_multi_* has no counterpart.
+ *   A tile context (sphx_tile_*, sphx_multi_tile_ctx) is refused with SPHX_ERR_INVALID_ARGUMENT; a tiled run is served by
+ *   sphx_multi_particle_fields ("per-particle flow fields of a tiled run", below).
  * Argument errors (SPHX_ERR_INVALID_ARGUMENT, the message names the argument): ctx or out NULL, every output NULL, unknown flag bits.
  *   n == 0 in a ready context is a successful no-op.
  * No side effects: the call only reads (it restores the sweep direction a launch toggles and leaves a queued run-ahead pass valid); a run
@@ -1022,6 +1025,61 @@ int sphx_tile_sample_points_fetch(sphx_ctx* tile_ctx, uint32_t* records /* host,
 int sphx_tile_sample_window(sphx_ctx* tile_ctx, float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, int kernel_kind, uint32_t fields,
                             uint32_t* out_window /* [4] */);
 int sphx_tile_sample_window_fetch(sphx_ctx* tile_ctx, const sphx_sample_out* out /* host, window-sized */);
+
+/* ---- per-particle flow fields of a tiled run (csrc/sphx_fields.inc, csrc/sphx_tiles.cpp) --------------------------------
+ * sphx_particle_fields for a sphx_multi: velocity gradient, divergence, vorticity and colour-field gradient at every particle the local
+ * tiles own, without a download and a second context.  A tile holds what the query needs: an owned particle's neighbour list is complete,
+ * and the ghost band carries its neighbours' position, velocity and density.
+ * What it computes: for every particle a local tile owns (bit 31 of its id word) the contract of sphx_particle_fields applies word for
+ *   word, evaluated over THAT TILE'S OWN ARRAYS, ghosts included: the list is the one sphx_download_neighbors on sphx_multi_tile_ctx
+ *   returns for the particle, positions, velocities and densities are the bits sphx_download on that tile context returns, "boundary"
+ *   means the tile's clipped boundary set; the fp32 order of operations is unchanged and a capped list stays capped.  A ghost is never
+ *   answered and never written (its list is not complete).  Any subset of the outputs gives the same bits as the full set.
+ * Order of the output: that of sphx_multi_download — the local tiles in order, within a tile the owned particles in the tile's device
+ *   order.  *inout_n: capacity in (entries), count out.  Entry k lines up with entry k of a sphx_multi_download made AFTER the call and
+ *   before the next step — not with one made before it, because the call may re-grid (the ghost band, below).  out->ids (the particle id
+ *   of entry k, 31 bits) is always the safe key; out->tile is the global rank of the tile that owns entry k.
+ * Consequences: (a) in every mode the result is bit-identical to tests/fields_reference.py::fields32 over the answering tile's own
+ *   downloads; (b) in tiling-invariant mode (sphx_set_tiling_invariant) it is bit-identical to sphx_particle_fields of a single context
+ *   in the same mode, matched by id.
+ * The ghost band: the precondition of tiled sampling (above) — ring-1 ghosts must hold final position, velocity and density, i.e.
+ *   need(min(avalid, valid) - 1), tested before any tile enqueues.  A ring is left: the call only reads (the sweep direction is put back,
+ *   a queued run-ahead pass stays valid).  The band is spent: the halo exchange and re-grid the next sphx_multi_step_begin owes happen
+ *   NOW; in this case alone sphx_multi_info().exchanges moves one earlier.  Because of that exchange the call is COLLECTIVE in rank mode.
+ *   A run with calls between its steps is bit-identical to one without: every sphx_step_stats field, every sphx_multi_state_digest word,
+ *   the rebalances.
+ * When allowed: after sphx_multi_upload (its warm-up block leaves lists and densities for the uploaded positions), after
+ *   sphx_multi_state_load, after every finished step, after sphx_multi_append / _remove (they end in a re-grid).  SPHX_ERR_NOT_READY
+ *   before the first upload, between sphx_multi_step_begin and _finish, on a multi a failed sphx_multi_state_load left broken and on one
+ *   whose collective step has failed.  SPHX_ERR_INVALID_ARGUMENT (sphx_multi_last_error names the argument): m, out or inout_n NULL, all
+ *   four field pointers NULL, any flags bit (there is no device-pointer path across several devices).  SPHX_ERR_CAPACITY: *inout_n is
+ *   smaller than the owned count of the local tiles; *inout_n receives that count and no output is written — the test comes after the
+ *   band check and before any walk (each tile counts its owned particles on its device: 4 bytes per local particle).  A refused call
+ *   touches no tile.  Zero owned particles is a successful no-op with *inout_n = 0.
+ * Rank mode (sphx_multi_create_rank): each rank returns its own tile's part; the whole answer is the parts concatenated in rank order.
+ *   No merge function is needed: no particle has two owners.
+ * Device work per tile: a counting pass over the id words (owned lanes per wavefront and per 256-slot piece), the exclusive scan of the
+ *   pieces, and the walk of sphx_particle_fields in its owned-only form — a piece without an owned particle leaves at once, a ghost
+ *   stages and walks nothing, an owned particle writes at its place among the owned ones (no atomic: two calls give the same bytes in
+ *   the same places).  Only the owned entries come back.
+ * One tile (INTERNAL, like the other sphx_tile_* calls; accepted only on a tile context): sphx_tile_owned_count runs count + scan and
+ *   returns the owned count; sphx_tile_particle_fields_enqueue queues count, scan and walk for the fields named by SPHX_FIELD_* bits into
+ *   a scratch of the tile (grown on demand, freed in sphx_destroy; want_ids: the ids too), _fetch copies back *out_n owned entries (out
+ *   names exactly the queued fields; more than cap: SPHX_ERR_CAPACITY with *out_n set).  SPHX_ERR_NOT_READY between a halo exchange and
+ *   the tile's re-grid. */
+enum { SPHX_FIELD_VEL_GRAD = 1u, SPHX_FIELD_DIVERGENCE = 2u, SPHX_FIELD_VORTICITY = 4u, SPHX_FIELD_COLOR_GRAD = 8u };
+typedef struct sphx_multi_fields_out {   /* host arrays */
+    float* vel_grad;    /* [4n] or NULL */
+    float* divergence;  /* [n]  or NULL */
+    float* vorticity;   /* [n]  or NULL */
+    float* color_grad;  /* [2n] or NULL */      /* not all four NULL */
+    uint32_t* ids;      /* [n] or NULL: particle id of entry k (31 bits) */
+    int32_t* tile;      /* [n] or NULL: global rank of the tile that owns entry k */
+} sphx_multi_fields_out;
+int sphx_multi_particle_fields(sphx_multi* m, uint32_t flags /* 0 */, const sphx_multi_fields_out* out, uint64_t* inout_n);
+int sphx_tile_owned_count(sphx_ctx* tile_ctx, uint32_t* out_owned);
+int sphx_tile_particle_fields_enqueue(sphx_ctx* tile_ctx, uint32_t field_mask, uint32_t want_ids);
+int sphx_tile_particle_fields_fetch(sphx_ctx* tile_ctx, const sphx_fields_out* out /* host */, uint32_t* ids /* host or NULL */, uint32_t cap, uint32_t* out_n);
 /* Solver::simulation_step(&mut world, &mut time_manager) (solver/mod.rs:17) in ONE call: phase A, the TimeManager mirror
  * (simulation_step() dfsph.rs:433, update_simulation_step dfsph.rs:478-480), phase B */
 struct sphx_timer;

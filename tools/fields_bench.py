@@ -2,7 +2,7 @@
 """Cost of the per-particle flow fields (sphx_particle_fields) on the bench scene (the 16 M dam break), next to the walk they are modelled
 on: the step's non-pressure pass (k_nonpressure<XSPH>, label nonpressure_accel_vmax), measured in the same run.
 
-  tools/fields_bench.py [--particles 16000000] [--warmup 40] [--steps 40] [--calls 25]
+  tools/fields_bench.py [--particles 16000000] [--warmup 40] [--steps 40] [--calls 25] [--tiles K]
 
 As tools/sample_bench.py: a scratch context keeps the GPU busy until the context's first step is queued, then --warmup untimed steps
 settle the flow.  Measured on that settled state:
@@ -11,7 +11,11 @@ settle the flow.  Measured on that settled state:
     per call = the hipEvent bracket of its one launch, median of --calls calls;
   * the host path's wall time for all outputs (the 32 bytes per particle cross to the host), median of --calls calls.
 The estimate stated before the measurement: all outputs cost at most 1.5 x the non-pressure pass (the same staged record, walked over
-count_total instead of count_dynamic entries, 32 bytes written per particle instead of 8).  Prints one JSON line."""
+count_total instead of count_dynamic entries, 32 bytes written per particle instead of 8).  Prints one JSON line.
+--tiles K measures the tiled call instead (sphx_multi_particle_fields, K tiles on device 0) after warmup + steps + steps steps: per call
+the host wall time, the device time of count + scan and of the walks summed over the tiles (sphx_profile_* of the tile contexts) and the
+bytes that come back.  The expectation: at K = 1 the walk costs what k_particle_fields costs plus a 4-byte id
+read per particle, and the count + scan on top."""
 import argparse
 import json
 import os
@@ -60,6 +64,73 @@ def timed(ctx, calls, fn):
     return float(np.median(dev)), float(np.median(wall))
 
 
+COUNT_SCAN = ("tile_fields_count", "tile_fields_scan")
+WALK = "tile_particle_fields"
+
+
+def tiled(args):
+    """sphx_multi_particle_fields on K tiles of device 0 after warmup + steps + steps steps: per call (medians of --calls calls) the
+    host wall time, the device time of count + scan (both rounds: the capacity check and the queued pass) and of the walks, summed over
+    the tiles, and the bytes that come back; next to the wall time of the sphx_multi_download a second context would start from"""
+    from yasph2d_amd.multi import MultiSolver
+
+    w = scene(args.particles)
+    m = MultiSolver(y.default_params(), devices=[0] * args.tiles)
+    m.set_boundary(w.boundary_particles)
+    m.upload(np.ascontiguousarray(w.positions, np.float32))
+    t = y.TimeManager()
+    m.steps(t, args.warmup)
+    m.synchronize()
+    t0 = time.perf_counter()
+    m.steps(t, args.steps)
+    m.synchronize()
+    ms_step = (time.perf_counter() - t0) * 1e3 / args.steps
+    m.steps(t, args.steps)
+    m.synchronize()
+    tiles = [m.tile_context(k) for k in range(args.tiles)]
+    local = [c.n for c in tiles]
+    before = m.info()["exchanges"]
+    n = len(m.fields("divergence")["ids"])  # (grows the scratch; refreshes a spent band once)
+    out = dict(particles=n, tiles=args.tiles, warmup=args.warmup, steps=args.steps, calls=args.calls, ms_per_step=ms_step, local_particles=local,
+               ghost_fraction=float(sum(local) - n) / max(sum(local), 1), ghost_rings=m.ghost_rings())
+    sets = (("all_outputs", tuple(SHAPE), 32), ("velocity_gradient_only", ("vel_grad", "divergence", "vorticity"), 24), ("color_grad_only", ("color_grad",), 8))
+    for name, fields, _ in sets:  # pass 1, profiler off: the wall time of the whole host call
+        m.fields(fields)
+        wall = []
+        for _ in range(args.calls):
+            t0 = time.perf_counter()
+            m.fields(fields)
+            wall.append((time.perf_counter() - t0) * 1e6)
+        out[name] = dict(call_wall_us=float(np.median(wall)))
+    for c in tiles:  # pass 2, profiler on: the device time of every tile's launches
+        c.profile_reset()
+        c.profile_filter(None)
+        c.profile_enable(True)
+    for name, fields, width in sets:
+        cs, walk = [], []
+        for _ in range(args.calls):
+            for c in tiles:
+                c.profile_reset()
+            m.fields(fields)
+            m.synchronize()
+            prof = [c.profile_get() for c in tiles]
+            cs.append(sum(p[lab]["total_ms"] * 1e3 for p in prof for lab in COUNT_SCAN if lab in p))
+            walk.append(sum(p[WALK]["total_ms"] * 1e3 for p in prof if WALK in p))
+        out[name].update(count_scan_us=float(np.median(cs)), walk_us=float(np.median(walk)), bytes_back=(width + 4) * n,
+                         particles_per_s=n / (float(np.median(walk)) * 1e-6))
+    for c in tiles:
+        c.profile_enable(False)
+    wall = []
+    for _ in range(max(3, args.calls // 5)):
+        t0 = time.perf_counter()
+        m.download()
+        wall.append((time.perf_counter() - t0) * 1e6)
+    out["multi_download_us"] = float(np.median(wall))
+    out["exchanges_caused"] = m.info()["exchanges"] - before
+    m.close()
+    print(json.dumps(out))
+
+
 def main():
     import torch
 
@@ -68,7 +139,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=40)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--calls", type=int, default=25)
+    ap.add_argument("--tiles", type=int, default=0, help="measure sphx_multi_particle_fields on this many tiles of device 0 instead")
     args = ap.parse_args()
+    if args.tiles:
+        tiled(args)
+        return
     stop = threading.Event()
     th = threading.Thread(target=busy, args=(stop, args.particles), daemon=True)
     th.start()

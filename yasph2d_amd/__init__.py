@@ -1258,6 +1258,10 @@ class DFSPHMultiSolver(DFSPHSolver):
     def sample_grid(self, origin, spacing, shape, kernel=KERNEL_WENDLAND_C2, fields=SAMPLE_FIELDS, tiles=False):
         return self.multi().sample_grid(origin, spacing, shape, kernel, fields, tiles)
 
+    # per-particle flow fields of the tiled run (MultiSolver.fields: computed by the tiles over their own arrays, no download)
+    def fields(self, fields=FIELD_NAMES, by_id=False):
+        return self.multi().fields(fields, by_id)
+
     # following particles by id (MultiSolver.track and friends; the recorder fires behind every step of simulation_steps(k))
     def track(self, ids):
         self.multi().track(ids)

@@ -158,6 +158,14 @@ class SphxFieldsOut(C.Structure):
     _fields_ = [("vel_grad", C.c_void_p), ("divergence", C.c_void_p), ("vorticity", C.c_void_p), ("color_grad", C.c_void_p)]
 
 
+FIELD_BITS = dict(vel_grad=1, divergence=2, vorticity=4, color_grad=8)  # SPHX_FIELD_* (sphx_tile_particle_fields_*)
+
+
+class SphxMultiFieldsOut(C.Structure):  # sphx_multi_fields_out: host pointers
+    _fields_ = [("vel_grad", C.c_void_p), ("divergence", C.c_void_p), ("vorticity", C.c_void_p), ("color_grad", C.c_void_p),
+                ("ids", C.c_void_p), ("tile", C.c_void_p)]
+
+
 STATS_DEVICE_POINTERS = 1  # sphx_fluid_stats flags
 STATS_MAX_RECTS = 8
 
@@ -303,6 +311,10 @@ SIGNATURES = {
     "sphx_tile_sample_points_fetch": (_i, [_vp, _vp, _u32, C.POINTER(_u32)]),
     "sphx_tile_sample_window": (_i, [_vp, _f, _f, _f, _f, _u32, _u32, _i, _u32, C.POINTER(_u32)]),
     "sphx_tile_sample_window_fetch": (_i, [_vp, C.POINTER(SphxSampleOut)]),
+    "sphx_multi_particle_fields": (_i, [_vp, _u32, C.POINTER(SphxMultiFieldsOut), C.POINTER(C.c_uint64)]),
+    "sphx_tile_owned_count": (_i, [_vp, C.POINTER(_u32)]),
+    "sphx_tile_particle_fields_enqueue": (_i, [_vp, _u32, _u32]),
+    "sphx_tile_particle_fields_fetch": (_i, [_vp, C.POINTER(SphxFieldsOut), _vp, _u32, C.POINTER(_u32)]),
     "sphx_render_fit": (_i, [_u32, _u32, _f, _f, _f, _f, C.POINTER(SphxRenderView)]),
     "sphx_render": (_i, [_vp, C.POINTER(SphxRenderView), _u32, C.POINTER(SphxRenderOut)]),
     "sphx_multi_render": (_i, [_vp, C.POINTER(SphxRenderView), _u32, C.POINTER(SphxRenderOut)]),

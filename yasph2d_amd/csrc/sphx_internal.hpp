@@ -403,6 +403,14 @@ struct sphx_ctx {
     size_t render_cap = 0;           // ... in 4-byte words
     float* fields_buf = nullptr;  // sphx_particle_fields: the requested outputs' device copies on the host-pointer path, grown on demand
     size_t fields_cap = 0;        // ... in 4-byte words
+    // sphx_tile_particle_fields_* (a tile context; fields_buf is its scratch too — sphx_particle_fields refuses a tile): the query in
+    // flight between the enqueue half and the fetch half
+    struct TileFields {
+        bool queued = false;   // an enqueue has run and no fetch since
+        uint32_t n = 0;        // local count (owned + ghosts) of the queued pass
+        uint32_t mask = 0;     // SPHX_FIELD_* bits of the queued pass
+        bool ids = false;      // ... and whether it writes the ids
+    } tfields;
     uint32_t num_density_iters = 1, num_divergence_iters = 0;  // dfsph.rs:51,55
     float step_dt_prev = 0, step_vmax = 0;
     uint32_t step_flags = 0;

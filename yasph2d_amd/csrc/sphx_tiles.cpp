@@ -2677,3 +2677,64 @@ int sphx_multi_sample_grid(sphx_multi* m, float x0, float y0, float dx, float dy
 }
 
 }  // extern "C"
+
+// ---- per-particle flow fields of a tiled run (include/sphx.h, "per-particle flow fields of a tiled run"; the device passes are
+// csrc/sphx_fields.inc) -------------------------------------------------------------------------------------------------------------------
+extern "C" {
+
+int sphx_multi_particle_fields(sphx_multi* m, uint32_t flags, const sphx_multi_fields_out* out, uint64_t* inout_n) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    const char* const fn = "sphx_multi_particle_fields";
+    if (!out) return sample_bad(m, fn, "out is NULL");
+    if (!inout_n) return sample_bad(m, fn, "inout_n is NULL");
+    const uint32_t mask = (out->vel_grad ? (uint32_t)SPHX_FIELD_VEL_GRAD : 0u) | (out->divergence ? (uint32_t)SPHX_FIELD_DIVERGENCE : 0u) |
+                          (out->vorticity ? (uint32_t)SPHX_FIELD_VORTICITY : 0u) | (out->color_grad ? (uint32_t)SPHX_FIELD_COLOR_GRAD : 0u);
+    if (!mask) return sample_bad(m, fn, "out requests no output (vel_grad, divergence, vorticity and color_grad are NULL)");
+    if (flags) return sample_bad(m, fn, "unknown flags bits (there is no device-pointer path across several devices)");
+    int rc;
+    if ((rc = multi_state_ready(m, fn, true))) return rc;
+    if ((rc = sample_band(m))) return rc;
+    // the capacity, before any walk: every tile counts what it owns on its device (the host's count lags a migration)
+    std::vector<uint32_t> owned(m->tiles.size(), 0u);
+    uint64_t total = 0;
+    for (size_t k = 0; k < m->tiles.size(); ++k) {
+        if ((rc = sphx_tile_owned_count(m->tiles[k]->ctx, &owned[k]))) {
+            m->tiles[k]->err = std::string("sphx_tile_owned_count: ") + sphx_last_error(m->tiles[k]->ctx);
+            return sample_tile_failed(m, k, rc);
+        }
+        total += owned[k];
+    }
+    const uint64_t cap = *inout_n;
+    *inout_n = total;
+    if (cap < total) {
+        m->err = std::string(fn) + ": *inout_n is smaller than the " + std::to_string(total) + " particles the local tiles own";
+        return SPHX_ERR_CAPACITY;
+    }
+    if (!total) return SPHX_OK;
+    // every local tile enqueues on its own stream and device first, then the parts are collected: the tiles' passes overlap
+    for (size_t k = 0; k < m->tiles.size(); ++k)
+        if (owned[k] && (rc = sphx_tile_particle_fields_enqueue(m->tiles[k]->ctx, mask, out->ids ? 1u : 0u))) {
+            m->tiles[k]->err = std::string("sphx_tile_particle_fields_enqueue: ") + sphx_last_error(m->tiles[k]->ctx);
+            return sample_tile_failed(m, k, rc);
+        }
+    uint64_t at = 0;
+    for (size_t k = 0; k < m->tiles.size(); ++k) {
+        if (!owned[k]) continue;
+        const sphx_fields_out part{out->vel_grad ? out->vel_grad + 4 * at : nullptr, out->divergence ? out->divergence + at : nullptr,
+                                   out->vorticity ? out->vorticity + at : nullptr, out->color_grad ? out->color_grad + 2 * at : nullptr};
+        uint32_t got = 0;
+        if ((rc = sphx_tile_particle_fields_fetch(m->tiles[k]->ctx, &part, out->ids ? out->ids + at : nullptr, owned[k], &got))) {
+            m->tiles[k]->err = std::string("sphx_tile_particle_fields_fetch: ") + sphx_last_error(m->tiles[k]->ctx);
+            return sample_tile_failed(m, k, rc);
+        }
+        if (got != owned[k]) {
+            m->err = std::string(fn) + ": tile " + std::to_string(k) + " answered another number of particles than it counted";
+            return SPHX_ERR_HIP;
+        }
+        if (out->tile) std::fill(out->tile + at, out->tile + at + got, (int32_t)track_tile_rank(m, k));
+        at += got;
+    }
+    return SPHX_OK;
+}
+
+}  // extern "C"

@@ -376,6 +376,37 @@ class MultiSolver:
         self._chk(self.L.sphx_multi_sample_grid(self.h, origin[0], origin[1], dx, dy, nx, ny, kernel, 0, C.byref(o)))
         return outs
 
+    # ---- per-particle flow fields of the tiled run (the contract is in include/sphx.h, "per-particle flow fields of a tiled run") ----
+    def fields(self, fields=None, by_id=False):
+        """sphx_multi_particle_fields: velocity gradient, divergence, vorticity and colour-field gradient (SphxContext.fields) at every
+        particle the local tiles own, each computed by its tile over the tile's own arrays — no download, no second context.  Returns
+        {name: numpy float32 array} for the requested `fields` (default: yasph2d_amd.FIELD_NAMES; shapes as SphxContext.fields) plus
+        "ids" (uint32 [n]: the particle id of row k) and "tile" (int32 [n]: the tile that owns it).  Row k belongs to row k of a
+        download() made AFTER the call and before the next step; by_id=True sorts the rows by id on the host instead.  If the ghost
+        band is spent, the halo exchange the next step owes happens now (collective in rank mode).  Rank mode: this rank's part; the
+        whole answer is the ranks' parts concatenated in rank order."""
+        from . import _FIELD_SHAPE, FIELD_NAMES, _field_names
+
+        names = _field_names(FIELD_NAMES if fields is None else fields)
+        n = C.c_uint64(self.L.sphx_multi_num_owned(self.h) + 1024)
+        for _ in range(2):  # (the host's owned count lags a migration: the call reports the count it needs)
+            cap = n.value
+            outs = {f: np.zeros((cap,) + _FIELD_SHAPE[f], np.float32) for f in names}
+            outs["ids"], outs["tile"] = np.zeros(cap, np.uint32), np.zeros(cap, np.int32)
+            o = _lib.SphxMultiFieldsOut()
+            for f, a in outs.items():
+                setattr(o, f, a.ctypes.data or 1)
+            rc = self.L.sphx_multi_particle_fields(self.h, 0, C.byref(o), C.byref(n))
+            if rc != _lib.ERR_CAPACITY:
+                break
+        self._chk(rc)
+        k = n.value
+        outs = {f: a[:k] for f, a in outs.items()}
+        if by_id:
+            order = np.argsort(outs["ids"], kind="stable")
+            outs = {f: a[order] for f, a in outs.items()}
+        return outs
+
     def tile_rects(self):
         """sphx_multi_tile_rects -> uint32 [world, 4]: the owned cell rectangle (x0, x1, y0, y1), half-open, of every tile in rank order."""
         n = C.c_uint32(self.info()["world"])
