@@ -116,6 +116,7 @@ def lib(omp=False):
         "orc_phase_seconds": (i32, [C.POINTER(C.c_double), i32]),
         "orc_phase_reset": (None, []),
         "orc_dfsph_set_tolerances": (None, [vp, f32, u32, f32, u32]),
+        "orc_set_xsph_epsilon": (None, [vp, f32]),
         "orc_dfsph_clear_cached": (None, [vp]),
         "orc_dfsph_step": (None, [vp, C.POINTER(StepStats)]),
         "orc_wcsph_clear_cached": (None, [vp]),
@@ -206,6 +207,15 @@ class Oracle:
 
     def set_fixed_iterations(self, nd, nv):
         self.L.orc_dfsph_set_fixed_iterations(self.h, nd, nv)
+
+    def set_tolerances(self, max_avg_density_error, max_density_iterations, max_divergence_error, max_divergence_iterations):
+        """The DFSPH stop tests (dfsph.rs:49-55: 0.01 % / 200 and 0.1 % / 400 in the reference app)."""
+        self.L.orc_dfsph_set_tolerances(self.h, max_avg_density_error, max_density_iterations, max_divergence_error,
+                                        max_divergence_iterations)
+
+    def set_xsph_epsilon(self, epsilon):
+        """XSPHViscosityModel::epsilon of the DFSPH and the WCSPH solver (xsph.rs:14: 0.05 unless set)."""
+        self.L.orc_set_xsph_epsilon(self.h, epsilon)
 
     def set_tiling_invariant(self, on=True):
         """NOT the reference's behaviour (sphx_set_tiling_invariant's twin): the particles of a cell are ordered by persistent id and the

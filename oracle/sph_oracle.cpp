@@ -1427,6 +1427,11 @@ void orc_dfsph_set_tolerances(OrcSim* s, float max_avg_density_error, uint32_t m
     s->dfsph.max_divergence_error = max_divergence_error;
     s->dfsph.max_num_divergence_correction_iterations = max_divergence_iters;
 }
+// XSPHViscosityModel::epsilon (xsph.rs:14) of both solvers; orc_create leaves it at the reference app's 0.05
+void orc_set_xsph_epsilon(OrcSim* s, float epsilon) {
+    s->dfsph.viscosity_model.epsilon = epsilon;
+    s->wcsph.viscosity_model.epsilon = epsilon;
+}
 void orc_dfsph_clear_cached(OrcSim* s) { s->dfsph.clear_cached_data(); }
 void orc_dfsph_step(OrcSim* s, StepStats* out) {
     s->dfsph.simulation_step(s->world, s->timer, s->last);

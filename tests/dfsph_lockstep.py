@@ -22,10 +22,11 @@ WHOLE_DOMAIN = (0, 65536, 0, 65536)
 PARTICLE_DENSITY = 10000.0  # the default_params() argument the parameter block was made with
 
 
-def restatement():
+def restatement(params=None, particle_density=PARTICLE_DENSITY):
+    """The restatement for a parameter block and the particle density it was made with (default: the reference app's)."""
     import yasph2d_amd as y
 
-    return Restatement.from_params(y.default_params(), PARTICLE_DENSITY)
+    return Restatement.from_params(y.default_params() if params is None else params, particle_density)
 
 
 class Bounds:
@@ -102,13 +103,15 @@ def single_tile(backend, pos, vel, boundary, kappa=None, stiffness=None):
     return boundary
 
 
-def make_plan(steps, fixed=(3, 2), dts=((0.003, 0.002), (0.002, 0.0025), (0.0025, 0.0015)), warm_from=1, fuse_predict=False, regrid="plain"):
+def make_plan(steps, fixed=(3, 2), dts=((0.003, 0.002), (0.002, 0.0025), (0.0025, 0.0015)), warm_from=1, fuse_predict=False, regrid="plain",
+              dt_scale=1.0):
     """Sub-steps of `steps` DFSPH steps (TiledDFSPH.step order).  Warm starts fire from step `warm_from` on (both loops).  regrid:
-    "plain" (sphx_sub_regrid), or the device's fused forms "fused" (_div before a cold divergence loop, _warm before a warm one)."""
+    "plain" (sphx_sub_regrid), or the device's fused forms "fused" (_div before a cold divergence loop, _warm before a warm one).
+    dt_scale: factor on `dts` (particle spacing / 0.01 for a parameter set of another resolution)."""
     nd, nv = fixed
     plan = [("regrid",)]
     for s in range(steps):
-        dt_prev, dt = (np.float32(x) for x in dts[s % len(dts)])
+        dt_prev, dt = (np.float32(x) * np.float32(dt_scale) for x in dts[s % len(dts)])
         warm = s >= warm_from
         plan.append(("nonpressure", dt_prev))
         if fuse_predict and not warm:
@@ -292,7 +295,7 @@ def check_trace(trace, ref, bounds, where="", rows=None):
     return bounds
 
 
-def check_membership(s, h, sample=64, seed=0):
+def check_membership(s, h, sample=64, seed=0, grid_min=(-100.0, -100.0)):
     """For a seeded sample of particles: an uncapped list is exactly the brute-force set of the reference rule, dynamic entries
     ascending then static entries ascending; a capped list (64 entries) holds members of it only."""
     counts, lists = s["counts"], s["lists"]
@@ -301,7 +304,8 @@ def check_membership(s, h, sample=64, seed=0):
     n = len(counts)
     rng = np.random.default_rng(seed)
     # not in the domain's rim cells, where the reference's neighbour box wraps (neighborhood_search.rs:193-194: pos.x - 1 at x = 0)
-    lo, hi = np.float32(-100.0 + 2 * h), np.float32(-100.0 + 65534 * h)
+    gm = np.asarray(grid_min, np.float64)
+    lo, hi = (gm + 2 * h).astype(np.float32), (gm + 65534 * h).astype(np.float32)
     inner = np.nonzero(((s["pos"] > lo) & (s["pos"] < hi)).all(1))[0]
     picks = rng.choice(inner, min(sample, len(inner)), replace=False) if len(inner) else []
     for i in picks:
@@ -315,10 +319,10 @@ def check_membership(s, h, sample=64, seed=0):
             assert np.isin(entries[:nd], dyn).all() and np.isin(entries[nd:], stat).all(), f"particle {i}: capped list has non-members"
 
 
-def membership_of_trace(trace, h, seed=0):
+def membership_of_trace(trace, h, seed=0, grid_min=(-100.0, -100.0)):
     for op, _, _, post in trace:
         if op[0].startswith("regrid"):
-            check_membership(post, h, seed=seed)
+            check_membership(post, h, seed=seed, grid_min=grid_min)
 
 
 # ---------------------------------------------------------------------------------------------------------------------- mutants
@@ -416,11 +420,11 @@ MUTANTS = [DropLastEntry, BoundaryScaled, AlphaWithoutMass, DensityErrorWithDtPr
            GradientNormH3, GradientSquare, NoWarmStartDamping]
 
 
-def mutant(cls):
+def mutant(cls, params=None, particle_density=PARTICLE_DENSITY):
     import yasph2d_amd as y
 
-    p = y.default_params()
-    return cls(p.smoothing_length, p.fluid_density, PARTICLE_DENSITY, tuple(p.gravity))
+    p = y.default_params() if params is None else params
+    return cls(p.smoothing_length, p.fluid_density, particle_density, tuple(p.gravity))
 
 
 # ------------------------------------------------------------------------------------------------------------------ whole steps

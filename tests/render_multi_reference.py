@@ -15,6 +15,7 @@ NONE, BOUNDARY = rr.NONE, rr.BOUNDARY
 OWNED = np.uint32(0x80000000)
 PARTICLE_RADIUS = F(0.005)  # default_params(): particle_radius = 0.5 / sqrt(particle_density)
 SMOOTHING_LENGTH = F(0.02)
+GRID_MIN = (-100.0, -100.0)
 
 
 def morton(cx, cy):
@@ -29,16 +30,21 @@ def morton(cx, cy):
     return (part1by1(cy) << np.uint32(1)) | part1by1(cx)
 
 
-def cell_keys(pos):
+def _cells(pos, h, grid_min):
+    return cell_coord(pos, 0, grid_min[0], h=h), cell_coord(pos, 1, grid_min[1], h=h)
+
+
+def cell_keys(pos, h=SMOOTHING_LENGTH, grid_min=GRID_MIN):
     """morton(cell_of(x)) per particle: the grid's fp32 cell function (tiles_reference.cell_coord) and the encode above"""
     pos = np.asarray(pos, F).reshape(-1, 2)
-    return morton(cell_coord(pos, 0), cell_coord(pos, 1))
+    return morton(*_cells(pos, h, grid_min))
 
 
-def layer32(tile_download, boundary, view, particle_radius=PARTICLE_RADIUS, rect=None):
+def layer32(tile_download, boundary, view, particle_radius=PARTICLE_RADIUS, rect=None, h=SMOOTHING_LENGTH, grid_min=GRID_MIN):
     """One tile's layer.  tile_download: dict(pos, vel, ids) of the tile's LOCAL arrays in local order (bit 31 of an id = owned; the
     ghosts are dropped here).  boundary: the boundary particles the tile holds.  rect = (x0, x1, y0, y1), the tile's cells: only the
-    boundary particles whose cell lies in it are drawn (None: all of `boundary`).  Returns dict(key uint32 [H, W], owner uint32 [H, W],
+    boundary particles whose cell lies in it are drawn (None: all of `boundary`).  particle_radius, h, grid_min: the parameter block's
+    (defaults: default_params()).  Returns dict(key uint32 [H, W], owner uint32 [H, W],
     rgba uint8 [H, W, 4])."""
     ids = np.asarray(tile_download["ids"], np.uint32)
     own = (ids & OWNED) != 0
@@ -47,7 +53,7 @@ def layer32(tile_download, boundary, view, particle_radius=PARTICLE_RADIUS, rect
     ids = ids[own] & ~OWNED
     bnd = np.asarray(boundary, F).reshape(-1, 2)
     if rect is not None and len(bnd):
-        bnd = bnd[in_rect(cell_coord(bnd, 0), cell_coord(bnd, 1), rect)]
+        bnd = bnd[in_rect(*_cells(bnd, h, grid_min), rect)]
     r = rr.render32(dict(pos=pos, vel=vel, boundary=bnd), view, particle_radius)
     idx = r["owner"]
     fluid = idx < BOUNDARY
@@ -55,7 +61,7 @@ def layer32(tile_download, boundary, view, particle_radius=PARTICLE_RADIUS, rect
     key = np.zeros(idx.shape, np.uint32)
     if fluid.any():
         owner[fluid] = ids[idx[fluid]]
-        key[fluid] = cell_keys(pos)[idx[fluid]]
+        key[fluid] = cell_keys(pos, h, grid_min)[idx[fluid]]
     return dict(key=key, owner=owner, rgba=r["rgba"])
 
 
@@ -75,7 +81,7 @@ def merge(layers):
     return acc
 
 
-def split(state, rects):
+def split(state, rects, h=SMOOTHING_LENGTH, grid_min=GRID_MIN):
     """A single context's state (pos, vel, boundary in device order, ids optional) cut into the tiles of `rects` (cell rectangles
     (x0, x1, y0, y1) that partition the domain): per tile the download a tile context would give — its owned particles in their
     relative order, ids with bit 31 — and the boundary particles of its cells."""
@@ -83,7 +89,7 @@ def split(state, rects):
     vel = np.asarray(state["vel"], F).reshape(-1, 2)
     ids = np.asarray(state["ids"], np.uint32) if "ids" in state else np.arange(len(pos), dtype=np.uint32)
     bnd = np.asarray(state["boundary"], F).reshape(-1, 2)
-    cx, cy, bx, by = cell_coord(pos, 0), cell_coord(pos, 1), cell_coord(bnd, 0), cell_coord(bnd, 1)
+    (cx, cy), (bx, by) = _cells(pos, h, grid_min), _cells(bnd, h, grid_min)
     out = []
     for r in rects:
         m = in_rect(cx, cy, r)

@@ -16,8 +16,11 @@ def _p(a):
 
 
 class OracleTileBackend:
-    def __init__(self):
-        self.o = Oracle()
+    def __init__(self, oracle=None, h=0.02, grid_min=(-100.0, -100.0)):
+        """oracle, h, grid_min: an Oracle made with other constants than the reference app's, and the smoothing length and grid
+        origin it was made with (the cell coordinates of the halo rules)."""
+        self.o = Oracle() if oracle is None else oracle
+        self.cell_h, self.cell_grid_min = h, grid_min
         self.L = self.o.L
 
     def make_buffers(self, cap, count):
@@ -45,7 +48,7 @@ class OracleTileBackend:
             self.o.stiffness() if n else np.zeros(0, np.float32))
 
     def _cells(self, pos):
-        return cell_coord(pos, 0), cell_coord(pos, 1)
+        return cell_coord(pos, 0, self.cell_grid_min[0], h=self.cell_h), cell_coord(pos, 1, self.cell_grid_min[1], h=self.cell_h)
 
     def upload(self, pos, vel, ids):
         n = len(pos)

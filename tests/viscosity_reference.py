@@ -37,10 +37,10 @@ def rs_powi(a, b):
 
 
 class Constants:
-    """The kernel constants the reference derives from the smoothing length (sphx_default_params of the reference app)."""
+    """The kernel constants the reference derives from the smoothing length (params: a parameter block; default: the reference app's)."""
 
-    def __init__(self):
-        p = y.default_params()
+    def __init__(self, params=None):
+        p = y.default_params() if params is None else params
         self.h, self.m, self.rho0 = F(p.smoothing_length), F(p.particle_mass), F(p.fluid_density)
         self.g = np.array(p.gravity, F)
         h = self.h
@@ -152,10 +152,14 @@ class ViscousOracleTileBackend(OracleTileBackend):
     """OracleTileBackend with the non-pressure pass and the velocity prediction in numpy: model "xsph" (coef = epsilon) or
     "physical" (coef = fluid_viscosity).  The oracle keeps positions, lists, densities and everything after the prediction."""
 
-    def __init__(self, model, coef):
-        super().__init__()
+    def __init__(self, model, coef, params=None, oracle=None):
+        """params, oracle: a parameter block and an Oracle made with the same constants (default: the reference app's)."""
+        if params is None:
+            super().__init__(oracle)
+        else:
+            super().__init__(oracle, h=params.smoothing_length, grid_min=tuple(params.grid_min))
         assert model in (XSPH, PHYSICAL)
-        self.model, self.coef, self.K = model, F(coef), Constants()
+        self.model, self.coef, self.K = model, F(coef), Constants(params)
 
     def nonpressure(self, dt_prev):
         pos, vel, ids, _, _ = self._state()

@@ -484,6 +484,7 @@ struct sphx_ctx {
     bool need_recover = false;      // a particle outran the directory (DF_STRAY): re-cover the true bounding box before the next build
     uint32_t recover_streak = 0;    // builds that still re-cover predictively after strays were seen
     uint32_t recover_cooldown = 0;  // builds to wait before the next re-cover attempt when the box is too large to cover
+    float wcsph_vmax_prev = 0.0f;   // max |v + a dt| of the latest WCSPH step: how far leap frog 1 of the next one can carry a particle
     std::vector<float> h_boundary;  // host copy of the boundary (caller order): the static directory is built on the host
     // neighbour lists: wave-sliced ELL, fixed stride: entry k of particle i at ((i>>6)*64 + k)*64 + (i&63)
     uint32_t* nb_list = nullptr;

@@ -2118,6 +2118,11 @@ int sphx_wcsph_step_begin(sphx_ctx* c, float dt, float* out_vmax) {
         SPHX_HIP(c, hipMemsetAsync(c->accel + c->wcsph_n, 0, (size_t)(n - c->wcsph_n) * 8, st));
     c->wcsph_n = n;
     launch(c, "wcsph_leapfrog1", 40.0 * n, [&] { hipLaunchKernelGGL(k_wcsph_leapfrog1, g, b, 0, st, c->vel, c->posA, (const float2*)c->accel, n, dt); });
+    // A step whose particles may travel a good part of a 64-cell block (a blow-up: the boundary force of wscsph.rs:109-116 does not
+    // scale with the resolution) covers the leap-frogged positions BEFORE the build instead of finding strays in it: a stray is kept
+    // without neighbours for that build, which is not the reference's arithmetic.  The estimate is the last step's max |v + a dt|
+    // (leap frog 1 adds another half kick: hence the factor 2); a calm run never pays the download.
+    if (2.0f * c->wcsph_vmax_prev * dt * c->K.cell_inv > 16.0f) c->recover_streak = std::max(c->recover_streak, 1u);
     int rc;
     if ((rc = update_neighborhood(c, false, 0.0f, false))) return rc;  // update_neighborhood_datastructure(vec![], vec![]), wscsph.rs:152
     launch_density<1>(c, true, false);                                   // update_densities(Poly6), wscsph.rs:153
@@ -2138,6 +2143,7 @@ int sphx_wcsph_step_begin(sphx_ctx* c, float dt, float* out_vmax) {
     std::memcpy(&vsq, &vbits, 4);
     if (!std::isfinite(vsq)) return c->fail(SPHX_ERR_NONFINITE, "max velocity is not finite (Duration::from_secs_f32 would panic, timemanager.rs:264)");
     c->step_vmax = std::sqrt(vsq);  // wscsph.rs:163
+    c->wcsph_vmax_prev = c->step_vmax;
     *out_vmax = c->step_vmax;
     c->in_step = true;
     c->in_wcsph = true;
