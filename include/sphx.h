@@ -606,8 +606,18 @@ int sphx_debug_takeover_counts(sphx_ctx* ctx, uint64_t out[3]);
  * (never: the launches from before) / 1 (at every context size; default: from 4 M particles, where the flags exist) / force
  * (whatever the hint says). */
 int sphx_debug_rigid_counts(sphx_ctx* ctx, uint64_t out[3]);
+/* Test aid: the rigid form of the first density producer.  A rigid non-pressure pass that finds no mark leaves
+ * the acceleration array unwritten, and the velocity prediction + compute_density_error behind it reads the uniform acceleration from
+ * its arguments; a workgroup none of whose particles has a static neighbour leaves without a list word or a neighbour's record.
+ * out[0] launches queued in that form (host count); with SPHX_ZERO_SKIP_COUNT=1 also out[1] workgroups that took the fluid-only exit,
+ * out[2] workgroups that walked with the uniform acceleration, out[3] launches that found no verdict (the pass had found a mark and
+ * filled the array: today's loads).  Cumulative; waits for the stream.  Switch, read by sphx_create: SPHX_RIGID_PREDICT=0 (the rigid
+ * pass fills the array: the launches from before) / accel (no exit: every workgroup walks) / default: both, wherever the rigid pass
+ * is queued. */
+int sphx_debug_rigid_predict_counts(sphx_ctx* ctx, uint64_t out[4]);
 /* Test aid: the acceleration array as the latest non-pressure pass left it, in sorted order — between two DFSPH steps the pass that
- * ran ahead for the next one.  out_xy holds 2 * N floats.  Waits for the stream. */
+ * ran ahead for the next one (where a rigid pass left the array to its reader, the fill it left out is queued first; the course of
+ * the run does not change).  out_xy holds 2 * N floats.  Waits for the stream. */
 int sphx_debug_download_accel(sphx_ctx* ctx, float* out_xy);
 
 /* ---- Solver trait (solver/mod.rs:12-18) ---------------------------------------------------------------------- */

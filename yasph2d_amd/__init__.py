@@ -751,6 +751,14 @@ class SphxContext:
         self._chk(self.L.sphx_debug_rigid_counts(self.h, out))
         return int(out[0]), int(out[1]), int(out[2])
 
+    def rigid_predict_counts(self):
+        """sphx_debug_rigid_predict_counts -> (first density producers queued in the rigid form, workgroups that took the fluid-only
+        exit, workgroups that walked with the uniform acceleration, launches that found no verdict); the last three are counted with
+        SPHX_ZERO_SKIP_COUNT=1 only.  Cumulative since the context was created."""
+        out = (C.c_uint64 * 4)()
+        self._chk(self.L.sphx_debug_rigid_predict_counts(self.h, out))
+        return int(out[0]), int(out[1]), int(out[2]), int(out[3])
+
     def download_accel(self):
         """sphx_debug_download_accel -> float32 [N, 2]: accel[] as the latest non-pressure pass left it (sorted order)."""
         out = np.zeros((self.n, 2), np.float32)

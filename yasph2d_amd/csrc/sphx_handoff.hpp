@@ -135,4 +135,42 @@ struct VelMarks {
     }
 };
 
+// Rigid motion, the acceleration array: the latest non-pressure launch was the rigid form under the gather's sequence
+// number `tag`.  Its workgroup 0 has stored `tag` in VerdictLine::accel_uniform iff it found no mark — then accel[] was NOT written and
+// stands for K.a, and every fluid velocity carried the bits of vel[0] when the pass ran; with a mark it stored ~tag and filled accel[].
+// Two facts with two lifetimes:
+//   owed     under the verdict accel[] is unwritten.  Ends when somebody writes the array: a non-pressure pass in any other form
+//            (filled), the fill k_accel_materialize(tag) that read() and take() ask for in front of whoever reads the array — or when
+//            the array itself is gone (filled: alloc_particles).
+//   uniform  under the verdict every fluid velocity still equals vel[0]: nothing queued since the pass can have written one.  Ends
+//            with everything that voids VelMarks, with broken() and rigid_forget() (velocities_written), and with the first consumer.
+// made     enqueue_nonpressure's rigid branch
+// read     somebody copies accel[] and leaves the velocities alone (sphx_debug_download_accel, a state blob with the WCSPH section)
+// take     the first consumer of accel[], a velocity prediction.  substitute: it is the rigid form of the density producer, which reads
+//          K.a from its arguments where the device word equals `tag` (Taken::k_a) and writes nothing to accel[] — an array still owed
+//          stays owed to a later reader; any other consumer reads the array, behind the fill if it is owed (Taken::fill).
+struct AccelUniform {
+    bool owed = false, uniform = false;
+    uint32_t tag = 0;
+    struct Taken {
+        bool fill, k_a;
+        uint32_t tag;
+    };
+    void made(uint32_t gather_tag) { *this = AccelUniform{true, true, gather_tag}; }
+    void velocities_written() { uniform = false; }
+    void filled() { *this = AccelUniform{}; }
+    Taken read() {
+        const Taken t{owed, false, tag};
+        owed = false;
+        return t;
+    }
+    Taken take(bool substitute) {
+        const bool k_a = substitute && uniform;
+        const Taken t{owed && !k_a, k_a, tag};
+        if (t.fill) owed = false;
+        uniform = false;
+        return t;
+    }
+};
+
 }  // namespace sphx

@@ -180,7 +180,10 @@ struct alignas(128) Stripe {
     // their walk / that a flag of their window stopped / that a flag behind an out-of-window table line stopped
     unsigned long long zs_skipped, zs_window, zs_remote;
     unsigned long long zs_quiet;    // ... and, of the skipped ones, those that left through the quiet-scene exit (decide-first form)
-    uint32_t pad[12];
+    // rigid form of the density producer (k_compute_error_rigid), the same switch: workgroups that left through the fluid-only exit /
+    // that walked with K.a from the arguments; launches whose workgroup 0 found no verdict (sphx_debug_rigid_predict_counts)
+    uint32_t rp_exit, rp_walk, rp_noverdict;
+    uint32_t pad[9];
 };
 static_assert(sizeof(Stripe) == 128, "one stripe, one cache line");
 // The max-velocity ring lives on cache lines of its own: the first density iteration READS it (velocity prediction folded into
@@ -216,6 +219,14 @@ struct alignas(128) SpecLine {
     unsigned long long moved;
     uint32_t pad[28];
 };
+// The verdict of the latest rigid non-pressure launch (k_nonpressure_rigid's workgroup 0, a plain store): the gather's tag when it found
+// no mark and left accel[] unwritten (it stands for K.a), ~tag when it filled the array.  Never reset: a reader compares with the tag
+// the host handed it (sphx::AccelUniform).  On a line of its own — every workgroup of the density producer's rigid form reads it
+// while finished workgroups of the same launch add their residuals to Stripe (knz_mark's lesson).
+struct alignas(128) VerdictLine {
+    uint32_t accel_uniform;
+    uint32_t pad[31];
+};
 struct DevScalars {
     uint32_t flags;        // DF_*
     uint32_t ticket;       // second-level arrival counter (one arrival per stripe); reset by the last arriver
@@ -230,6 +241,7 @@ struct DevScalars {
     VmaxStripe vstripe[STRIPES];
     MarkStripe mstripe[STRIPES];
     SpecLine spec;
+    VerdictLine verdict;
 };
 
 // Pinned, host-coherent memory the device publishes step scalars into (no D2H copy, no stream sync on the fast path).
@@ -461,10 +473,19 @@ struct sphx_ctx {
     uint32_t rigid_judged = 0;
     void rigid_forget() {
         velmarks.wrote();
+        accel_uniform.velocities_written();
         rigid_hint = false;
         rigid_judged = 0;
     }
     unsigned long long rigid_launches = 0;     // non-pressure passes queued in the rigid form (sphx_debug_rigid_counts)
+    // The rigid pass leaves accel[] unwritten and the density producer behind it reads K.a from its arguments.
+    // SPHX_RIGID_PREDICT=0: the parent's launches (the pass fills accel[], no record); accel = 1: the K.a substitution without the
+    // fluid-only exit (the per-part A/B); 2 (default): both, wherever the rigid pass is queued.
+    int rigid_predict = 2;
+    // What the latest rigid pass owes accel[] (sphx_handoff.hpp).  made: enqueue_nonpressure's rigid branch; filled: any other
+    // non-pressure launch, alloc_particles; velocities_written: whatever voids velmarks; take: the first consumer of accel[].
+    sphx::AccelUniform accel_uniform;
+    unsigned long long rigid_predict_launches = 0;  // density producers queued in the rigid form (sphx_debug_rigid_predict_counts)
     float2* accel = nullptr;                   // [N]
     float *density = nullptr, *alpha = nullptr, *alpha2 = nullptr, *kappa = nullptr, *stiff = nullptr;  // [N]
     float *kappa2 = nullptr, *stiff2 = nullptr;  // gather targets (tile mode only)

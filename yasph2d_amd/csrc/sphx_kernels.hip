@@ -2621,6 +2621,7 @@ struct RigidArgs {
     uint32_t check_knz;
     uint32_t vgrid;      // blocks of the full grid
     Mailbox* mb;         // Mailbox::rigid_tag
+    uint32_t fill;       // != 0: the unmarked path stores accel[i] = K.a (SPHX_RIGID_PREDICT=0); 0: it leaves the array to its consumer
 };
 // Called by a whole wavefront: some stripe carries a mark — or dt is not a step for which f = em W / (rho_j dt) stays finite
 // (rho_j >= rho0: a denormal rho0 dt could make it infinite, and inf * 0 is NaN).  The host tests the same where it knows dt.
@@ -2635,10 +2636,12 @@ __device__ __forceinline__ bool rigid_marked(const DevScalars* __restrict__ scal
     return __any(vm == ra.vmix_tag || (ra.check_knz != 0u && km == ra.knz_tag)) != 0 || !dt_ok;
 }
 // The rigid form of the pass: min(vgrid, 2 048) workgroups stand for the vgrid blocks of the full grid, k_correct_thin's shape.  Each
-// looks at the 64 mark words once.  No mark: accel[i] = K.a for its blocks' particles, and one lane adds |v_ref + K.a dt|^2 — today's
-// operations on v_ref = vel[0], the velocity of every particle — to the max-velocity reduction; no list word, window or density is
-// requested.  A mark: today's body over its blocks, with a barrier between two blocks for the staged records.  Workgroup 0 reports
-// what it saw (Mailbox::rigid_tag: the hint for the next step's launch; DevScalars::rigid_exits / rigid_marked).
+// looks at the 64 mark words once.  No mark: accel[] stands for K.a — left unwritten for the consumer that reads K.a from its arguments
+// (ra.fill == 0; k_compute_error_rigid, or k_accel_materialize in front of any other), or filled here (ra.fill) — and one lane adds
+// |v_ref + K.a dt|^2 — today's operations on v_ref = vel[0], the velocity of every particle — to the max-velocity reduction; no list
+// word, window or density is requested.  A mark: today's body over its blocks, with a barrier between two blocks for the staged
+// records.  Workgroup 0 reports what it saw (Mailbox::rigid_tag: the hint for the next step's launch; DevScalars::rigid_exits /
+// rigid_marked; VerdictLine::accel_uniform: whether accel[] was written).
 template <int VM>
 __global__ NONP_BOUNDS void k_nonpressure_rigid(PVr PV, const float* __restrict__ density, uint32_t n, uint32_t soff, Consts K,
                                                             float dt, NbView nb, float2* __restrict__ accel, DevScalars* __restrict__ scal, uint32_t vslot,
@@ -2654,12 +2657,17 @@ __global__ NONP_BOUNDS void k_nonpressure_rigid(PVr PV, const float* __restrict_
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         __hip_atomic_store(&ra.mb->rigid_tag, marked ? 0u : ra.vmix_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         atomicAdd(marked ? &scal->rigid_marked : &scal->rigid_exits, 1u);
+        // the verdict for accel[]'s consumer (VerdictLine; a plain store, read by the kernels queued behind this one): the tag iff the
+        // array is left unwritten and stands for K.a
+        scal->verdict.accel_uniform = (!marked && ra.fill == 0u) ? ra.vmix_tag : ~ra.vmix_tag;
     }
     if (!marked) {
         const float2 a = make_float2(K.ax, K.ay);
-        for (uint32_t vblk = blockIdx.x; vblk < ra.vgrid; vblk += gridDim.x) {
-            const uint32_t i = xcd_map(vblk, ra.vgrid, K.rev, K.xcd_shift) * 256u + threadIdx.x;
-            if (i < n) accel[i] = a;
+        if (ra.fill != 0u) {
+            for (uint32_t vblk = blockIdx.x; vblk < ra.vgrid; vblk += gridDim.x) {
+                const uint32_t i = xcd_map(vblk, ra.vgrid, K.rev, K.xcd_shift) * 256u + threadIdx.x;
+                if (i < n) accel[i] = a;
+            }
         }
         if (blockIdx.x == 0 && threadIdx.x == 0) {
             const float2 v = PV.vel[0];
@@ -2857,121 +2865,58 @@ __global__ TRAV_BOUNDS void k_compute_error(PVr PV, const float* __restrict__ de
                                                         uint32_t* __restrict__ clear_hist, uint32_t clear_len, PredArgs pa,
                                                         uint32_t* __restrict__ knz, uint32_t knz_tag,
                                                         std::conditional_t<TAKE && !DIVERGENCE, CountArgs, NoTake> ta) {
-    static_assert(!TAKE || KNZ, "the take-over producers are the ones that leave flags");
-    constexpr bool SPEC = TAKE && !DIVERGENCE;  // (the speculative cell count)
-    // device-run loop: an iteration queued behind the one that met the residual test has nothing to do
-    if (la.enabled && la.iter > 1u && scal->loop_done != 0u) return;
-    if (dt_dev) dt = *dt_dev;
-    // Every density correction of a device-run loop also does the re-grid's cell count (it cannot know early and cheaply whether it
-    // is the last one: deriving the verdict in every workgroup cost that kernel 2.5 us).  This iteration exists, so the previous
-    // correction was not the last: its count is wiped here, a slice per workgroup, before this iteration's correction counts again.
-    if (clear_hist) {
-        const uint32_t per = (clear_len + gridDim.x - 1u) / gridDim.x;
-        const uint32_t c0 = blockIdx.x * per, c1 = min(c0 + per, clear_len);
-        for (uint32_t k = c0 + threadIdx.x; k < c1; k += 256u) clear_hist[k] = 0u;
+    constexpr int RIGID = 0;
+#include "sphx_compute_error_body.inc"
+}
+
+// Rigid motion, the density producer: k_compute_error<false, true, true, true> queued behind a rigid non-pressure pass
+// that may have left accel[] unwritten.  VerdictLine::accel_uniform == ta.accel_tag says it did: accel[g] stands for K.a for every
+// g < soff, and every fluid velocity carried the bits of vel[0] when the pass ran — nothing has written one since (sphx::AccelUniform).
+// A decide-first form, like QF: verdict, vel[0], the count word, the wavefront's format word and the own particle's words are
+// requested together with the max-velocity stripes; the timer law runs; then one __syncthreads_or over "this lane has a static
+// neighbour (ct != cd) or its wavefront is wide".
+//   Exit (EXIT; verdict, v* finite, nobody reaches a static record): no list word, table line, window record, vel[i] or accel word is
+//     requested.  Why it is exact.  predicted() gives every fluid record v* = vel[g] + accel[g] dt = vel[0] + K.a dt: the same two
+//     operations on the same bits, for the own particle too.  The walk adds delta = delta + (dvx g.x + dvy g.y) per neighbour with
+//     dv = v* - v* = +0 (v* finite, tested here) and g = grad W finite (K.q_noclamp with current lists: the host queued the pass in
+//     front only then, and a launch that loses either loses the record): (+0) g.x and (+0) g.y are +-0, their sum is +-0, and
+//     +0 + (+-0) = +0 — the sum starts at +0 and stays +0, -0 terms included.  A particle with no neighbour at all has delta = +0
+//     too.  e = fmax(rho0, rho_i + ((+0) m) dt) - rho0 is evaluated here with delta = +0 written in, so rho_i goes through the same
+//     multiplications and the same addition as in the walk, whatever m and dt are.  Boundary records (g >= soff) keep v = 0:
+//     v* - 0 is not +0, which is why a static neighbour anywhere in the workgroup sends it through the walk; a wide wavefront gathers
+//     from global memory and is left to the walk as well.  The stores, the speculative count, the flags and the residual are the
+//     walk's statements on the same values.
+//   Walk with K.a (verdict, but a static neighbour, a wide wavefront or a v* that is not finite; every workgroup of EXIT = false):
+//     today's path one round trip late, predicted() taking K.a from the arguments for every g < soff — no accel word is requested.
+//   Slow path (no verdict: the pass found a mark and filled accel[]): today's path with the accel loads, one round trip late.  Once
+//     per transition — the mark also clears the host's hint, and the next pass is not rigid.
+// ta.count (SPHX_ZERO_SKIP_COUNT=1): Stripe::rp_exit / rp_walk / rp_noverdict.
+struct RigidTake : CountArgs {
+    uint32_t accel_tag;  // the gather's sequence number the pass in front was queued under
+    uint32_t count;
+};
+template <bool EXIT>
+__global__ TRAV_BOUNDS void k_compute_error_rigid(PVr PV, const float* __restrict__ density,
+                                                              const float* __restrict__ alpha, uint32_t n, uint32_t soff, Consts K, float dt,
+                                                              NbView nb, float* __restrict__ kbuf, float* __restrict__ warm_zero,
+                                                              DevScalars* __restrict__ scal, const float* __restrict__ dt_dev, LoopArgs la,
+                                                              uint32_t* __restrict__ clear_hist, uint32_t clear_len, PredArgs pa,
+                                                              uint32_t* __restrict__ knz, uint32_t knz_tag, RigidTake ta) {
+    constexpr bool DIVERGENCE = false, PREDICT = true, KNZ = true, TAKE = true;
+    constexpr int RIGID = EXIT ? 2 : 1;
+#include "sphx_compute_error_body.inc"
+}
+
+// The fill the rigid non-pressure pass left out, in front of a consumer that reads accel[] (k_predict, a download): every workgroup
+// reads the verdict and stores K.a over its blocks iff the pass under `tag` left the array unwritten.  k_nonpressure_rigid's grid.
+__global__ __launch_bounds__(256) void k_accel_materialize(float2* __restrict__ accel, uint32_t n, uint32_t vgrid, float ax, float ay,
+                                                           const DevScalars* __restrict__ scal, uint32_t tag) {
+    if (scal->verdict.accel_uniform != tag) return;
+    const float2 a = make_float2(ax, ay);
+    for (uint32_t vblk = blockIdx.x; vblk < vgrid; vblk += gridDim.x) {
+        const uint32_t i = vblk * 256u + threadIdx.x;
+        if (i < n) accel[i] = a;
     }
-    __shared__ Stage<2, 0> rec;  // position, velocity
-    auto put = [&](uint32_t slot, const float4& r) { rec.put_vec01(slot, r); };
-    auto take = [&](uint32_t o) { return rec.vec01(o); };
-    const uint32_t blk = xcd_bid(K.rev, K.xcd_shift);
-    const uint32_t i = blk * 256 + threadIdx.x;
-    NbHead h = nb_head(nb, blk, i, n);
-    // this particle's scalars are requested together with everything else (one round trip, not two)
-    const float rho_i = (!DIVERGENCE && i < n) ? density[i] : 0.0f;
-    const float alpha_i = i < n ? alpha[i] : 0.0f;
-    struct PredRec {
-        float4 pv;
-        float2 a;
-    };
-    auto load_pred = [&](uint32_t g) { return PredRec{ldpv(PV, g), gat(pa.accel, g < soff ? g : 0u)}; };  // accel[] has no boundary tail
-    auto predicted = [&](const PredRec& r, uint32_t g) {  // dfsph.rs:484-492, the operations of k_predict; boundary records keep v = 0
-        return g < soff ? make_float4(r.pv.x, r.pv.y, r.pv.z + r.a.x * dt, r.pv.w + r.a.y * dt) : r.pv;
-    };
-    if (PREDICT) {
-        // The reduction's stripes are requested FIRST (loads return in order: behind the staging loads the maximum would arrive last),
-        // then all records; the first wavefront applies the timer law while the records are in flight.
-        // (pa.va.enabled == 0 — tile path: dt is the host's, all-reduced over the tiles; no law here)
-        uint32_t vb = 0;
-        if (pa.va.enabled && threadIdx.x < STRIPES) vb = scal->vstripe[threadIdx.x].vmax[pa.va.vslot & 3u];
-        // (a pair that straddles soff: its second record is a boundary particle's, predicted() ignores the acceleration it got)
-        auto load_pred2 = [&](uint32_t g) {
-            const Pair<float4> pv = ldpv2(PV, g);
-            const Pair<float2> a = gat2(pa.accel, g < soff ? g : 0u);
-            return Pair<PredRec>{PredRec{pv.a, a.a}, PredRec{pv.b, a.b}};
-        };
-        const NbStaged<PredRec> st = nb_stage_load(h, nb, blk, i, n, load_pred, load_pred2);
-        __shared__ float dt_s;
-        if (pa.va.enabled && threadIdx.x < 64) {
-            const uint32_t b = wave_max_u32(vb);
-            const unsigned long long ns = timer_law_step_ns(pa.law, sqrtf(__uint_as_float(b)));
-            const float d = duration_as_secs_f32(ns);
-            if (threadIdx.x == 0) dt_s = d;
-            if (blockIdx.x == 0) vmax_publish(scal, pa.va, b, pa.law, ns, d);
-        }
-        if (pa.va.enabled) {
-            __syncthreads();
-            dt = dt_s;
-        }
-        nb_stage_store(h, st, [&](uint32_t slot, const PredRec& r, uint32_t g) { put(slot, predicted(r, g)); });
-    } else {
-        nb_stage(h, nb, blk, i, n, [&](uint32_t g) { return ldpv(PV, g); }, [&](uint32_t g) { return ldpv2(PV, g); }, put);
-    }
-    __syncthreads();
-    float e = 0.0f, e_owned = 0.0f;
-    uint32_t k_bits = 0u;
-    [[maybe_unused]] float2 pnew = make_float2(0.0f, 0.0f);
-    [[maybe_unused]] DirAhead ahead{0xFFFFFFFFu, EMPTY};
-    if (i < n) {
-        const uint32_t ct = h.ct;
-        float4 pvi = h.wide ? ldpv(PV, i) : take((i - h.lw0) * 4u);
-        if (PREDICT && h.wide) pvi = predicted(load_pred(i), i);
-        if constexpr (SPEC) {
-            if (ta.hist) {  // the directory entry of the block the particle is in now, requested in front of the walk (k_correct)
-                uint32_t cx0, cy0;
-                cell_of(K, make_float2(pvi.x, pvi.y), cx0, cy0);
-                ahead = dir_ahead(ta.g, cx0, cy0);
-            }
-        }
-        if (!(DIVERGENCE && ct < 9)) {  // dfsph.rs:261
-            const float2 ri = make_float2(pvi.x, pvi.y);
-            float delta = 0.0f;
-            auto walk = [&](auto fast) {
-                auto consume = [&](const float4& r, uint32_t) {
-                    const float2 g = wendland_grad<decltype(fast)::value>(K, ri, make_float2(r.x, r.y));
-                    // boundary records carry v = 0, so v_i - 0 = v_i is the static form of dfsph.rs:118 / :274
-                    const float dvx = pvi.z - r.z, dvy = pvi.w - r.w;
-                    delta = delta + (dvx * g.x + dvy * g.y);
-                };
-                nb_traverse(h, ct, take, [&](uint32_t g) { return PREDICT ? predicted(load_pred(g), g) : ldpv(PV, g); }, consume);
-            };
-            if (K.q_noclamp)  // (kernel argument: a scalar branch; sqrt_dist)
-                walk(std::true_type{});
-            else
-                walk(std::false_type{});
-            if (DIVERGENCE) {
-                e = fmaxf(delta * K.mass, 0.0f);  // dfsph.rs:277-278
-            } else {
-                e = rho_i + delta * K.mass * dt;  // dfsph.rs:121
-                e = fmaxf(K.rho0, e) - K.rho0;         // dfsph.rs:124
-            }
-        }
-        const float kv = e * alpha_i;
-        kbuf[i] = kv;  // k = err * alpha: all the correction needs of a neighbour besides its position
-        k_bits = __float_as_uint(kv);
-        // the predicted velocity of the own particle (staged with the window).  Stored HERE, behind the walk: a store in front of it
-        // sits in the same counter as the walk's entry loads, and every wait for one of those waited for the store's acknowledge too
-        if (PREDICT) pa.vel_out[i] = make_float2(pvi.z, pvi.w);
-        if constexpr (TAKE)
-            store_cold(&warm_zero[i], 0.0f + kv, K.nt_cold);  // dfsph.rs:296 behind :361-363
-        else if (warm_zero)
-            warm_zero[i] = 0.0f;  // dfsph.rs:206-208 / 361-363 (callers whose first correction does not start from zero itself)
-        e_owned = tile_owns(K, pvi.x, pvi.y) ? e : 0.0f;
-        if constexpr (SPEC) pnew = make_float2(pvi.x + pvi.z * dt, pvi.y + pvi.w * dt);  // dfsph.rs:499-510, as the quiet exit of k_correct
-    }
-    if constexpr (SPEC)
-        if (ta.hist) count_cell(K, ta.g, i < n, i, pnew, ta.hist, ta.cidx, ta.slot, 1u, scal, ahead, &scal->spec.flags);
-    if constexpr (KNZ) knz_store(knz, i, k_bits, scal, knz_tag);  // (the grid is rounded up to whole workgroups, and so is knz[])
-    block_residual_add(e_owned, scal);  // read by the correction queued behind this launch (ResArgs)
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -611,6 +611,7 @@ int build_grid(sphx_ctx* c, Grid& g, const float2* pos, uint32_t n, const Gather
     const bool partial = &g == &c->gdyn && tile_n && advect_dt == 0.0f && !counted && c->pending.is_for_first_of(n);
     const uint32_t first = partial ? c->pending.n() : 0u;
     if (&g == &c->gdyn) c->velmarks.wrote();  // (the gather below moves every velocity: an earlier gather's marks describe the old array)
+    if (&g == &c->gdyn) c->accel_uniform.velocities_written();
     if (counted || partial)
         c->pending.forget();  // consumed: k_scatter counts the histogram back down to zero, as behind any count (the scan leaves it as it is)
     else
@@ -983,6 +984,7 @@ int update_neighborhood(sphx_ctx* c, bool extra_alpha, float advect_dt, bool fus
             launch(c, "neighbor_build+density_alpha+divergence_warmstart", (8.0 + list_bytes(c) + 8.0 + 8.0 + 8.0 + 4.0) * n, [&] { go(k_neighbor_build<3>, dv); });
             c->handoff = BuildHandoff::warm_applied();
             c->velmarks.wrote();  // (the warm start corrects velocities behind the gather)
+            c->accel_uniform.velocities_written();
         } else if (fuse && fuse_div) {
             DivArgs dv{};
             dv.vel = (const float2*)c->vel;
@@ -1029,6 +1031,26 @@ void launch_density(sphx_ctx* c, bool density, bool alpha) {
     launch(c, "compute_alpha_factors", bytes, [&] { go(k_density_alpha<0, false, true>); });
 }
 
+// What every reader of accel[] starts with (sphx::AccelUniform, DESIGN.md §4): a rigid non-pressure pass may have left the array
+// unwritten, and the fill it left out goes in front of the reader (k_accel_materialize decides on the device whether there is
+// anything to fill).  read_accel: a copy that leaves the velocities alone.  take_accel: the first consumer, a velocity prediction —
+// substitute: the density producer's rigid form, which reads K.a from its arguments while nothing has written a velocity since the pass.
+void fill_accel(sphx_ctx* c, const AccelUniform::Taken& t) {
+    const uint32_t n = std::min(c->N, c->capN);
+    if (!t.fill || !n || !c->accel) return;
+    const uint32_t vgrid = nblocks(n);
+    launch(c, "accel_materialize", 8.0 * n, [&] {
+        hipLaunchKernelGGL(k_accel_materialize, dim3(std::min(vgrid, 2048u)), dim3(256), 0, c->stream, c->accel, n, vgrid, c->K.ax, c->K.ay,
+                           (const DevScalars*)c->d_scal, t.tag);
+    }, false);
+}
+void read_accel(sphx_ctx* c) { fill_accel(c, c->accel_uniform.read()); }
+AccelUniform::Taken take_accel(sphx_ctx* c, bool substitute) {
+    const AccelUniform::Taken t = c->accel_uniform.take(substitute);
+    fill_accel(c, t);
+    return t;
+}
+
 // cap: the capacity to allocate when n does not fit (0: exactly n).  keep_set (sphx_append): positions, velocities and ids of [0, N)
 // survive the reallocation too.
 int alloc_particles(sphx_ctx* c, uint32_t n, uint32_t cap = 0, bool keep_set = false) {
@@ -1043,6 +1065,8 @@ int alloc_particles(sphx_ctx* c, uint32_t n, uint32_t cap = 0, bool keep_set = f
     if (keep_set) c->pid = nullptr;
     const uint32_t keep = std::min(c->cached_n, c->capN);
     const uint32_t keep_accel = std::min(c->wcsph_n, c->capN);
+    // (a rigid pass may owe the old array its fill: paid where the array is copied, forgotten with the array otherwise)
+    keep_accel ? read_accel(c) : c->accel_uniform.filled();
     c->kappa = c->stiff = c->alpha = nullptr;
     c->accel = nullptr;
     auto give_up = [&](int code) {  // an allocation failed: the old slot-bound arrays are of no use without their siblings
@@ -1096,6 +1120,7 @@ inline bool device_loop(const sphx_ctx* c) { return !c->tile_mode && !c->host_lo
 void launch_predict(sphx_ctx* c, const char* label, float dt, const VmaxArgs& va = VmaxArgs{}, const TimerLaw& tl = TimerLaw{}) {
     const uint32_t n = c->N;
     c->velmarks.wrote();
+    take_accel(c, false);  // (k_predict reads accel[]: a fill the rigid pass left out comes first)
     launch(c, label, 24.0 * n, [&] { hipLaunchKernelGGL(k_predict, dim3(nblocks(n)), dim3(256), 0, c->stream, c->vel, (const float2*)c->accel, n, dt, c->d_scal, va, tl); });
 }
 
@@ -1123,6 +1148,22 @@ void launch_compute_error(sphx_ctx* c, bool divergence, float dt, const float* d
         PredArgs pa = *pred;
         pa.accel = c->accel;
         pa.vel_out = c->vel2;
+        // Rigid motion: the first consumer of accel[] behind a rigid non-pressure pass.  As the take-over producer, with every grad W
+        // finite, it takes the record for itself and reads K.a from its arguments (k_compute_error_rigid); any other form reads the
+        // array, behind the fill the pass left out.
+        const AccelUniform::Taken au = take_accel(c, c->rigid_predict != 0 && knz && take_warm && c->K.q_noclamp && !c->tile_mode);
+        if (au.k_a) {
+            c->rigid_predict_launches += 1;
+            const RigidTake rt{take_count, au.tag, c->zero_skip_count ? 1u : 0u};
+            auto go_rigid = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, dim3(nblocks(n)), dim3(256), 0, c->stream, c->pv(), (const float*)c->density, (const float*)c->alpha, n, c->soff(), c->K, dt,
+                                   c->nbv(), c->kbuf, c->kappa, c->d_scal, dt_dev, la, clear_hist, clear_len, pa, knz, knz_tag, rt);
+            };
+            // (the exit's stream: own position, density, alpha, count word; k, v*, kappa, the cell word and its count)
+            const double bytes = c->rigid_predict == 2 ? (8 + 4 + 4 + 2 + 4 + 8 + 4 + 4 + 8) * (double)n : (16 + 8 + 4 + 4 + 4 + lb) * n;
+            return launch(c, "velocity_prediction+compute_density_error", bytes,
+                          [&] { c->rigid_predict == 2 ? go_rigid(k_compute_error_rigid<true>) : go_rigid(k_compute_error_rigid<false>); });
+        }
         launch(c, "velocity_prediction+compute_density_error", (16 + 8 + 8 + 4 + 4 + 4 + lb) * n, [&] {
             if (knz && take_warm) return go(k_compute_error<false, true, true, true>, c->kappa, pa, take_count);  // (take-over: kappa = 0 + k and the count go out too)
             if (knz) return go(k_compute_error<false, true, true>, nullptr, pa, NoTake{});
@@ -1165,6 +1206,7 @@ void launch_correct(sphx_ctx* c, bool divergence, float dt, const float* dt_dev,
     if ((quiet_first || thin) && c->zero_skip_count) c->qf_launches += 1;
     // (rigid motion: a thin correction writes velocities only with its iteration's mark set, which the consumer reads; any other form voids)
     thin ? c->velmarks.thin(ra.rseq) : c->velmarks.wrote();
+    c->accel_uniform.velocities_written();
     if (thin) {
         c->thin_launches += 1;
         const uint32_t vblocks = nblocks(n);
@@ -1196,6 +1238,7 @@ void launch_correct(sphx_ctx* c, bool divergence, float dt, const float* dt_dev,
 void launch_warmstart(sphx_ctx* c, bool divergence, float dt, const float* dt_dev, bool labelled) {
     const uint32_t n = c->N;
     c->velmarks.wrote();
+    c->accel_uniform.velocities_written();
     const float inv_dt = 1.0f / dt, lim = -0.5f * c->K.rho0 * c->K.rho0;
     auto one = [&](auto kernel, float* warm) {
         hipLaunchKernelGGL(kernel, dim3(nblocks(n)), dim3(256), 0, c->stream, c->vel, (const float2*)c->posA, (const float*)c->kbuf, warm, n, c->soff(), c->K, inv_dt,
@@ -1378,11 +1421,13 @@ inline bool rigid_conditions(const sphx_ctx* c, float dt) {
 void enqueue_nonpressure(sphx_ctx* c, float dt_prev, uint32_t vslot, const VelMarks::Taken& marks = VelMarks::Taken{}) {
     const uint32_t n = c->N;
     const bool judged = marks.usable && rigid_conditions(c, dt_prev);
-    const RigidArgs ra{marks.tag, marks.knz_tag, marks.check_knz ? 1u : 0u, nblocks(n), c->mbox_dev};
+    // (fill: SPHX_RIGID_PREDICT=0 — the rigid form stores K.a itself, as it did before its consumer could read K.a from its arguments)
+    const RigidArgs ra{marks.tag, marks.knz_tag, marks.check_knz ? 1u : 0u, nblocks(n), c->mbox_dev, c->rigid_predict == 0 ? 1u : 0u};
     c->rigid_judged = judged ? marks.tag : 0u;
     if (!judged) c->rigid_hint = false;
     if (judged && (c->rigid_skip == 2 || c->rigid_hint)) {
         c->rigid_launches += 1;
+        ra.fill ? c->accel_uniform.filled() : c->accel_uniform.made(marks.tag);  // (what the pass owes accel[]: taken by its first reader)
         auto go_rigid = [&](auto kernel, auto visc) {
             hipLaunchKernelGGL(kernel, dim3(std::min(ra.vgrid, c->thin_grid ? c->thin_grid : 2048u)), dim3(256), 0, c->stream, c->pv(), (const float*)c->density, n,
                                c->soff(), c->K, dt_prev, c->nbv(), c->accel, c->d_scal, vslot, visc, ra);
@@ -1393,6 +1438,7 @@ void enqueue_nonpressure(sphx_ctx* c, float dt_prev, uint32_t vslot, const VelMa
             go_rigid(k_nonpressure_rigid<SPHX_VISCOSITY_XSPH>, ViscArg<SPHX_VISCOSITY_XSPH>{});
         }, false);
     }
+    c->accel_uniform.filled();  // (the full pass writes every acceleration)
     auto go = [&](auto kernel, auto visc) {
         hipLaunchKernelGGL(kernel, dim3(nblocks(n)), dim3(256), 0, c->stream, c->pv(), (const float*)c->density, n, c->soff(), c->K, dt_prev, c->nbv(), c->accel,
                            c->d_scal, vslot, visc);
@@ -1569,9 +1615,26 @@ int sphx_debug_rigid_counts(sphx_ctx* c, uint64_t out[3]) {
     return SPHX_OK;
 }
 
+int sphx_debug_rigid_predict_counts(sphx_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return SPHX_ERR_INVALID_ARGUMENT;
+    SPHX_HIP(c, hipSetDevice(c->device));
+    SPHX_HIP(c, hipStreamSynchronize(c->stream));
+    std::vector<Stripe> st(STRIPES);
+    SPHX_HIP(c, hipMemcpy(st.data(), c->d_scal->stripe, sizeof(Stripe) * STRIPES, hipMemcpyDeviceToHost));
+    out[0] = c->rigid_predict_launches;
+    out[1] = out[2] = out[3] = 0;
+    for (const Stripe& s : st) {
+        out[1] += s.rp_exit;
+        out[2] += s.rp_walk;
+        out[3] += s.rp_noverdict;
+    }
+    return SPHX_OK;
+}
+
 int sphx_debug_download_accel(sphx_ctx* c, float* out_xy) {
     if (!c || (c->N && !out_xy)) return SPHX_ERR_INVALID_ARGUMENT;
     SPHX_HIP(c, hipSetDevice(c->device));
+    read_accel(c);  // (a rigid pass leaves the array to its reader: the fill comes first; the course of the run does not change)
     SPHX_HIP(c, hipStreamSynchronize(c->stream));
     if (c->N) SPHX_HIP(c, hipMemcpy(out_xy, c->accel, (size_t)c->N * 8, hipMemcpyDeviceToHost));
     return SPHX_OK;
@@ -1628,6 +1691,7 @@ int sphx_create(const sphx_params* params, sphx_ctx** out) {
     if (const char* e = std::getenv("SPHX_QUIET_TAKEOVER")) c->quiet_takeover = std::strcmp(e, "force") == 0 ? 2 : (e[0] != '0' ? 1 : 0);  // (0: the A/B switch)
     if (const char* e = std::getenv("SPHX_QUIET_TAKEOVER_DENSITY")) c->quiet_takeover_density = e[0] != '0';  // (0: divergence loop only — the per-part A/B)
     if (const char* e = std::getenv("SPHX_RIGID_SKIP")) c->rigid_skip = std::strcmp(e, "force") == 0 ? 2 : (e[0] != '0' ? 1 : 0);  // (0: the A/B switch; unset: from 4 M particles)
+    if (const char* e = std::getenv("SPHX_RIGID_PREDICT")) c->rigid_predict = std::strcmp(e, "accel") == 0 ? 1 : (e[0] != '0' ? 2 : 0);  // (0: the A/B switch; accel: the per-part A/B)
     if (const char* e = std::getenv("SPHX_THIN_GRID")) c->thin_grid = (uint32_t)std::max(0, std::atoi(e));  // (test aid: small scenes run the block loop)
     if (const char* e = std::getenv("SPHX_FUSE_WARM")) c->fuse_warm = e[0] != '0';  // (A/B: the divergence warm start as a walk of its own behind k_neighbor_build<1>)
     c->P = *params;
@@ -2114,6 +2178,7 @@ int sphx_wcsph_step_begin(sphx_ctx* c, float dt, float* out_vmax) {
     }
     hipStream_t st = c->stream;
     const dim3 g(nblocks(n)), b(256);
+    read_accel(c);  // (leap frog 1 reads accel[]: a DFSPH pass in the rigid form may have left it unwritten)
     if (c->wcsph_n < n)  // accellerations.resize(n, zero), wscsph.rs:129
         SPHX_HIP(c, hipMemsetAsync(c->accel + c->wcsph_n, 0, (size_t)(n - c->wcsph_n) * 8, st));
     c->wcsph_n = n;

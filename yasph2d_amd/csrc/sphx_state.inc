@@ -96,6 +96,8 @@ const void* state_section_ptr(const sphx_ctx* c, uint32_t k) {
 // Digests of the device sections, by the layout of h, into dig[] (dig[boundary] from the host copy).  Synchronises the stream.
 int state_digests(sphx_ctx* c, const Header& h, uint64_t* dig) {
     if (!c->state_dig) SPHX_HIP(c, hipMalloc((void**)&c->state_dig, STATE_NSEC * sizeof(unsigned long long)));
+    // (the blob holds accel[] only for WCSPH: then a fill that a rigid non-pressure pass left out comes first, sphx::AccelUniform)
+    if (h.sec[SPHX_STATE_SEC_ACCEL].bytes) read_accel(c);
     hipStream_t st = c->stream;
     SPHX_HIP(c, hipMemsetAsync(c->state_dig, 0, STATE_NSEC * sizeof(unsigned long long), st));
     for (uint32_t k = 0; k < STATE_NSEC; ++k) {
@@ -242,6 +244,8 @@ int sphx_state_load(sphx_ctx* c, const void* buf, uint64_t bytes, uint32_t flags
     if ((rc = alloc_particles(c, std::max(n, h.s.wcsph_n)))) return broken(rc);
     c->N = n;
     lists_went_stale(c);
+    // (accelerations about to arrive replace what a rigid non-pressure pass owes the array: paid now, not over them by the digest below)
+    if (h.sec[SPHX_STATE_SEC_ACCEL].bytes) read_accel(c);
     if (c->capN) {  // the slot-bound slots the blob does not hold read zero
         SPHX_HIP(c, hipMemsetAsync(c->alpha, 0, (size_t)c->capN * 4, st));
         SPHX_HIP(c, hipMemsetAsync(c->kappa, 0, (size_t)c->capN * 4, st));
