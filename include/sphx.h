@@ -75,7 +75,8 @@ extern "C" {
                             *    sphx_multi_tile_rects, sphx_multi_ghost_rings, sphx_tile_sample_points / _points_fetch / _window /
                             *    _window_fetch, SPHX_SAMPLE_FIELD_*
                             * 5 (additive): sphx_multi_particle_fields, sphx_multi_fields_out, sphx_tile_owned_count,
-                            *    sphx_tile_particle_fields_enqueue / _fetch, SPHX_FIELD_* */
+                            *    sphx_tile_particle_fields_enqueue / _fetch, SPHX_FIELD_*
+                            * 5 (additive): sphx_surface_contour, sphx_contour_chain, sphx_contour_out, SPHX_CONTOUR_* */
 
 /* ---- status codes ---- */
 enum {
@@ -244,6 +245,57 @@ int sphx_sample_points(sphx_ctx* ctx, const float* xy, uint32_t m, int kernel_ki
  * through sphx_sample_points give bit-identical outputs. */
 int sphx_sample_grid(sphx_ctx* ctx, float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, int kernel_kind,
                      uint32_t flags, const sphx_sample_out* out);
+
+/* ---- free-surface extraction: the iso-contour of a sampled field, as directed segments (marching squares on the device) -------------
+ * The dam-break papers plot the free-surface profile; a viewer draws a water line.  sphx_surface_contour samples a lattice, cuts the
+ * contour `field == iso` out of it and returns the segments in a defined order, without the lattice crossing to the host;
+ * sphx_contour_chain (host code) stitches segments into polylines.  The contract (every fp32 operation is rounded once, unfused):
+ *   Lattice values: f[iy*nx+ix] is exactly what sphx_sample_grid returns for the chosen field (SPHX_CONTOUR_FIELD_FRACTION: fraction,
+ *     SPHX_CONTOUR_FIELD_DENSITY: density) at that lattice, kernel_kind and state — the same device function, the same bits.
+ *     out->values, when given, receives those bits.
+ *   Inside test: b = (f >= iso) in fp32; a NaN value is outside.
+ *   Cells: cell (ix, iy), 0 <= ix < nx-1, 0 <= iy < ny-1, has the nodes 0 = (ix, iy), 1 = (ix+1, iy), 2 = (ix+1, iy+1), 3 = (ix, iy+1)
+ *     and the edges B (0-1), R (1-2), T (3-2), L (0-3).  Each edge is written a-b: a is the node with the lower lattice index
+ *     iy*nx+ix, b the one with the higher, so the two cells that share an edge name it alike.
+ *   Crossing point: an edge whose nodes differ in b has t = (iso - f_a) / (f_b - f_a) and the point
+ *     p = (x_a + t*(x_b - x_a), y_a + t*(y_b - y_a)), with x_a, y_a the lattice coordinates of sphx_sample_grid
+ *     (x0 + (float)ix*dx, y0 + (float)iy*dy).  Both cells that share an edge compute the same bits: the contour is watertight by bit
+ *     equality.
+ *   Segments: case c = b0 | b1<<1 | b2<<2 | b3<<3; cases 0 and 15 emit nothing.  A segment is directed with the inside on its left:
+ *       1: B->L    2: R->B    4: T->R    8: L->T    3: R->L    6: T->B    12: L->R    9: B->T
+ *      14: L->B   13: B->R   11: R->T    7: T->L
+ *     Saddle cells (5 and 10): the centre ((f0+f1)+(f2+f3))*0.25f is inside iff it is >= iso.
+ *       5, centre inside: B->R and T->L; outside: B->L and T->R.      10, centre inside: R->T and L->B; outside: R->B and L->T.
+ *     Of the two segments of a cell the one that starts on the earlier edge in the order B, R, T, L comes first.
+ *   Output order: cells in ascending iy*(nx-1)+ix, within a cell as above.  *count is the total number of segments.  A segment whose
+ *     index is >= cap_segments is not written and memory behind the capacity is never touched; the call returns SPHX_OK either way (the
+ *     caller compares count with its capacity).  segments NULL: the count alone.  Two calls on one state return the same bytes: no atomic
+ *     decides an order.
+ *   When allowed, refusals, side effects: as sphx_sample_grid (the same SPHX_ERR_NOT_READY rules and lattice errors, a tile context is
+ *     refused, the call only reads).  Further argument errors: iso not finite, unknown field, unknown flag bit, out or out->count NULL.
+ *     nx < 2, ny < 2 or nx*ny == 0 is a successful call with count = 0; values is still filled when nx*ny > 0.
+ * SPHX_CONTOUR_DEVICE_POINTERS: every pointer of out is a device pointer; the call is enqueued on the context's stream and returns
+ * without waiting, and nothing crosses to the host between the sampling and the segments.  Without it: host pointers, the call returns
+ * when they are written (through a device scratch grown on demand and freed in sphx_destroy).
+ * sphx_contour_chain (pure host code, no context): segment u follows s when start(u) == end(s) — fp32 == on both coordinates, so NaN
+ *   equals nothing and -0 equals +0.  successor(s) is the lowest-index unused such u.  Pass 1: in ascending index, every unused segment
+ *   whose start equals no segment's end opens a line, which follows successors until there is none (an open line).  Pass 2: in ascending
+ *   index, every segment still unused opens a line that follows successors; it is closed iff the end of its last segment equals the
+ *   start of its first.  order[n] lists the segment indices line after line, line_first[k] is the first position of line k in order and
+ *   line_first[lines] = n, closed[k] is 0 or 1, *out_lines the number of lines.  O(n log n).  n == 0 succeeds with *out_lines = 0 (the
+ *   pointers but out_lines may be NULL); a NULL pointer with n > 0 (or out_lines NULL) returns SPHX_ERR_INVALID_ARGUMENT. */
+enum { SPHX_CONTOUR_FIELD_FRACTION = 0, SPHX_CONTOUR_FIELD_DENSITY = 1 };
+enum { SPHX_CONTOUR_DEVICE_POINTERS = 1u };   /* as SPHX_SAMPLE_DEVICE_POINTERS: enqueued on the context's stream, no wait */
+typedef struct sphx_contour_out {
+    float*    segments;  /* [cap_segments][4] = x0, y0, x1, y1, or NULL (count only) */
+    uint32_t* cell;      /* [cap_segments] cell index iy*(nx-1)+ix of each segment, or NULL */
+    float*    values;    /* [nx*ny] the lattice values the contour was cut from, or NULL */
+    uint32_t* count;     /* [1] total number of segments; required */
+} sphx_contour_out;
+int sphx_surface_contour(sphx_ctx* ctx, float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, int kernel_kind,
+                         int field, float iso, uint32_t cap_segments, uint32_t flags, const sphx_contour_out* out);
+int sphx_contour_chain(const float* segments, uint32_t n, uint32_t* order /* [n] */, uint32_t* line_first /* [n+1] */,
+                       uint8_t* closed /* [n] */, uint32_t* out_lines);
 
 /* ---- rendering: the reference app's picture of the particles (main.rs:239-275 draw_fluid, recording mode :310-331, :380-397) ---------
  * Every fluid particle a disc coloured heatmap_color(|v| * speed_scale), drawn in array order over the grey boundary particles over the

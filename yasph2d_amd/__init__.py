@@ -15,7 +15,7 @@ from ._lib import (FLAG_DENSITY_ITER_CAP, FLAG_DIVERGENCE_ITER_CAP, FLAG_DENSE_C
                    KERNEL_SPIKY, KERNEL_WENDLAND_C2, VISCOSITY_PHYSICAL, VISCOSITY_XSPH, SphxError, SphxKernelTime, SphxParams, SphxStepStats)
 
 __all__ = ["SphxContext", "FluidParticleWorld", "TimeManager", "DFSPHSolver", "DFSPHMultiSolver", "default_params", "duration_from_secs_f32",
-           "duration_as_secs_f32", "SphxError", "WCSPHSolver", "VISCOSITY_XSPH", "VISCOSITY_PHYSICAL", "SAMPLE_FIELDS", "gauge_elevation",
+           "duration_as_secs_f32", "SphxError", "WCSPHSolver", "VISCOSITY_XSPH", "VISCOSITY_PHYSICAL", "SAMPLE_FIELDS", "gauge_elevation", "contour_chain", "contour_lines",
            "sample_merge", "render_fit", "render_merge", "track_merge", "track_merge_frames", "write_png", "SCENE_RECT", "TRACK_FIELDS", "MULTI_TRACK_FIELDS", "FIELD_NAMES", "STATS_DTYPE", "STATS_FRAME_DTYPE"]
 
 
@@ -331,6 +331,31 @@ def gauge_elevation(ctx, xs, y_lo, y_hi, dy, kernel=KERNEL_WENDLAND_C2):
                             fields=("fraction",))["fraction"][:, 0]
         out.append(_elevation(y, f))
     return np.array(out, np.float64)
+
+
+def contour_chain(segments):
+    """sphx_contour_chain: (order [n], line_first [lines + 1], closed [lines]) of segments [n, 2, 2] (or [n, 4]): the segment indices
+    line after line, where each line starts in `order`, and which lines are closed.  The rule is in include/sphx.h.  Host code; no GPU."""
+    seg = np.ascontiguousarray(segments, np.float32).reshape(-1, 4)
+    n = len(seg)
+    order, first, closed, lines = np.zeros(n, np.uint32), np.zeros(n + 1, np.uint32), np.zeros(n, np.uint8), C.c_uint32()
+    rc = _lib.lib().sphx_contour_chain(_p(seg), n, _p(order), _p(first), _p(closed), C.byref(lines))
+    if rc:
+        raise SphxError(rc, "sphx_contour_chain")
+    return order, first[:lines.value + 1], closed[:lines.value].astype(bool)
+
+
+def contour_lines(segments):
+    """The polylines of a contour (SphxContext.contour()["segments"]): -> (list of float32 [k, 2] point arrays, list of closed flags).
+    A line of s segments has k = s + 1 points: the start of its first segment and every segment's end (a closed line repeats its first
+    point as its last).  Stitched by sphx_contour_chain; host code, no GPU."""
+    seg = np.ascontiguousarray(segments, np.float32).reshape(-1, 2, 2)
+    order, first, closed = contour_chain(seg)
+    lines = []
+    for k in range(len(closed)):
+        idx = order[first[k]:first[k + 1]]
+        lines.append(np.concatenate([seg[idx[:1], 0], seg[idx, 1]]))
+    return lines, [bool(c) for c in closed]
 
 
 def _elevation(y, f):
@@ -829,6 +854,85 @@ class SphxContext:
         self._chk(self.L.sphx_sample_grid(self.h, origin[0], origin[1], dx, dy, nx, ny, kernel, 0,
                                           C.byref(_out_struct(outs, lambda a: a.ctypes.data))))
         return outs
+
+    def contour(self, origin, spacing, shape, iso=0.5, field="fraction", kind=KERNEL_WENDLAND_C2, cap=None, values=False, out=None):
+        """sphx_surface_contour: the contour `field == iso` of the lattice sample_grid(origin, spacing, shape) would return, as directed
+        segments with the inside (field >= iso) on their left, in the order of include/sphx.h (cell after cell).
+
+        field: "fraction" or "density"; shape = (ny, nx).  Returns dict(segments [n, 2, 2] = (start, end) x (x, y), cell [n] = the cell
+        iy * (nx - 1) + ix of each segment, count = the contour's total number of segments, and values [ny, nx] with values=True).
+        cap: the most segments to return (n = min(count, cap)); None calls once with a guessed capacity and once more with the exact
+        count if that was too small, so n = count.  cap = 0 returns the count alone.
+        Device path: out = dict of torch tensors on the context's device — "segments" float32 [cap, 2, 2] (or [cap, 4]) and / or "cell"
+        int32 [cap], optionally "values" float32 [ny, nx]; "count" int32 [1] is allocated when missing.  The tensors are written in
+        place (nothing behind min(count, cap) is touched) and the dict returned holds views of their first n entries and count as an
+        int.  Like sample(), this path synchronises torch's current stream before the call and the context's stream after it."""
+        if field not in _lib.CONTOUR_FIELDS:
+            raise ValueError("field must be one of %s, not %r" % (sorted(_lib.CONTOUR_FIELDS), field))
+        dx, dy = (spacing, spacing) if np.ndim(spacing) == 0 else spacing
+        ny, nx = (int(v) for v in shape)
+        if nx < 0 or ny < 0:
+            raise ValueError("shape must be (ny, nx) with non-negative sizes")
+        o = _lib.SphxContourOut()
+
+        def call(cap_, flags):
+            self._chk(self.L.sphx_surface_contour(self.h, origin[0], origin[1], dx, dy, nx, ny, kind, _lib.CONTOUR_FIELDS[field], iso, cap_, flags, C.byref(o)))
+
+        if out is not None:
+            import torch
+
+            seg, cel, val = out.get("segments"), out.get("cell"), out.get("values")
+            some = next((t for t in (seg, cel, val, out.get("count")) if t is not None), None)
+            if some is None or any(t is not None and (not _is_torch(t) or t.device.type != "cuda" or not t.is_contiguous()) for t in (seg, cel, val, out.get("count"))):
+                raise ValueError("out must hold contiguous torch tensors on the context's device")
+            if seg is not None and (seg.dtype != torch.float32 or seg.dim() < 2 or seg.numel() != 4 * seg.shape[0]):
+                raise ValueError("out[\"segments\"] must be a float32 [cap, 2, 2] or [cap, 4] tensor")
+            if cel is not None and (cel.dtype != torch.int32 or cel.dim() != 1 or (seg is not None and cel.shape[0] != seg.shape[0])):
+                raise ValueError("out[\"cell\"] must be an int32 [cap] tensor, as long as out[\"segments\"]")
+            if val is not None and (val.dtype != torch.float32 or val.numel() != nx * ny):
+                raise ValueError("out[\"values\"] must be a float32 tensor of ny * nx values")
+            cnt = out.get("count")
+            if cnt is None:
+                cnt = torch.zeros(1, dtype=torch.int32, device=some.device)
+            elif cnt.dtype != torch.int32 or cnt.numel() != 1:
+                raise ValueError("out[\"count\"] must be an int32 [1] tensor")
+            have = seg.shape[0] if seg is not None else (cel.shape[0] if cel is not None else 0)
+            cap_ = have if cap is None else min(int(cap), have)
+            o.segments = (seg.data_ptr() or 1) if seg is not None and cap_ else None
+            o.cell = (cel.data_ptr() or 1) if cel is not None and cap_ else None
+            o.values = (val.data_ptr() or 1) if val is not None else None
+            o.count = cnt.data_ptr()
+            torch.cuda.current_stream(some.device).synchronize()
+            call(cap_, _lib.CONTOUR_DEVICE_POINTERS)
+            self.synchronize()
+            count = int(cnt.item())
+            n = min(count, cap_)
+            res = dict(count=count)
+            if seg is not None:
+                res["segments"] = seg.view(-1, 2, 2)[:n]
+            if cel is not None:
+                res["cell"] = cel[:n]
+            if val is not None:
+                res["values"] = val.view(ny, nx)
+            return res
+        cnt = np.zeros(1, np.uint32)
+        o.count = cnt.ctypes.data
+        val = np.zeros((ny, nx), np.float32) if values else None
+        cap_ = max(1024, 8 * (nx + ny)) if cap is None else int(cap)
+        while True:
+            seg, cel = np.zeros((cap_, 2, 2), np.float32), np.zeros(cap_, np.uint32)
+            o.segments, o.cell = (seg.ctypes.data, cel.ctypes.data) if cap_ else (None, None)
+            o.values = (val.ctypes.data or 1) if values else None
+            call(cap_, 0)
+            count = int(cnt[0])
+            if cap is not None or count <= cap_:
+                break
+            cap_ = count
+        n = min(count, cap_)
+        res = dict(segments=seg[:n], cell=cel[:n], count=count)
+        if values:
+            res["values"] = val
+        return res
 
     def render(self, view=None, *, out=None, owner=False, rgba=True, **view_fields):
         """sphx_render: the particles drawn as discs (the contract is in include/sphx.h).

@@ -89,6 +89,14 @@ class SphxSampleOut(C.Structure):
     _fields_ = [("density", C.c_void_p), ("fraction", C.c_void_p), ("velocity", C.c_void_p), ("count", C.c_void_p)]
 
 
+CONTOUR_DEVICE_POINTERS = 1  # sphx_surface_contour flags
+CONTOUR_FIELDS = dict(fraction=0, density=1)  # SPHX_CONTOUR_FIELD_*
+
+
+class SphxContourOut(C.Structure):
+    _fields_ = [("segments", C.c_void_p), ("cell", C.c_void_p), ("values", C.c_void_p), ("count", C.c_void_p)]
+
+
 SAMPLE_FIELD_BITS = dict(density=1, fraction=2, velocity=4, count=8)  # SPHX_SAMPLE_FIELD_* (sphx_tile_sample_*)
 
 
@@ -303,6 +311,8 @@ SIGNATURES = {
     "sphx_num_boundary": (_u32, [_vp]),
     "sphx_sample_points": (_i, [_vp, _vp, _u32, _i, _u32, C.POINTER(SphxSampleOut)]),
     "sphx_sample_grid": (_i, [_vp, _f, _f, _f, _f, _u32, _u32, _i, _u32, C.POINTER(SphxSampleOut)]),
+    "sphx_surface_contour": (_i, [_vp, _f, _f, _f, _f, _u32, _u32, _i, _i, _f, _u32, _u32, C.POINTER(SphxContourOut)]),
+    "sphx_contour_chain": (_i, [_vp, _u32, _vp, _vp, _vp, C.POINTER(_u32)]),
     "sphx_multi_sample_points": (_i, [_vp, _vp, _u32, _i, _u32, C.POINTER(SphxMultiSampleOut)]),
     "sphx_multi_sample_grid": (_i, [_vp, _f, _f, _f, _f, _u32, _u32, _i, _u32, C.POINTER(SphxMultiSampleOut)]),
     "sphx_sample_merge": (_i, [_u32, C.POINTER(SphxMultiSampleOut), _u32, C.POINTER(SphxMultiSampleOut)]),

@@ -7,7 +7,14 @@
 //                [--emit x,y,w,h[:every=K][:until=S][:vel=vx,vy]] [--drain x0,y0,x1,y1]... [--keep x0,y0,x1,y1]...
 //                [--load-state FILE] [--save-state FILE[:at=STEP]] [--track ID[,ID...] [--track-every E] --track-out FILE] [--fields-out FILE]
 //                [--stats-out FILE [--stats-every K]]
+//                [--contour-out FILE [--contour-grid x0,y0,dx,dy,nx,ny] [--contour-iso V]]
 //                [--help]
+//
+// --contour-out: after the last step, the free surface of the final state (sphx_surface_contour of the fluid fraction, Wendland kernel, at
+// V = 0.5 unless --contour-iso says otherwise; stitched by sphx_contour_chain) as the CSV "line,closed,x,y": the points of line 0, then of
+// line 1, ... (%.9g, which round-trips fp32; a closed line repeats its first point as its last).  --contour-grid gives the lattice (fp32
+// origin and spacing, whole numbers of nodes); the default is 513 x 385 nodes over the app's camera rectangle, Rect(-0.1, -0.1, 2.1, 1.6) x
+// scale.  The JSON line gains "contour_segments" and "contour_lines".
 //
 // --stats-out: the statistics of the whole fluid (sphx_fluid_stats, record 0) are recorded on the device behind every K-th step of the
 // run (sphx_stats_record; --stats-every K, default 1; warm-up and timed steps counted together) and written after the run, one JSON
@@ -115,6 +122,7 @@ static const char* const USAGE =
     "             [--emit x,y,w,h[:every=K][:until=S][:vel=vx,vy]] [--drain x0,y0,x1,y1]... [--keep x0,y0,x1,y1]...\n"
     "             [--load-state FILE] [--save-state FILE[:at=STEP]] [--track ID[,ID...] [--track-every E] --track-out FILE] [--fields-out FILE]\n"
     "             [--stats-out FILE [--stats-every K]]\n"
+    "             [--contour-out FILE [--contour-grid x0,y0,dx,dy,nx,ny] [--contour-iso V]]\n"
     "             [--help]\n"
     "  --load-state FILE            start from a solver state file (sphx_solver_load) instead of the scene\n"
     "  --save-state FILE[:at=STEP]  write a solver state file (sphx_solver_save) after STEP steps of this run; default: after the last step\n"
@@ -124,6 +132,9 @@ static const char* const USAGE =
     "  --stats-out FILE             record the whole fluid's statistics (sphx_stats_record) behind every step, write one JSON line per frame\n"
     "  --stats-every K              ... behind every K-th step only (default 1)\n"
     "  --fields-out FILE            write the final state's flow fields (sphx_particle_fields) as CSV: id,x,y,divergence,vorticity,cx,cy\n"
+    "  --contour-out FILE           write the final state's free surface (sphx_surface_contour + sphx_contour_chain) as CSV: line,closed,x,y\n"
+    "  --contour-grid x0,y0,dx,dy,nx,ny  ... on this lattice (default: 513 x 385 nodes over the camera rectangle of the scene)\n"
+    "  --contour-iso V              ... at fraction V (default 0.5)\n"
     "Prints one JSON line with the throughput, the timer's final step and a checksum of the final state.\n";
 
 static bool parse_list(const std::string& s, size_t count, bool allow_inf, double* out) {
@@ -162,6 +173,8 @@ int main(int argc, char** argv) {
     bool want_stats = false, want_stats_every = false;
     std::string fields_out;
     bool want_fields = false;
+    std::string contour_out, contour_grid_arg, contour_iso_arg;
+    bool want_contour = false, want_contour_grid = false, want_contour_iso = false;
     auto add_rect = [&](std::vector<sphx_rect>& to, const char* opt, const std::string& arg) {
         double v[4];
         if (!parse_list(arg, 4, true, v) || drain_rects.size() + keep_rects.size() >= SPHX_REMOVE_MAX_RECTS) {
@@ -199,6 +212,9 @@ int main(int argc, char** argv) {
         else if (s == "--stats-out") stats_out = a + 1 < argc ? argv[++a] : "", want_stats = true;
         else if (s == "--stats-every") stats_every_arg = next(), want_stats_every = true;
         else if (s == "--fields-out") fields_out = a + 1 < argc ? argv[++a] : "", want_fields = true;
+        else if (s == "--contour-out") contour_out = a + 1 < argc ? argv[++a] : "", want_contour = true;
+        else if (s == "--contour-grid") contour_grid_arg = next(), want_contour_grid = true;
+        else if (s == "--contour-iso") contour_iso_arg = next(), want_contour_iso = true;
         else if (s == "--help" || s == "-h") {
             std::fputs(USAGE, stdout);
             return 0;
@@ -229,6 +245,20 @@ int main(int argc, char** argv) {
     if (want_fields && fields_out.empty()) {
         std::fprintf(stderr, "invalid --fields-out (FILE)\n");
         return 2;
+    }
+    double contour_grid[6] = {0, 0, 0, 0, 0, 0}, contour_iso = 0.5;
+    if (want_contour || want_contour_grid || want_contour_iso) {
+        bool ok = want_contour && !contour_out.empty();
+        if (ok && want_contour_grid)
+            ok = parse_list(contour_grid_arg, 6, false, contour_grid) && contour_grid[2] > 0.0 && contour_grid[3] > 0.0 && contour_grid[4] >= 0.0 &&
+                 contour_grid[5] >= 0.0 && contour_grid[4] == std::floor(contour_grid[4]) && contour_grid[5] == std::floor(contour_grid[5]) &&
+                 contour_grid[4] * contour_grid[5] < 2147483648.0;
+        if (ok && want_contour_iso) ok = parse_double(contour_iso_arg, &contour_iso);
+        if (!ok) {
+            std::fprintf(stderr, "invalid --contour options (--contour-out FILE [--contour-grid x0,y0,dx,dy,nx,ny: finite, dx, dy > 0, nx, ny whole numbers, "
+                                 "nx * ny < 2^31] [--contour-iso V: finite])\n");
+            return 2;
+        }
     }
     uint32_t stats_every = 1;
     if (want_stats || want_stats_every) {
@@ -610,6 +640,53 @@ int main(int argc, char** argv) {
         }
         char buf[64];
         std::snprintf(buf, sizeof(buf), ", \"fields_particles\": %zu", n_final);
+        gauge_json += buf;
+    }
+    if (want_contour) {
+        if (!want_contour_grid) {  // the app's camera rectangle (main.rs:137) x scale
+            contour_grid[0] = contour_grid[1] = -0.1 * (double)scale;
+            contour_grid[2] = 2.2 * (double)scale / 512.0, contour_grid[3] = 1.7 * (double)scale / 384.0;
+            contour_grid[4] = 513.0, contour_grid[5] = 385.0;
+        }
+        const float gx0 = (float)contour_grid[0], gy0 = (float)contour_grid[1], gdx = (float)contour_grid[2], gdy = (float)contour_grid[3];
+        const uint32_t gnx = (uint32_t)contour_grid[4], gny = (uint32_t)contour_grid[5];
+        uint32_t total = 0, lines = 0;
+        sphx_contour_out co{};
+        co.count = &total;
+        int rc = sphx_surface_contour(solver->ctx(), gx0, gy0, gdx, gdy, gnx, gny, SPHX_KERNEL_WENDLAND_C2, SPHX_CONTOUR_FIELD_FRACTION, (float)contour_iso, 0u, 0u, &co);
+        std::vector<float> seg(4 * (size_t)total);
+        if (rc == SPHX_OK && total) {
+            co.segments = seg.data();
+            rc = sphx_surface_contour(solver->ctx(), gx0, gy0, gdx, gdy, gnx, gny, SPHX_KERNEL_WENDLAND_C2, SPHX_CONTOUR_FIELD_FRACTION, (float)contour_iso, total, 0u, &co);
+        }
+        if (rc != SPHX_OK) {
+            std::fprintf(stderr, "--contour-out: %s (status %d)\n", sphx_last_error(solver->ctx()), rc);
+            return 1;
+        }
+        const uint32_t ns = (uint32_t)(seg.size() / 4);
+        std::vector<uint32_t> order(ns), first((size_t)ns + 1);
+        std::vector<uint8_t> closed(ns);
+        if (sphx_contour_chain(seg.data(), ns, order.data(), first.data(), closed.data(), &lines) != SPHX_OK) {
+            std::fprintf(stderr, "--contour-out: sphx_contour_chain failed\n");
+            return 1;
+        }
+        FILE* f = std::fopen(contour_out.c_str(), "w");
+        bool ok = f != nullptr && std::fputs("line,closed,x,y\n", f) >= 0;
+        for (uint32_t k = 0; ok && k < lines; ++k) {
+            const float* s0 = seg.data() + 4 * (size_t)order[first[k]];
+            ok = std::fprintf(f, "%u,%u,%.9g,%.9g\n", k, (unsigned)closed[k], (double)s0[0], (double)s0[1]) > 0;
+            for (uint32_t q = first[k]; ok && q < first[k + 1]; ++q) {
+                const float* s = seg.data() + 4 * (size_t)order[q];
+                ok = std::fprintf(f, "%u,%u,%.9g,%.9g\n", k, (unsigned)closed[k], (double)s[2], (double)s[3]) > 0;
+            }
+        }
+        if (f) ok = std::fclose(f) == 0 && ok;
+        if (!ok) {
+            std::fprintf(stderr, "cannot write %s\n", contour_out.c_str());
+            return 1;
+        }
+        char buf[96];
+        std::snprintf(buf, sizeof(buf), ", \"contour_segments\": %u, \"contour_lines\": %u", total, lines);
         gauge_json += buf;
     }
     if (want_edit) {

@@ -411,6 +411,8 @@ struct sphx_ctx {
         size_t rec_at = 0;                 // word offset of the records in sample_buf (points query)
         uint32_t* null_grid = nullptr;     // device: BLOCK_CELLS empty ranges, then two one-entry directories (flagged / unflagged)
     } tsample;
+    uint32_t* contour_buf = nullptr;  // sphx_surface_contour: lattice values, workgroup offsets (+ the outputs' device copies on the host-pointer path), grown on demand
+    size_t contour_cap = 0;           // ... in 4-byte words
     uint32_t* render_buf = nullptr;  // sphx_render: one owner code per pixel (+ the outputs' device copies on the host-pointer path), grown on demand
     size_t render_cap = 0;           // ... in 4-byte words
     float* fields_buf = nullptr;  // sphx_particle_fields: the requested outputs' device copies on the host-pointer path, grown on demand

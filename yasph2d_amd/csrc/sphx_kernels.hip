@@ -3096,3 +3096,5 @@ __global__ __launch_bounds__(64) void k_publish(DevScalars* scal, Mailbox* mb, u
 #include "sphx_multi_state.inc"
 // an edit of a tiled run, device half: owned records retired by the removal predicate, new owned records behind the local set (kernels + the tile seam)
 #include "sphx_multi_edit.inc"
+// the iso-contour of a sampled field as ordered segments, and the host stitcher that makes polylines of them (kernels + C ABI)
+#include "sphx_contour.inc"
