@@ -1,15 +1,17 @@
 #!/bin/bash
-# Build libsphx from the kernel sources of a COMMIT as a variant library:  tools/ab_build_commit.sh NAME COMMIT [-DFOO ...]
+# Build libsphx from the sources of a COMMIT as a variant library:  tools/ab_build_commit.sh NAME COMMIT [-DFOO ...]
 # (same-box A/B against the working tree's library: SPHX_LIB=yasph2d_amd/variants/libsphx_NAME.so)
+# The commit's whole yasph2d_amd/csrc and include go to a temporary directory and are built there by the commit's own Makefile, with
+# its CXXFLAGS plus the extra flags: every object is the commit's, nothing comes from the working tree.  AB_KEEP_SRC=1 keeps the
+# directory (with --save-temps among the flags its device assembly is what tools/isa_compare.py reads).
 set -e
 root="$(cd "$(dirname "$0")/.." && pwd)"
 name=$1; commit=$2; shift 2
-d=/tmp/ab_src_$name; rm -rf $d; mkdir -p $d
-for f in sphx_kernels.hip sphx_launch.inc sphx_internal.hpp sphx_host.hpp sphx_host.cpp sphx_tiles.cpp; do git -C $root show $commit:yasph2d_amd/csrc/$f > $d/$f; done
-mkdir -p $d/../include_$name; cp -r $root/include $d/..  2>/dev/null || true
-cd $d
-F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wno-unused-value -Wno-unused-result -I$root/include -I$root/yasph2d_amd/csrc"
-/opt/rocm/bin/hipcc $F "$@" -c sphx_kernels.hip -o k.o
-mkdir -p $root/yasph2d_amd/variants
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $root/yasph2d_amd/variants/libsphx_$name.so k.o $root/yasph2d_amd/csrc/sphx_host.o $root/yasph2d_amd/csrc/sphx_tiles.o -ldl -lpthread
-echo built yasph2d_amd/variants/libsphx_$name.so from $commit
+d=$(mktemp -d "${TMPDIR:-/tmp}/ab_src_$name.XXXXXX")
+[ -n "$AB_KEEP_SRC" ] && echo "sources kept in $d" || trap 'rm -rf "$d"' EXIT
+git -C "$root" archive "$commit" yasph2d_amd/csrc include | tar -x -C "$d"
+flags="$(sed -n 's/^CXXFLAGS *?= *//p' "$d/yasph2d_amd/csrc/Makefile") $*"
+make -C "$d/yasph2d_amd/csrc" ARCH=gfx950 CXXFLAGS="$flags" ../libsphx.so
+mkdir -p "$root/yasph2d_amd/variants"
+cp "$d/yasph2d_amd/libsphx.so" "$root/yasph2d_amd/variants/libsphx_$name.so"
+echo "built yasph2d_amd/variants/libsphx_$name.so from $commit"

@@ -85,7 +85,7 @@
                 e_owned = tile_owns(K, pvi.x, pvi.y) ? e : 0.0f;
                 pnew = make_float2(pvi.x + pvi.z * dt, pvi.y + pvi.w * dt);
             }
-            if (ta.hist) count_cell(K, ta.g, i < n, i, pnew, ta.hist, ta.cidx, ta.slot, 1u, scal, ahead_r, &scal->spec.flags);
+            if (ta.hist) count_cell(K, ta.g, i < n, i, pnew, ta.hist, ta.cidx, 1u, scal, ahead_r, &scal->spec.flags);
             knz_store(knz, i, k_bits, scal, knz_tag);
             block_residual_add(e_owned, scal);
             return;
@@ -194,6 +194,6 @@
         if constexpr (SPEC) pnew = make_float2(pvi.x + pvi.z * dt, pvi.y + pvi.w * dt);  // dfsph.rs:499-510, as the quiet exit of k_correct
     }
     if constexpr (SPEC)
-        if (ta.hist) count_cell(K, ta.g, i < n, i, pnew, ta.hist, ta.cidx, ta.slot, 1u, scal, ahead, &scal->spec.flags);
+        if (ta.hist) count_cell(K, ta.g, i < n, i, pnew, ta.hist, ta.cidx, 1u, scal, ahead, &scal->spec.flags);
     if constexpr (KNZ) knz_store(knz, i, k_bits, scal, knz_tag);  // (the grid is rounded up to whole workgroups, and so is knz[])
     block_residual_add(e_owned, scal);  // read by the correction queued behind this launch (ResArgs)

@@ -92,17 +92,12 @@
         L.blk = blk;
         L.i = blk * 256 + threadIdx.x;
         L.h = nb_head(nb, blk, L.i, n);
-        // (position and velocity of the own particle: two 8-byte loads; only the velocity is written back)
-#ifdef SPHX_CORRECT_POS_GLOBAL
-        L.pvi = L.i < n ? ldpv(PVr{posA, vel}, L.i) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-#else
-        // (round 6: only the velocity — the position is in the window this workgroup stages, process() takes it from there: one 8-byte
+        // (the own particle, round 6: only the velocity — the position is in the window this workgroup stages, process() takes it from there: one 8-byte
         // load per thread less, 16 cycles of the CU's address path per wavefront, tools/vmem_issue_bench.hip)
         {
             const float2 vi = gat((const float2*)vel, min(L.i, n ? n - 1u : 0u));
             L.pvi = make_float4(0.0f, 0.0f, vi.x, vi.y);
         }
-#endif
         // first: the first correction of its loop — the accumulated warm-start value starts from zero (dfsph.rs:206-208 / :361-363):
         // nothing is read, and nobody had to write that zero either
         // (clamped, not predicated on i < n: behind that branch the compiler also selects the count word — and waits for it there)
@@ -116,20 +111,7 @@
     };
     auto load_stage = [&](Loaded& L) {
         L.st = nb_stage_load(L.h, nb, L.blk, L.i, n, load_rec, load_rec2);
-        L.ahead = DirAhead{0xFFFFFFFFu, EMPTY};
-#ifdef SPHX_CORRECT_POS_GLOBAL
-        if (!WARM && INV_DT && ca.hist) {
-#else
-        if (false) {  // (requested in process(), once the position is there)
-#endif
-            // the cell count at the end of this kernel needs the directory entry of the particle's block: requested now, with the
-            // staging loads in flight, for the block the particle is in BEFORE it moves (a particle rarely changes its 64 x 64 block)
-            if (L.i < n) {
-                uint32_t cx0, cy0;
-                cell_of(K, make_float2(L.pvi.x, L.pvi.y), cx0, cy0);
-                L.ahead = dir_ahead(ca.g, cx0, cy0);
-            }
-        }
+        L.ahead = DirAhead{0xFFFFFFFFu, EMPTY};  // (requested in process(), once the position is there)
     };
     auto verdict = [&] {
     if (judge) {
@@ -235,7 +217,7 @@
                     store_cold(&warm[i], warm_i + ki, K.nt_cold);  // dfsph.rs:142 / :296
                 }
                 if (INV_DT)
-                    if (ca.hist) count_cell(K, ca.g, i < n, i, pnew, ca.hist, ca.cidx, ca.slot, 1u, scal, ahead);
+                    if (ca.hist) count_cell(K, ca.g, i < n, i, pnew, ca.hist, ca.cidx, 1u, scal, ahead);
                 SPHX_CORRECT_LEAVE(true);
             }
         }
@@ -303,7 +285,7 @@
                             if constexpr (THIN)
                                 recount_cell(K, ca.g, i < n, i, pnew, ca.hist, ca.cidx, scal, ahead, zs.count);
                             else
-                                count_cell(K, ca.g, i < n, i, pnew, ca.hist, ca.cidx, ca.slot, 1u, scal, ahead);
+                                count_cell(K, ca.g, i < n, i, pnew, ca.hist, ca.cidx, 1u, scal, ahead);
                         }
                     SPHX_CORRECT_LEAVE(false);
                 }
@@ -323,7 +305,6 @@
     (void)blk;
     (void)id_i;
     __syncthreads();
-#ifndef SPHX_CORRECT_POS_GLOBAL
     if (i < n) {
         const float2 pi = h.wide ? gat(posA, i) : rec.vec<0>((i - h.lw0) * 4u);
         pvi.x = pi.x, pvi.y = pi.y;
@@ -335,7 +316,6 @@
             ahead = dir_ahead(ca.g, cx0, cy0);
         }
     }
-#endif
     (void)ahead;
     float2 pnew = make_float2(0.0f, 0.0f);
     if (i < n) {
@@ -403,7 +383,7 @@
                     cell_of(K, pnew, cx, cy);
                     if (!((id_i >> 31) != 0 && pnew.x == pnew.x && rect_has(K.tile, cx, cy, tc.halo))) pnew.x = __uint_as_float(0x7FC00000u);
                 }
-                count_cell(K, ca.g, i < n, i, pnew, ca.hist, ca.cidx, ca.slot, 1u, scal, ahead);
+                count_cell(K, ca.g, i < n, i, pnew, ca.hist, ca.cidx, 1u, scal, ahead);
                 // (the send counts last: the barrier they need then only holds back wavefronts that have nothing left to do; a tile
                 // without neighbours has none to write)
                 if (tc.n) {
@@ -420,7 +400,7 @@
             if constexpr (THIN)  // (the producer has counted p + v* dt: move the particles whose corrected velocity takes them elsewhere)
                 recount_cell(K, ca.g, i < n, i, pnew, ca.hist, ca.cidx, scal, ahead, zs.count);
             else
-                count_cell(K, ca.g, i < n, i, pnew, ca.hist, ca.cidx, ca.slot, 1u, scal, ahead);  // every density correction counts
+                count_cell(K, ca.g, i < n, i, pnew, ca.hist, ca.cidx, 1u, scal, ahead);  // every density correction counts
         }
     };
     process(LA);

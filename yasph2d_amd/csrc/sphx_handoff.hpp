@@ -44,7 +44,7 @@ struct BuildHandoff {
     }
 };
 
-// The cell count in gdyn.hist / key / slot of a neighbour build that has not come yet, and who made it:
+// The cell count in gdyn.hist / key of a neighbour build that has not come yet, and who made it:
 //   Nobody      the histogram is all-zero, as between any two builds
 //   Correction  a single context's density correction (CountArgs), for its n particles: the step's own build starts from it
 //   Pack        tile_pack_impl or sphx_tile_count_kept, for the n particles the tile keeps: the re-grid counts the arrivals only

@@ -145,9 +145,6 @@ struct GridView {
     const uint32_t* dir;
     const uint2* fine;  // {first sorted particle of the cell, one past its last}
     uint32_t bx0, by0, nbx, nby;
-    // the re-grid's per-particle word (count_cell): cell index in the low `cbits` bits (the table has fewer than 2^cbits - 1 entries),
-    // the particle's arrival slot inside its cell above them (saturating at cell_slot_max(): then the slot is in the side array)
-    uint32_t cbits;
 };
 // The same grid as the neighbour build reads it (round 4): a second directory `dirn` in which NO entry is special —
 //   * a block the directory does not cover points at the NULL BLOCK, 4096 all-zero entries behind the cell table ({0, 0}: an empty
@@ -321,15 +318,7 @@ struct Grid {
     std::vector<uint32_t> h_dir;  // host copy of dir
     bool fine_valid = false;      // `fine` holds the cell ranges of a build made with THIS directory
     uint32_t len() const { return nblk * BLOCK_CELLS; }
-    uint32_t cbits_floor = 1;  // SPHX_CBITS_MIN, read ONCE in sphx_create (a test knob — with 29 a packed word of count_cell has room for
-                               // arrival slots 0..6 only, and ordinary scenes exercise the side array); round 5 read the environment on
-                               // every view(): several getenv calls per step, and not safe against a concurrent setenv
-    uint32_t cbits() const {  // bits of a cell index: len() <= 2^cbits - 1, so that no packed word of count_cell equals EMPTY
-        uint32_t b = cbits_floor < 1u ? 1u : cbits_floor > 31u ? 31u : cbits_floor;
-        while (b < 31u && ((1u << b) - 1u) < len()) ++b;
-        return b;
-    }
-    GridView view() const { return GridView{dir, fine, bx0, by0, nbx, nby, cbits()}; }
+    GridView view() const { return GridView{dir, fine, bx0, by0, nbx, nby}; }
     NbGrid nview() const { return nbx && nby ? NbGrid{dirn, fine, bx0, by0, nbx, nbx - 1u, nby - 1u} : NbGrid{dirn, fine, 0u, 0u, 1u, 0u, 0u}; }
 };
 
@@ -492,7 +481,7 @@ struct sphx_ctx {
     float *density = nullptr, *alpha = nullptr, *alpha2 = nullptr, *kappa = nullptr, *stiff = nullptr;  // [N]
     float *kappa2 = nullptr, *stiff2 = nullptr;  // gather targets (tile mode only)
     uint32_t *pid = nullptr, *pid2 = nullptr;
-    uint32_t *key = nullptr, *slot = nullptr, *order = nullptr;  // grid-build scratch, sized for max(N, B)
+    uint32_t *key = nullptr, *order = nullptr;  // grid-build scratch, sized for max(N, B)
     uint32_t idx_cap = 0;
     uint32_t soff() const { return capN; }
     // boundary (own arrays for the one-off static grid build)
@@ -585,7 +574,7 @@ struct sphx_ctx {
     uint32_t scan_partials_cap = 0;
     unsigned long long* scan_state = nullptr;  // one-pass scan: {epoch, flag, value} per 4096-entry tile
     uint32_t scan_state_cap = 0, scan_epoch = 0;
-    // The cell count in gdyn.hist / key / slot of a build that has not come yet (sphx_handoff.hpp).  Nobody -> Correction / Classifier: a
+    // The cell count in gdyn.hist / key of a build that has not come yet (sphx_handoff.hpp).  Nobody -> Correction / Classifier: a
     // counting / classifying density correction (enqueue_iteration); -> Pack: tile_pack_impl (its own count, or the classifier's taken
     // over), sphx_tile_count_kept.  Back to Nobody: build_grid (consumed), drop_fused_count, drop_class_count (the classifier's only),
     // clear_histograms, set_directory.  A Classifier's count loses `takeable` in the tile entry points without a flush_pending_advect.

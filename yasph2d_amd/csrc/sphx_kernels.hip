@@ -428,7 +428,7 @@ __global__ __launch_bounds__(256) void k_scan_reduce(const uint32_t* __restrict_
     }
 }
 
-// out[i] = {exclusive prefix of in[], + in[i]} = the cell's particle range; in[] is zeroed
+// out[i] = {exclusive prefix of in[], + in[i]} = the cell's particle range; in[] stays (k_scatter counts it down to zero)
 __global__ __launch_bounds__(256) void k_scan_apply(uint32_t* __restrict__ in, uint2* __restrict__ out, uint32_t len,
                                                      const uint32_t* __restrict__ partials) {
     const uint32_t base = blockIdx.x * SCAN_TILE;
@@ -445,17 +445,11 @@ __global__ __launch_bounds__(256) void k_scan_apply(uint32_t* __restrict__ in, u
             v[4 * k + 1] = q.y;
             v[4 * k + 2] = q.z;
             v[4 * k + 3] = q.w;
-#ifdef SPHX_SLOT_AT_COUNT
-            p4[k] = make_uint4(0, 0, 0, 0);
-#endif
         }
     } else {
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
             v[k] = (t0 + k < len) ? in[t0 + k] : 0;
-#ifdef SPHX_SLOT_AT_COUNT
-            if (t0 + k < len) in[t0 + k] = 0;
-#endif
         }
     }
 #pragma unroll
@@ -494,7 +488,7 @@ __device__ __forceinline__ unsigned long long scan_word(uint32_t epoch, uint32_t
     return ((unsigned long long)epoch << 32) | ((unsigned long long)flag << 30) | value;  // value < 2^30 (contexts hold < 2^28 slots)
 }
 // Round 4: a tile of the table that holds no particle costs its 16 KiB of histogram reads and nothing else.  The histogram is
-// only re-zeroed where it was not zero (per thread), and the tile's 32 KiB of cell ranges are not rewritten when the tile was
+// not written (k_scatter counts it down to zero again), and the tile's 32 KiB of cell ranges are not rewritten when the tile was
 // empty at the previous build of this grid as well (tile_empty[], kept by this kernel; set for every tile when set_directory zeroes
 // the table): whoever looks at a cell of such a tile only needs start == end, which stale-but-equal entries still say.  The dam
 // break's table is a third fringe and empty interior blocks at t = 0 and more than half once the splashes have spread it.
@@ -520,16 +514,10 @@ __global__ __launch_bounds__(256) void k_scan_onepass(uint32_t* __restrict__ in,
             uint4* const p4 = reinterpret_cast<uint4*>(in + t);
             const uint4 q = *p4;
             v[k][0] = q.x, v[k][1] = q.y, v[k][2] = q.z, v[k][3] = q.w;
-#ifdef SPHX_SLOT_AT_COUNT
-            if ((q.x | q.y | q.z | q.w) != 0u) *p4 = make_uint4(0, 0, 0, 0);  // the histogram is re-zeroed where it was not zero
-#endif  // (round 6: k_scatter counts it down to zero again)
         } else {
 #pragma unroll
             for (uint32_t c = 0; c < 4; ++c) {
                 v[k][c] = (t + c < len) ? in[t + c] : 0u;
-#ifdef SPHX_SLOT_AT_COUNT
-                if (t + c < len && v[k][c] != 0u) in[t + c] = 0u;
-#endif
             }
         }
     }
@@ -622,12 +610,10 @@ __global__ __launch_bounds__(256) void k_scan_onepass(uint32_t* __restrict__ in,
     }
 }
 
-// the largest arrival slot count_cell's packed word can hold is one less: this value says "look in slot[]"
-__device__ __forceinline__ uint32_t cell_slot_max(uint32_t cbits) { return 0xFFFFFFFFu >> cbits; }
 // what a kernel that ends with the re-grid's cell count (count_cell) is handed
 struct CountArgs {
     GridView g;
-    uint32_t *hist, *cidx, *slot;
+    uint32_t *hist, *cidx;
     float dt;  // the step (host value; with dt_dev the device's)
 };
 
@@ -637,13 +623,12 @@ struct CountArgs {
 // a1 (+a17): cell of every particle (neighborhood_search.rs:111-114) and the per-cell histogram in one pass.  ADVECT fuses the
 // position update x += v* dt (dfsph.rs:499-510) in front.  Particles arrive almost sorted (they were in cell order one step
 // ago), so equal cells sit in adjacent lanes: each run of equal cells inside a wavefront does ONE atomic for the whole run.
-// The value returned by the atomic is an arbitrary arrival slot inside the cell; k_rank_gather restores the stable order.
-// cidx[i] = the particle's index into the fine table (round 6; rounds 1-5 — SPHX_SLOT_AT_COUNT — also took the arrival slot here, from
-// the atomic's returned value, and packed it into the word's upper bits, GridView::cbits, with a side array for slots that did not fit).
+// cidx[i] = the particle's index into the fine table, nothing else: the arrival slot inside the cell is taken by k_scatter (rounds 1-5
+// took it here, from the atomic's returned value, and packed it into the word's upper bits); k_rank_gather restores the stable order.
 // Called by ALL lanes of a wavefront (live = this lane holds particle i at position p).
 // flag_word: where the DF_* flags of the count go (nullptr: DevScalars::flags; the speculative count of the quiet take-over: SpecLine)
 __device__ __forceinline__ void count_cell(const Consts& K, const GridView& g, bool live, uint32_t i, float2 p, uint32_t* __restrict__ hist,
-                                           uint32_t* __restrict__ cidx, uint32_t* __restrict__ slot, uint32_t ring, DevScalars* __restrict__ scal,
+                                           uint32_t* __restrict__ cidx, uint32_t ring, DevScalars* __restrict__ scal,
                                            const DirAhead ahead = DirAhead{0xFFFFFFFFu, EMPTY}, uint32_t* flag_word = nullptr) {
     const uint32_t lane = threadIdx.x & 63;
     uint32_t idx = EMPTY;
@@ -676,30 +661,16 @@ __device__ __forceinline__ void count_cell(const Consts& K, const GridView& g, b
     const uint32_t prev = dpp_mov<0x138>(idx, idx);  // wave_shr:1 — the cell of the lane below (lane 0: its own; unused)
     const bool head = (lane == 0) || (idx != prev);
     const unsigned long long mask = __ballot(head);
-    const uint32_t start = 63u - (uint32_t)__clzll(mask & (~0ull >> (63u - lane)));
     const unsigned long long rest = (lane == 63) ? 0ull : (mask >> (lane + 1));
     const uint32_t end = rest ? lane + (uint32_t)__ffsll((long long)rest) : 64u;
-#ifdef SPHX_SLOT_AT_COUNT  // (rounds 1-5: the arrival slot taken HERE, with the atomic's returned value, and packed into the word)
-    uint32_t base = 0;
-    if (head && idx != EMPTY) base = atomicAdd(&hist[idx], end - lane);
-    base = __shfl(base, start, 64);
-    if (live) {
-        const uint32_t sl = base + (lane - start), sl_max = cell_slot_max(g.cbits);
-        cidx[i] = (idx != EMPTY) ? idx | (min(sl, sl_max) << g.cbits) : EMPTY;
-        if (idx != EMPTY && sl >= sl_max) slot[i] = sl;
-    }
-#else
     // Round 6: the count only COUNTS — a no-return atomic, nothing to wait for.  The returning form ended every workgroup of the last
     // density correction with a memory round trip (the slot had to come back before the packed word could be stored): 62 500
     // workgroups in 30 generations of the chip, ~1.5 us each — most of the 56 us the fused count cost that kernel at 16 M
     // (profiles/r06_experiments/fused_count.txt).  The slot inside the cell is taken where it is used, by k_scatter: it counts the
     // histogram DOWN again (the returned value is the slot; four particles per lane in flight), which also leaves the histogram
     // all-zero for the next count — the scan no longer clears it.
-    (void)slot;
-    (void)start;
     if (head && idx != EMPTY) atomicAdd(&hist[idx], end - lane);
     if (live) cidx[i] = idx;
-#endif
 }
 // Recount (k_correct_thin on its marked path): the cell count was made ahead of the correction, from the position the particle
 // reaches if the correction changes nothing (k_compute_error<false, ., KNZ, TAKE>).  The correction has run: the cell is computed
@@ -734,8 +705,7 @@ __device__ __forceinline__ void recount_cell(const Consts& K, const GridView& g,
 template <bool ADVECT>
 __global__ __launch_bounds__(256) void k_key_count(PVr PV, const float2* __restrict__ pos_in,
                                                     uint32_t n, float dt, Consts K, GridView g, uint32_t* __restrict__ hist,
-                                                    uint32_t* __restrict__ cidx, uint32_t* __restrict__ slot, uint32_t ring,
-                                                    DevScalars* __restrict__ scal, uint32_t first) {
+                                                    uint32_t* __restrict__ cidx, uint32_t ring, DevScalars* __restrict__ scal, uint32_t first) {
     const uint32_t i = first + xcd_bid(K.rev, K.xcd_shift) * 256 + threadIdx.x;
     float2 p = make_float2(0.0f, 0.0f);
     if (i < n) {
@@ -748,7 +718,7 @@ __global__ __launch_bounds__(256) void k_key_count(PVr PV, const float2* __restr
             p = pos_in[i];
         }
     }
-    count_cell(K, g, i < n, i, p, hist, cidx, slot, ring, scal);
+    count_cell(K, g, i < n, i, p, hist, cidx, ring, scal);
 }
 
 // order[cell_start + slot] = i  (unstable within a cell; k_rank_gather restores the stable order).  Bit 31 marks the FIRST slot of a
@@ -760,9 +730,8 @@ constexpr uint32_t ORDER_HEAD = 0x80000000u, ORDER_INDEX = 0x7FFFFFFFu;  // (con
 #define SPHX_SCATTER_PER_LANE 4
 #endif
 constexpr uint32_t SCATTER_PER_LANE = SPHX_SCATTER_PER_LANE;
-__global__ __launch_bounds__(256) void k_scatter(const uint32_t* __restrict__ cidx, const uint32_t* __restrict__ slot, uint32_t n,
-                                                  const uint2* __restrict__ fine, uint32_t* __restrict__ order, uint32_t cbits,
-                                                  uint32_t* __restrict__ hist, uint32_t rev) {
+__global__ __launch_bounds__(256) void k_scatter(const uint32_t* __restrict__ cidx, uint32_t n, const uint2* __restrict__ fine,
+                                                  uint32_t* __restrict__ order, uint32_t* __restrict__ hist, uint32_t rev) {
     // (lane t of a workgroup takes the particles b0 + t, b0 + 256 + t, ...: every load and every store of a wavefront is one run of
     // consecutive words — particles arrive nearly sorted, so consecutive particles go to consecutive slots)
     const uint32_t b0 = xcd_bid(xcd_packed_rev(rev), xcd_packed_shift(rev)) * (256u * SCATTER_PER_LANE) + threadIdx.x;  // (rev: xcd_scatter_pack)
@@ -772,24 +741,11 @@ __global__ __launch_bounds__(256) void k_scatter(const uint32_t* __restrict__ ci
     for (uint32_t u = 0; u < SCATTER_PER_LANE; ++u) w[u] = b0 + u * 256u < n ? cidx[b0 + u * 256u] : EMPTY;
     uint32_t first[SCATTER_PER_LANE];
 #pragma unroll
-    for (uint32_t u = 0; u < SCATTER_PER_LANE; ++u) first[u] = fine[w[u] == EMPTY ? 0u : w[u] & ((1u << cbits) - 1u)].x;  // four gathers in flight
-#ifdef SPHX_SLOT_AT_COUNT
-    (void)hist;
-#pragma unroll
-    for (uint32_t u = 0; u < SCATTER_PER_LANE; ++u) {
-        if (w[u] == EMPTY) continue;
-        const uint32_t i = b0 + u * 256u;
-        uint32_t sl = w[u] >> cbits;
-        if (sl == cell_slot_max(cbits)) sl = slot[i];
-        const uint32_t p = first[u] + sl;
-        if (p < n) order[p] = i | (sl == 0u ? ORDER_HEAD : 0u);
-    }
-#else
+    for (uint32_t u = 0; u < SCATTER_PER_LANE; ++u) first[u] = fine[w[u] == EMPTY ? 0u : w[u]].x;  // four gathers in flight
     // The slot inside the cell (count_cell): the histogram holds each cell's population; a run of lanes with the same cell takes it
     // down by the run's length with ONE returning atomic and shares out the slots old - 1, old - 2, ... — every particle of the cell
     // gets one of 0 .. population - 1, whoever comes first, and the histogram is back at zero when the last one has been.  The four
     // atomics of a lane are in flight together with its four table look-ups.
-    (void)slot;
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t old[SCATTER_PER_LANE], pos_in_run[SCATTER_PER_LANE];
 #pragma unroll
@@ -815,7 +771,6 @@ __global__ __launch_bounds__(256) void k_scatter(const uint32_t* __restrict__ ci
         const uint32_t p = first[u] + sl;
         if (p < n) order[p] = i | (sl == 0u ? ORDER_HEAD : 0u);
     }
-#endif
 }
 
 struct GatherArgs {
@@ -861,7 +816,7 @@ constexpr uint32_t GATHER_PER_LANE = SPHX_GATHER_PER_LANE;
 // the upper bound n.
 __global__ __launch_bounds__(256) void k_rank_gather(const uint32_t* __restrict__ order, const uint32_t* __restrict__ cidx, uint32_t n,
                                                       uint32_t n_in, const uint2* __restrict__ fine, GatherArgs a,
-                                                      const uint32_t* __restrict__ n_dev, uint32_t cbits, uint32_t rev) {
+                                                      const uint32_t* __restrict__ n_dev, uint32_t rev) {
     if (n_dev) n = min(n, *n_dev);
     // GATHER_PER_LANE slots per lane (lane t: b0 + t, b0 + 256 + t, ...): the loads of all of them are requested before the first one
     // is placed.  ONE is the default: unlike the scatter, whose lanes had a single 4-byte load each, this kernel has 24 bytes per slot
@@ -936,7 +891,7 @@ __global__ __launch_bounds__(256) void k_rank_gather(const uint32_t* __restrict_
         } else {
             const uint32_t cw = cidx[i];
             if (cw == EMPTY) continue;
-            const uint2 se = fine[cw & ((1u << cbits) - 1u)];
+            const uint2 se = fine[cw];
             const uint32_t s = se.x;
             uint32_t e = se.y;
             if (e > n) e = n;
@@ -1187,7 +1142,7 @@ __global__ __launch_bounds__(256) void k_tile_pack(const float2* __restrict__ ve
     }
     // first pass of the re-grid that follows the exchange, for the particles the tile keeps: their cell and the histogram (the
     // arrivals are counted by the re-grid itself; a retired particle has no cell)
-    if (ca.hist) count_cell(K, ca.g, i < n, i, pkeep, ca.hist, ca.cidx, ca.slot, 1u, scal);
+    if (ca.hist) count_cell(K, ca.g, i < n, i, pkeep, ca.hist, ca.cidx, 1u, scal);
 }
 // append the received records (peer after peer, `cap` slots each) behind the current particles; unused slots are marked dropped
 struct TileInbox {
@@ -1352,7 +1307,6 @@ __device__ __forceinline__ void slots9n(const NbGrid& g, uint32_t cx, uint32_t c
     // (36 % of the wavefronts of the dam break at t = 0, counted on the host): the full network for the wavefront.
     const bool inside = ((cx & 63u) - 1u) < 62u && ((cy & 63u) - 1u) < 62u;
     const bool all_inside = !__any(!inside);
-#ifndef SPHX_DIRN_NINE
     if (all_inside) {
         // ... and ONE directory entry: the eight other look-ups would return the same word, each holding the CU's address path like a
         // load of 64 different ones (round 6, tools/vmem_issue_bench.hip)
@@ -1366,7 +1320,6 @@ __device__ __forceinline__ void slots9n(const NbGrid& g, uint32_t cx, uint32_t c
         sort9_monotone(slot[0], slot[1], slot[2], slot[3], slot[4], slot[5], slot[6], slot[7], slot[8]);
         return;
     }
-#endif
     flags = 0;
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy)
@@ -1383,23 +1336,14 @@ __device__ __forceinline__ void slots9n(const NbGrid& g, uint32_t cx, uint32_t c
         sort9(slot[0], slot[1], slot[2], slot[3], slot[4], slot[5], slot[6], slot[7], slot[8]);
 }
 __device__ __forceinline__ void ranges9n(const NbGrid& g, const uint32_t (&slot)[9], uint32_t (&s)[9], uint32_t (&e)[9]) {
-#ifndef SPHX_FINE_SPLIT
+    // (one 8-byte gather per cell.  Round 6 tried start and end as TWO 4-byte gathers, which hold the CU's address path for less in
+    // tools/vmem_issue_bench.hip: no gain in the kernel, 494.6 against 491.7 us at 16 M.)
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
         const uint2 se = gat(g.fine, slot[t]);
         s[t] = se.x;
         e[t] = se.y;
     }
-#else
-    // (experiment, round 6: start and end as TWO 4-byte gathers — a 4-byte load of ~20 consecutive entries holds the CU's address path
-    // for ~4 cycles in tools/vmem_issue_bench.hip, an 8-byte one for 16.  No gain in the kernel: 494.6 against 491.7 us at 16 M.)
-    const uint32_t* const f32 = (const uint32_t*)g.fine;
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-        s[t] = gat(f32, 2u * slot[t]);
-        e[t] = gat(f32, 2u * slot[t] + 1u);
-    }
-#endif
 }
 
 // 8 waves per SIMD = 8 workgroups per CU: the staged rows (12 KiB) + the window (4 KiB; two of them in the form that also stages
@@ -1581,11 +1525,7 @@ __device__ __forceinline__ void nb_tail(const float2* __restrict__ posA, uint32_
     f32x2 ws = {0.0f, 0.0f};                        // WARM: sum of (k_i + k_j) grad W_ij, dfsph.rs:316-344, as k_correct<true, false> adds it
     const float ki = 0.5f * fmaxf(warm_i, dv.lim);  // dfsph.rs:356-358
     const f32x2 pi2 = {pi.x, pi.y}, vi2 = {vi.x, vi.y}, mass2 = {K.mass, K.mass};
-#ifdef SPHX_ABL_NOPHASE2
-    for (uint32_t k0 = 0; false;) {
-#else
     for (uint32_t k0 = 0; k0 < mct; k0 += 4) {
-#endif
         uint32_t E[4];  // window byte offsets (see entry_slot)
         float2 rj[4];
         float2 vj[4];
@@ -1619,14 +1559,12 @@ __device__ __forceinline__ void nb_tail(const float2* __restrict__ posA, uint32_
             for (uint32_t u = 0; u < 4; ++u) {
                 if (fm[u] == 0ull) continue;  // (scalar)
                 const uint32_t gb = w0b + E[u];  // 8 g
-#ifndef SPHX_ABL_NOFAR2  // (timing experiments: the second loop does NOT re-read out-of-window records — results are wrong)
                 if (FUSE && far[u]) {
                     rj[u] = *(const float2*)((const char*)posA + gb);
                     if (DIV) vj[u] = *(const float2*)((const char*)dv.vel + gb);  // boundary records carry v = 0 (the static form of dfsph.rs:274 is v_i alone)
                     if (WARM) wj4[u] = gat(dv.warm, (gb >> 3) < soff ? (gb >> 3) : i);  // warm[] has no boundary tail (clamped below, once the trip's gathers are all out)
                     SPHX_STAMP_VMWAIT(12)
                 }
-#endif
                 if (cap != 0u && staged) {
                     const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(fm[u] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fm[u], run));
                     run += (uint32_t)__popcll(fm[u]);
@@ -1828,15 +1766,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == 2 ?
     float2 wreg[NWIN];
     float2 vreg[MODE == 2 ? NWIN : 1];
     float2 vi = make_float2(0.0f, 0.0f);
-#ifdef SPHX_BUILD_SINGLE
-#pragma unroll
-    for (uint32_t u = 0; u < NWIN; ++u) wreg[u] = gat(posA, w0 + min(threadIdx.x + u * 256u, wlen - 1u));
-    if (MODE == 2) {
-#pragma unroll
-        for (uint32_t u = 0; u < NWIN; ++u) vreg[u] = gat(dv.vel, w0 + min(threadIdx.x + u * 256u, wlen - 1u));
-        vi = gat(dv.vel, live ? i : b0);
-    }
-#else
     // Round 6: TWO window slots per thread in one 16-byte load (slots w0 + 2t, w0 + 2t + 1; w0 is even) — as nb_stage_load does
     static_assert(NWIN == 2 && (WIN_HALO & 1u) == 0u, "two slots per thread");
     const uint32_t wpair = w0 + min(2u * threadIdx.x, (wlen - 1u) & ~1u);
@@ -1848,7 +1777,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == 2 ?
         const Pair<float2> q = gat2(dv.vel, wpair);
         vreg[0] = q.a, vreg[1] = q.b;  // (the own velocity: from the window, behind the barrier)
     }
-#endif
     float sreg[MODE == 3 ? NWIN : 1];
     float warm_i = 0.0f;
     if (MODE == 3) {
@@ -1887,16 +1815,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == 2 ?
             for (uint32_t u = 0; u < 4; ++u) G[u] = gp[u];
         }
     };
-#ifndef SPHX_NO_FAR_PREFETCH
     if (scan) prefetch(0);
-#endif
 #pragma unroll
     for (uint32_t u = 0; u < NWIN; ++u) {
-#ifdef SPHX_BUILD_SINGLE
-        const uint32_t tw = threadIdx.x + u * 256u;
-#else
         const uint32_t tw = 2u * threadIdx.x + u;
-#endif
         if (tw < wlen) {
             win[tw] = wreg[u];
             if (MODE == 2) vwin[tw] = vreg[u];
@@ -1908,15 +1830,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == 2 ?
     // pad slots: a candidate read past the window's end finds a NaN position (rejected) until the re-read from global memory replaces it
     if (threadIdx.x < WIN_PAD) win[wlen + threadIdx.x] = make_float2(__uint_as_float(0x7FC00000u), 0.0f);
     __syncthreads();
-#ifndef SPHX_BUILD_SINGLE
     if (MODE == 2 && live) vi = vwin[i - w0];
-#endif
     SPHX_STAMP(0)
     uint32_t ct = 0;
     if (scan) {
         // phase 1: filter
         SPHX_STAMP(1)
-#ifndef SPHX_ABL_NOLOOP
         // the list row the next accepted candidate goes to, as an LDS byte address (row ct of this lane): it moves by one row per
         // accepted candidate.  t_dump: the dump row (one for the workgroup: what is written there is never read); t_fast: while no
         // lane of the wavefront is past it, the four candidates of a trip land in staged rows whatever is accepted: no clamp, no spill test.
@@ -1956,8 +1875,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == 2 ?
                         pj[W - 1] = make_float2(p23.z, p23.w);
                     }
                 }
-#ifndef SPHX_ABL_NOFAR1  // (timing experiments: out-of-window candidates are NOT re-read from global memory — results are wrong)
-#ifndef SPHX_NO_FAR_PREFETCH
                 if (FIRST) {
                     if (ab >= far_lim) {
                         SPHX_STAMP_VMWAIT(8)
@@ -1966,7 +1883,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == 2 ?
                     }
                     if (t < 8) prefetch(t + 1);  // (G is free again)
                 } else
-#endif
                 if (ab >= far_lim) {
                     // the first (ab "negative": j < w0) or the last of the four lies outside the window: this lane takes ALL of them from
                     // global memory (one address, loads with immediate offsets; what the window holds is the same data, and the
@@ -1976,7 +1892,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == 2 ?
                     for (uint32_t u = 0; u < W; ++u) pj[u] = gp[u];
                     SPHX_STAMP_VMWAIT(10)
                 }
-#endif
                 bool acc[W];
 #pragma unroll
                 for (uint32_t u = 0; u < W; ++u) {
@@ -2000,18 +1915,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == 2 ?
                 a[0] = ta;
 #pragma unroll
                 for (uint32_t u = 0; u < W; ++u) a[u + 1] = a[u] + (acc[u] ? ROW_B : 0u);
-#ifdef SPHX_ABL_NOAPPEND  // (timing experiments: accepted candidates are counted, not stored — results are wrong)
-                if (false) {
-#else
                 if (!__any(ta > t_fast)) {
-#endif
 #pragma unroll
                     for (uint32_t u = 0; u < W; ++u) lds_store_u32(a[u], ab + 8u * u);
                 } else {
-#ifndef SPHX_ABL_NOAPPEND
 #pragma unroll
                     for (uint32_t u = 0; u < W; ++u) lds_store_u32(a[u] < t_end ? a[u] : t_dump, ab + 8u * u);
-#endif
                     if (a[W] > t_end) {  // rare: rows past the staged ones live in global memory (32-bit slots, at their wide address)
 #pragma unroll
                         for (uint32_t u = 0; u < W; ++u) {
@@ -2027,13 +1936,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == 2 ?
                 trip(std::integral_constant<uint32_t, 4>{}, std::integral_constant<int, 1>{});
                 while (ab != eb) trip(std::integral_constant<uint32_t, 2>{}, std::integral_constant<int, 0>{});
             }
-#ifndef SPHX_NO_FAR_PREFETCH
             else if (t < 8)
                 prefetch(t + 1);  // (an empty cell makes no trip: the next cell's request goes out from here)
-#endif
         }
         ct = (ta - t_base) / ROW_B;
-#endif
     }
     SPHX_STAMP(2)
     nb_tail<MODE, TAKE>(posA, n, soff, K, gs, list, counts, wave, remote, density, alpha, scal, i, b0, w0, wlen, live, scan, pi, cx, cy, maybe_static, ct, tile, win, vwin, vi, dv, swin, warm_i
@@ -2175,20 +2081,12 @@ struct NbStaged {  // the records a thread has requested for the staging area: w
     uint32_t g[NB_NR];  // [N|B] slots of the table lines
 };
 // load2(g) -> Pair of the records of the slots g, g + 1 (g even): the window is requested two slots per thread (round 6; until then
-// one slot per thread in two rounds — SPHX_STAGE_SINGLE), thread t holds the slots lw0 + 2t, lw0 + 2t + 1 in w[0], w[1].
+// one slot per thread in two rounds), thread t holds the slots lw0 + 2t, lw0 + 2t + 1 in w[0], w[1].
 template <class L, class L2>
 __device__ __forceinline__ auto nb_stage_load(NbHead& h, const NbView& nb, uint32_t blk, uint32_t i, uint32_t n, L&& load, L2&& load2) -> NbStaged<decltype(load(0u))> {
     NbStaged<decltype(load(0u))> st;
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t (&g)[NB_NR] = st.g;
-#ifdef SPHX_STAGE_SINGLE
-    (void)load2;
-#pragma unroll
-    for (uint32_t u = 0; u < NB_NW; ++u) {
-        const uint32_t t = threadIdx.x + u * 256u;
-        st.w[u] = load(h.lw0 + min(t, h.lwlen ? h.lwlen - 1u : 0u));  // clamped, not predicated: no branch between the loads
-    }
-#else
     {
         static_assert(NB_NW == 2 && (LIST_HALO & 1u) == 0u, "two slots per thread; the window starts at an even slot");
         // (clamped, not predicated.  lw0 is even; the last pair may reach one slot past the window's end, i.e. at most one record past the
@@ -2197,20 +2095,12 @@ __device__ __forceinline__ auto nb_stage_load(NbHead& h, const NbView& nb, uint3
         st.w[0] = pr.a;
         st.w[1] = pr.b;
     }
-#endif
     nb_head_late(h, nb, blk, i, n);  // (waits for the count word: everything that does not depend on it is in flight)
 #pragma unroll
     for (uint32_t u = 0; u < NB_NR; ++u) g[u] = h.g[u];
     // (every table line is fetched, used or not: loading lines 64.. only for the wavefronts with more than 64 out-of-window
     // neighbours saved 4 bytes per particle and walk at 16 M (-0.7 % of the step) and cost 3 % at 1 M — the branch waits for the
     // wavefront's count word; profiles/r03_experiments/predict_fusion.txt section 6)
-#ifdef SPHX_ABL_NOREMOTE  // (traffic / timing experiments: the out-of-window records are NOT fetched — results are wrong)
-    for (uint32_t u = 0; u < NB_NR; ++u) st.r[u] = load(h.lw0);
-#else
-#ifdef SPHX_REMOTE_ALWAYS
-#pragma unroll
-    for (uint32_t u = 0; u < NB_NR; ++u) st.r[u] = load(lane + u * 64u < h.R ? g[u] : h.lw0);
-#else
     // Round 6: the records of lines 64.. are only requested by a wavefront that has such lines (h.R: a scalar, long there — it was
     // requested with the count word nb_head_late has just waited for).  A vector load of eight bytes or more per lane holds the CU's
     // address path for 16 cycles whatever its exec mask (tools/vmem_issue_bench.hip): the second round cost every wavefront one such
@@ -2218,8 +2108,6 @@ __device__ __forceinline__ auto nb_stage_load(NbHead& h, const NbView& nb, uint3
     st.r[0] = load(lane < h.R ? g[0] : h.lw0);
     static_assert(NB_NR == 2, "two rounds of table lines");
     if (h.R > 64u) st.r[1] = load(lane + 64u < h.R ? g[1] : h.lw0);
-#endif
-#endif
     return st;
 }
 template <class R, class S>
@@ -2227,11 +2115,7 @@ __device__ __forceinline__ void nb_stage_store(const NbHead& h, const NbStaged<R
     const uint32_t lane = threadIdx.x & 63u, wq = (threadIdx.x >> 6) * WAVE_REMOTE;
 #pragma unroll
     for (uint32_t u = 0; u < NB_NW; ++u) {
-#ifdef SPHX_STAGE_SINGLE
-        const uint32_t t = threadIdx.x + u * 256u;
-#else
         const uint32_t t = 2u * threadIdx.x + u;
-#endif
         if (t < h.lwlen) store(t, st.w[u], h.lw0 + t);
     }
 #pragma unroll
@@ -2250,16 +2134,6 @@ __device__ __forceinline__ void nb_stage(NbHead& h, const NbView& nb, uint32_t b
 // part, tools/valu_issue_bench.hip), and a slot no lane of the wavefront has is skipped by the same branch.
 template <class GL, class GG, class C>
 __device__ __forceinline__ void nb_traverse(const NbHead& h, uint32_t lim, GL&& gather_lds, GG&& gather_global, C&& consume) {
-#ifdef SPHX_ABL_NOWALK  // (timing experiments: no walk at all — results are wrong; the compiler also drops the staging the walk would have read)
-    return;
-#endif
-#ifdef SPHX_ABL_ONEENTRY  // (timing experiments: everything is loaded and staged, but only ONE entry is walked — results are wrong)
-    {
-        asm volatile("" ::"v"(h.e[0]), "v"(h.e[1]), "v"(h.e[2]), "v"(h.e[3]));
-        if (lim) consume(gather_lds(entry_off(h.e[0], 0u)), 0u);
-        return;
-    }
-#endif
     if (!h.wide) {
         // the three entries of a 32-bit word are read from the staging area together
         auto triple = [&](uint32_t w3, uint32_t k) {
@@ -2270,14 +2144,6 @@ __device__ __forceinline__ void nb_traverse(const NbHead& h, uint32_t lim, GL&& 
             for (uint32_t u = 0; u < 3; ++u)
                 if (k + u < lim) {
                     consume(r[u], k + u);
-#ifdef SPHX_ABL_HEAVYWALK  // (timing experiments: N more 4-cycle instructions per entry on a register nothing reads — results unchanged)
-                    {
-                        float dummy_ = 1.0f;
-#pragma unroll
-                        for (int z = 0; z < SPHX_ABL_HEAVYWALK; ++z) asm volatile("v_fma_f32 %0, %0, %0, %0" : "+v"(dummy_));
-                        asm volatile("" ::"v"(dummy_));
-                    }
-#endif
                 }
         };
 #pragma unroll
@@ -2312,12 +2178,8 @@ __device__ __forceinline__ void nb_traverse(const NbHead& h, uint32_t lim, GL&& 
 // The LDS staging area of a traversal kernel: NV float2 components (position; velocity) and NS scalars per slot.  A list entry is
 // the byte offset of its slot in a 4-byte array (entry_off), so ONE address register (times 1, 2 or 4) serves all components of a
 // neighbour's record, the component's place being the instruction's immediate offset.
-// SPHX_STAGE_LAYOUT: 0 = every float in an array of its own (x[], y[], ...: ds_read2st64_b32 pairs); 1 = every float2 component in
-// an array of float2 (ds_read_b64 at twice the offset), scalars in float arrays; 2 = the float2 components of a slot together in one
-// record (NV = 2: a float4, ONE ds_read_b128 at four times the offset), scalars in float arrays.
-#ifndef SPHX_STAGE_LAYOUT
-#define SPHX_STAGE_LAYOUT 2
-#endif
+// Layout: the float2 components of a slot together in one record (NV = 2: a float4, ONE ds_read_b128 at four times the offset),
+// scalars in float arrays.
 typedef __attribute__((address_space(3))) const f32x4 lds_cf4;
 template <uint32_t NV, uint32_t NS>
 struct Stage {
@@ -2327,23 +2189,11 @@ struct Stage {
     template <uint32_t C>
     __device__ __forceinline__ void put_vec(uint32_t slot, float2 v) {
         static_assert(C < NV, "component");
-        if (SPHX_STAGE_LAYOUT == 0) {
-            raw[(2u * C) * S + slot] = v.x;
-            raw[(2u * C + 1u) * S + slot] = v.y;
-        } else if (SPHX_STAGE_LAYOUT == 1) {
-            ((float2*)raw)[C * S + slot] = v;
-        } else {
-            ((float2*)raw)[slot * NV + C] = v;
-        }
+        ((float2*)raw)[slot * NV + C] = v;
     }
     __device__ __forceinline__ void put_vec01(uint32_t slot, float4 v) {  // both float2 components of a slot (NV = 2)
         static_assert(NV == 2, "two components");
-        if (SPHX_STAGE_LAYOUT == 2) {
-            ((float4*)raw)[slot] = v;
-        } else {
-            put_vec<0>(slot, make_float2(v.x, v.y));
-            put_vec<1>(slot, make_float2(v.z, v.w));
-        }
+        ((float4*)raw)[slot] = v;
     }
     template <uint32_t C>
     __device__ __forceinline__ void put_scal(uint32_t slot, float v) {
@@ -2354,25 +2204,13 @@ struct Stage {
     template <uint32_t C>
     __device__ __forceinline__ float2 vec(uint32_t o) const {
         static_assert(C < NV, "component");
-        if (SPHX_STAGE_LAYOUT == 0) {
-            return make_float2(__uint_as_float(lds_load_u32(base() + (2u * C) * S * 4u + o)), __uint_as_float(lds_load_u32(base() + (2u * C + 1u) * S * 4u + o)));
-        } else if (SPHX_STAGE_LAYOUT == 1) {
-            const unsigned long long v = *(lds_cu64*)(uintptr_t)(base() + C * S * 8u + (o + o));
-            return make_float2(__uint_as_float((uint32_t)v), __uint_as_float((uint32_t)(v >> 32)));
-        } else {
-            const unsigned long long v = *(lds_cu64*)(uintptr_t)(base() + C * 8u + o * NV * 2u);
-            return make_float2(__uint_as_float((uint32_t)v), __uint_as_float((uint32_t)(v >> 32)));
-        }
+        const unsigned long long v = *(lds_cu64*)(uintptr_t)(base() + C * 8u + o * NV * 2u);
+        return make_float2(__uint_as_float((uint32_t)v), __uint_as_float((uint32_t)(v >> 32)));
     }
     __device__ __forceinline__ float4 vec01(uint32_t o) const {
         static_assert(NV == 2, "two components");
-        if (SPHX_STAGE_LAYOUT == 2) {
-            const f32x4 v = *(lds_cf4*)(uintptr_t)(base() + o * 4u);
-            return make_float4(v.x, v.y, v.z, v.w);
-        } else {
-            const float2 a = vec<0>(o), b = vec<1>(o);
-            return make_float4(a.x, a.y, b.x, b.y);
-        }
+        const f32x4 v = *(lds_cf4*)(uintptr_t)(base() + o * 4u);
+        return make_float4(v.x, v.y, v.z, v.w);
     }
     template <uint32_t C>
     __device__ __forceinline__ float scal(uint32_t o) const {

@@ -538,7 +538,7 @@ int publish_and_wait(sphx_ctx* c) {
     return wait_mailbox(c, seq);
 }
 
-// The density correction of a step may have left the NEXT build's cell count in gdyn.hist / key / slot (CountArgs).  Whoever
+// The density correction of a step may have left the NEXT build's cell count in gdyn.hist / key (CountArgs).  Whoever
 // needs those buffers clean, or changes what the count was made with, calls this first.
 void wipe_histogram(sphx_ctx* c, Grid& g) {
     if (g.hist && g.len()) hipMemsetAsync(g.hist, 0, (size_t)g.len() * 4, c->stream);
@@ -615,18 +615,18 @@ int build_grid(sphx_ctx* c, Grid& g, const float2* pos, uint32_t n, const Gather
     if (counted || partial)
         c->pending.forget();  // consumed: k_scatter counts the histogram back down to zero, as behind any count (the scan leaves it as it is)
     else
-        drop_fused_count(c);  // (the other grid's build too: key / slot are shared)
+        drop_fused_count(c);  // (the other grid's build too: key is shared)
     if (n > first && !counted) {
         const uint32_t gbc = std::max(1u, nblocks(n - first));
         if (advect_dt > 0)
             launch(c, "advect+cell_count", (16.0 + 4 + 4) * n, [&] {
                 hipLaunchKernelGGL(k_key_count<true>, dim3(gbc), dim3(256), 0, st, c->pv(), (const float2*)nullptr, n, advect_dt, c->K,
-                                   g.view(), g.hist, c->key, c->slot, ring ? 1u : 0u, ds, first);
+                                   g.view(), g.hist, c->key, ring ? 1u : 0u, ds, first);
             });
         else
             launch(c, "cell_count", (8.0 + 4 + 4) * (n - first), [&] {
                 hipLaunchKernelGGL(k_key_count<false>, dim3(gbc), dim3(256), 0, st, PVr{nullptr, nullptr}, pos, n, 0.0f, c->K, g.view(),
-                                   g.hist, c->key, c->slot, ring ? 1u : 0u, ds, first);
+                                   g.hist, c->key, ring ? 1u : 0u, ds, first);
             });
     }
     // no table at all (a tile that owns nothing yet): the count of sorted particles is zero — it must not keep the value another
@@ -649,8 +649,8 @@ int build_grid(sphx_ctx* c, Grid& g, const float2* pos, uint32_t n, const Gather
     g.fine_valid = len != 0;
     if (n) {
         launch(c, "cell_scatter", 12.0 * n, [&] {
-            hipLaunchKernelGGL(k_scatter, dim3((nblocks(n, 256 * SCATTER_PER_LANE) + 7u) & ~7u), dim3(256), 0, st, (const uint32_t*)c->key, (const uint32_t*)c->slot, n, (const uint2*)g.fine,
-                               c->order, g.cbits(), g.hist, xcd_scatter_pack(c->K.rev, xcd_shift_of(c)));  // (its blocks hold 1 024 particles)
+            hipLaunchKernelGGL(k_scatter, dim3((nblocks(n, 256 * SCATTER_PER_LANE) + 7u) & ~7u), dim3(256), 0, st, (const uint32_t*)c->key, n, (const uint2*)g.fine,
+                               c->order, g.hist, xcd_scatter_pack(c->K.rev, xcd_shift_of(c)));  // (its blocks hold 1 024 particles)
         });
         const uint32_t ng = n;
         if (tile_n) {
@@ -680,7 +680,7 @@ int build_grid(sphx_ctx* c, Grid& g, const float2* pos, uint32_t n, const Gather
         if (ng)
             launch(c, "gather_attributes", gbytes * ng, [&] {
                 hipLaunchKernelGGL(k_rank_gather, dim3(gb2), dim3(256), 0, st, (const uint32_t*)c->order, (const uint32_t*)c->key, ng, n,
-                                   (const uint2*)g.fine, gm, tile_n ? (const uint32_t*)&ds->sort_total : (const uint32_t*)nullptr, g.cbits(), xcd_pack(c->K.rev, xcd_shift_of(c)));
+                                   (const uint2*)g.fine, gm, tile_n ? (const uint32_t*)&ds->sort_total : (const uint32_t*)nullptr, xcd_pack(c->K.rev, xcd_shift_of(c)));
             });
         if (ng && gm.vmix_tag) c->velmarks.made(gm.vmix_tag);
     }
@@ -693,9 +693,6 @@ int ensure_index_scratch(sphx_ctx* c) {
     if (need <= c->idx_cap) return SPHX_OK;
     int rc;
     if ((rc = dev_alloc(c, &c->key, need))) return rc;
-#ifdef SPHX_SLOT_AT_COUNT  // (round 6: the arrival slot is taken by k_scatter — no side array; the round-5 form for A/B builds)
-    if ((rc = dev_alloc(c, &c->slot, need))) return rc;
-#endif
     if ((rc = dev_alloc(c, &c->order, need))) return rc;
     SPHX_HIP(c, hipMemsetAsync(c->order, 0, (size_t)need * 4, c->stream));
     c->idx_cap = need;
@@ -1265,7 +1262,7 @@ struct IterSpec {
     bool drop_count = false;         // ... once the count an earlier correction left has been dropped
     TileClassArgs tc{};
 };
-inline CountArgs count_args(const sphx_ctx* c, float dt) { return CountArgs{c->gdyn.view(), c->gdyn.hist, c->key, c->slot, dt}; }
+inline CountArgs count_args(const sphx_ctx* c, float dt) { return CountArgs{c->gdyn.view(), c->gdyn.hist, c->key, dt}; }
 
 // One iteration of a solver loop queued on the stream: [warm start, before the first one], compute_density_error /
 // compute_density_change, correct_velocity_* (dfsph.rs:217-218 / :372-373).  The only place that does.  Returns the mailbox sequence
@@ -1674,7 +1671,6 @@ int sphx_create(const sphx_params* params, sphx_ctx** out) {
     }
     sphx_ctx* c = new sphx_ctx();
     if (const char* e = std::getenv("SPHX_SCAN_TWO_PASS")) c->scan_two_pass = e[0] == '1';
-    if (const char* e = std::getenv("SPHX_CBITS_MIN")) c->gdyn.cbits_floor = c->gstat.cbits_floor = (uint32_t)std::max(1, std::atoi(e));
     if (const char* e = std::getenv("SPHX_NO_FUSED_COUNT")) c->no_fused_count = e[0] == '1';
     if (const char* e = std::getenv("SPHX_HOST_LOOP")) c->host_loop = e[0] == '1';
     if (const char* e = std::getenv("SPHX_RUN_AHEAD")) c->run_ahead = e[0] != '0';
@@ -1801,7 +1797,7 @@ void sphx_destroy(sphx_ctx* c) {
     for (auto e : c->ev_pool) hipEventDestroy(e);
     dev_free(&c->posA); dev_free(&c->posA2); dev_free(&c->vel); dev_free(&c->vel2); dev_free(&c->kbuf); dev_free(&c->knz); dev_free(&c->accel);
     dev_free(&c->density); dev_free(&c->alpha); dev_free(&c->alpha2); dev_free(&c->kappa); dev_free(&c->stiff); dev_free(&c->kappa2); dev_free(&c->stiff2);
-    dev_free(&c->pid); dev_free(&c->pid2); dev_free(&c->key); dev_free(&c->slot); dev_free(&c->order);
+    dev_free(&c->pid); dev_free(&c->pid2); dev_free(&c->key); dev_free(&c->order);
     dev_free(&c->bpos); dev_free(&c->bpos2); dev_free(&c->bid); dev_free(&c->bid2); dev_free(&c->nb_list); dev_free(&c->nb_wave); dev_free(&c->nb_counts); dev_free(&c->nb_remote);
     dev_free(&c->scan_partials); dev_free(&c->scan_state); dev_free(&c->d_scal); dev_free(&c->tile_blk); dev_free(&c->sample_buf); dev_free(&c->render_buf); dev_free(&c->edit_buf); dev_free(&c->state_dig); dev_free(&c->mstate_buf);
     dev_free(&c->track.set_buf); dev_free(&c->track.rec); dev_free(&c->track.scratch); dev_free(&c->fields_buf);
@@ -2671,7 +2667,7 @@ int sphx_tile_count_kept(sphx_ctx* c) {
     drop_fused_count(c);
     launch(c, "cell_count", (8.0 + 4 + 4) * n, [&] {
         hipLaunchKernelGGL(k_key_count<false>, dim3(std::max(1u, nblocks(n))), dim3(256), 0, c->stream, PVr{nullptr, nullptr}, (const float2*)c->posA, n, 0.0f,
-                           c->K, c->gdyn.view(), c->gdyn.hist, c->key, c->slot, 1u, c->d_scal, 0u);
+                           c->K, c->gdyn.view(), c->gdyn.hist, c->key, 1u, c->d_scal, 0u);
     });
     c->pending.made_by_pack(n);
     return SPHX_OK;
