@@ -76,7 +76,9 @@ extern "C" {
                             *    _window_fetch, SPHX_SAMPLE_FIELD_*
                             * 5 (additive): sphx_multi_particle_fields, sphx_multi_fields_out, sphx_tile_owned_count,
                             *    sphx_tile_particle_fields_enqueue / _fetch, SPHX_FIELD_*
-                            * 5 (additive): sphx_surface_contour, sphx_contour_chain, sphx_contour_out, SPHX_CONTOUR_* */
+                            * 5 (additive): sphx_surface_contour, sphx_contour_chain, sphx_contour_out, SPHX_CONTOUR_*
+                            * 5 (additive): sphx_multi_surface_contour, sphx_multi_contour_out, sphx_contour_merge,
+                            *    sphx_tile_contour_sample / _border_fetch / _cut / _fetch */
 
 /* ---- status codes ---- */
 enum {
@@ -1087,6 +1089,61 @@ int sphx_tile_sample_points_fetch(sphx_ctx* tile_ctx, uint32_t* records /* host,
 int sphx_tile_sample_window(sphx_ctx* tile_ctx, float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, int kernel_kind, uint32_t fields,
                             uint32_t* out_window /* [4] */);
 int sphx_tile_sample_window_fetch(sphx_ctx* tile_ctx, const sphx_sample_out* out /* host, window-sized */);
+
+/* ---- free surface of a tiled run (csrc/sphx_tiles.cpp; device passes csrc/sphx_contour.inc and csrc/sphx_sample.inc, apron look-up and
+ * merge csrc/sphx_contour_merge.hpp) ---------------------------------------------------------------------------
+ * sphx_surface_contour for a sphx_multi, without sphx_multi_download and a second context and without the lattice crossing to the host.
+ * Lattice values: node (ix, iy) has the value sphx_multi_sample_grid returns for the chosen field at that lattice, kernel and state: the
+ *   tile that owns the node's grid cell answers it over its own arrays, with the one device function.  Consequences (a) to (c) of
+ *   "sampling the fields of a tiled run" carry over.  There is no `values` output: sphx_multi_sample_grid returns those bits.
+ * Who cuts a cell: lattice cell (ix, iy) is cut by the tile whose window (csrc/sphx_sample_window.hpp) holds its node 0 = (ix, iy).  The
+ *   windows partition the lattice, so every cell is cut exactly once.  The other three nodes may be another tile's: a tile samples its
+ *   window into an array padded by one apron column and row, and the tiles swap the first row and first column of their windows (every
+ *   apron node is in one of those) as bit patterns through the host.  A node that no border holds is SPHX_ERR_HIP, never a zero.
+ * Marching squares: the inside test, cases, saddle rule, edge naming, crossing point, segment direction and the order inside a cell are
+ *   those of "free-surface extraction" above, word for word, evaluated with GLOBAL lattice indices: the point is x0 + (float)ix*dx, never
+ *   a shifted origin, and the cell word is iy*(nx-1)+ix.
+ * In-process (sphx_multi_create): *count is the total over all tiles; the output is in ascending global cell index, within a cell as
+ *   above.  In tiling-invariant mode that is byte for byte the output of sphx_surface_contour on a single context in the same mode; in
+ *   every mode it is byte for byte the contract applied to the values of sphx_multi_sample_grid on the same state.  Capacity as in the
+ *   single call: the first cap_segments segments of the global order are written, nothing at or behind the capacity is written.  Each
+ *   tile is asked for min(cap_segments, 2 * its cells) segments, which suffices: a segment among the first cap_segments of the global
+ *   order is among the first cap_segments of its tile.  out->tile[k] is the tile that cut the cell of segment k.
+ * Rank mode (sphx_multi_create_rank): the call returns this rank's part — the count of its tile and its first min(count, cap_segments)
+ *   segments in its own ascending cell order; out->cell is required whenever cap_segments > 0.  The borders cross the ranks in one vector
+ *   of known layout, each rank filling its own entries as (double)(uint32 bit pattern) and zeros elsewhere, summed by the all-reduce of
+ *   sphx_comm_ops eight words at a time (integers below 2^32: exact); the exchange op is not used.  The caller moves the parts and folds
+ *   them with sphx_contour_merge: pure host code, a stable K-way merge by cell word (of equal words the earlier part first, within a part
+ *   the stored order).  stored[p] is how many entries part p holds; *out->count becomes the sum of the parts' counts.  If any part has
+ *   count > stored the merge sets the count, writes no segment and returns SPHX_ERR_CAPACITY — the caller then knows what capacity to
+ *   retry with.  Otherwise it writes the first cap_segments of the merged order; n_parts == 0 gives count 0.  out may alias no part.
+ * When allowed, refusals, side effects: as sphx_multi_sample_grid — the same SPHX_ERR_NOT_READY rules, lattice errors and 64-tile
+ *   limit, the same ghost-band precondition and "exchange now instead of at the next step_begin" behaviour, so the call is COLLECTIVE
+ *   in rank mode; a run with calls between its steps is bit-identical to one without.  Further SPHX_ERR_INVALID_ARGUMENT: iso not
+ *   finite, an unknown field or kernel_kind, any flags bit, out or out->count NULL, rank mode with cap_segments > 0 and out->cell NULL.
+ *   nx < 2, ny < 2 or nx*ny == 0 is a successful call with count 0.  A refused call touches no tile; the argument checks come before
+ *   the band exchange.
+ * One tile (INTERNAL, like the other sphx_tile_* calls; accepted only on a tile context): sphx_tile_contour_sample enqueues the walk over
+ *   the tile's window into the padded array and the border pack, and reports the window {ix0, ix1, iy0, iy1} (all zero: the tile owns no
+ *   node); _border_fetch copies the window's row 0 and column 0 back (w + h words); _cut takes the apron (last column rows [iy0, iy1) if
+ *   ix1 < nx, then last row columns [ix0, ix1) if iy1 < ny, then the corner if both), uploads and unpacks it and enqueues count, carry and
+ *   emit for min(cap_segments, 2 * cells) segments; _fetch copies back the count, then min(count, cap) segments and cell words.  The
+ *   scratch grows on demand on the tile's context and is freed in sphx_destroy; no atomics, the sweep direction is put back. */
+typedef struct sphx_multi_contour_out {   /* host arrays */
+    float*    segments;  /* [cap_segments][4] or NULL */
+    uint32_t* cell;      /* [cap_segments] GLOBAL cell index iy*(nx-1)+ix, or NULL (required in rank mode) */
+    int32_t*  tile;      /* [cap_segments] global rank of the tile that emitted the segment, or NULL */
+    uint32_t* count;     /* [1] required */
+} sphx_multi_contour_out;
+int sphx_multi_surface_contour(sphx_multi* m, float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, int kernel_kind,
+                               int field, float iso, uint32_t cap_segments, uint32_t flags /* 0 */, const sphx_multi_contour_out* out);
+int sphx_contour_merge(const sphx_multi_contour_out* parts, const uint32_t* stored /* [n_parts] */, uint32_t n_parts,
+                       uint32_t cap_segments, const sphx_multi_contour_out* out);
+int sphx_tile_contour_sample(sphx_ctx* tile_ctx, float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, int kernel_kind, int field,
+                             uint32_t* out_window /* [4] */);
+int sphx_tile_contour_border_fetch(sphx_ctx* tile_ctx, uint32_t* border /* host, [cap_words] */, uint32_t cap_words);
+int sphx_tile_contour_cut(sphx_ctx* tile_ctx, float iso, uint32_t cap_segments, const uint32_t* apron /* host, [n_apron] */, uint32_t n_apron);
+int sphx_tile_contour_fetch(sphx_ctx* tile_ctx, float* segments /* host or NULL */, uint32_t* cell /* host or NULL */, uint32_t* out_count);
 
 /* ---- per-particle flow fields of a tiled run (csrc/sphx_fields.inc, csrc/sphx_tiles.cpp) --------------------------------
  * sphx_particle_fields for a sphx_multi: velocity gradient, divergence, vorticity and colour-field gradient at every particle the local

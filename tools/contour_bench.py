@@ -10,7 +10,15 @@ Per particle count: the scene is stepped --warmup times, then for every lattice 
   * yardstick 2, the route without the call: sphx_sample_grid into host memory (wall time, copy included) and marching squares in numpy
     (tests/contour_reference.py, wall time), measured twice;
   * the wall time of the whole host-pointer call (segments copied back) and of sphx_contour_chain on its segments.
-Prints one JSON line per particle count."""
+Prints one JSON line per particle count.
+
+  tools/contour_bench.py --tiles 1,2,4,8 [...]
+
+The tiled call (sphx_multi_surface_contour) instead: per particle count and K the dam break runs as K tiles, all on device 0, and for
+every lattice the tool reports per tile the device time of every pass (tile_sample_window, contour_border_pack, contour_apron_unpack,
+contour_count, contour_carry, contour_emit; medians over --calls calls) and the wall time of the whole call, next to two yardsticks
+measured in the same process on the same state: MultiSolver.sample_grid(fields=("fraction",)) (wall), and that plus contour32 in numpy —
+the route the call replaces.  One JSON line per particle count and K."""
 import argparse
 import ctypes as C
 import json
@@ -100,15 +108,68 @@ def run(n, args):
     print(json.dumps(out), flush=True)
 
 
+TILE_PASSES = ("tile_sample_window", "contour_border_pack", "contour_apron_unpack", "contour_count", "contour_carry", "contour_emit")
+
+
+def run_tiles(n, k, args):
+    scale = float(np.sqrt(n / 4050.0))
+    w = y.FluidParticleWorld()
+    w.reset_fluid(scale)
+    s = y.DFSPHMultiSolver(w, [0] * k)
+    t = y.TimeManager()
+    s.simulation_steps(w, t, args.warmup, sync_world=False)
+    m = s.multi()
+    tiles = [m.tile_context(i) for i in range(k)]
+    out = dict(particles=int(sum(c.n for c in tiles)), tiles=k, scale=scale, warmup=args.warmup, calls=args.calls, lattices=[])
+    for spec in args.lattices.split(","):
+        nx, ny = (int(v) for v in spec.split("x"))
+        x0 = y0 = np.float32(-0.1 * scale)
+        dx, dy = np.float32(2.2 * scale / (nx - 1)), np.float32(1.7 * scale / (ny - 1))
+        count = m.contour((x0, y0), (dx, dy), (ny, nx), cap=0)["count"]
+        cap = count + 16
+        per = [{p: [] for p in TILE_PASSES} for _ in tiles]
+        for c in tiles:
+            c.profile_filter(None)
+            c.profile_enable(True)
+        for _ in range(args.calls):
+            for c in tiles:
+                c.profile_reset()
+            m.contour((x0, y0), (dx, dy), (ny, nx), cap=cap)
+            for i, c in enumerate(tiles):
+                c.synchronize()
+                prof = c.profile_get()
+                for p in TILE_PASSES:
+                    per[i][p].append(prof[p]["total_ms"] * 1e3 if p in prof else 0.0)
+        for c in tiles:
+            c.profile_enable(False)
+        passes = [{p: float(np.median(v)) for p, v in one.items()} for one in per]
+        call_wall, res = wall_us(args.calls, lambda: m.contour((x0, y0), (dx, dy), (ny, nx), cap=cap))
+        count_wall, _ = wall_us(args.calls, lambda: m.contour((x0, y0), (dx, dy), (ny, nx), cap=0))
+        grid_wall, g = wall_us(max(3, args.calls // 3), lambda: m.sample_grid((x0, y0), (dx, dy), (ny, nx), fields=("fraction",))["fraction"])
+        numpy_wall, ref = wall_us(2, lambda: cr.contour32(g, x0, y0, dx, dy, nx, ny, 0.5))
+        assert ref["count"] == count == res["count"] and np.array_equal(ref["segments"].view(np.uint32), res["segments"].view(np.uint32))
+        out["lattices"].append(dict(nx=nx, ny=ny, segments=count, tile_passes_us=passes, tile_device_us=[sum(one.values()) for one in passes],
+                                    call_wall_us=call_wall, count_only_wall_us=count_wall, yardstick_sample_grid_wall_us=grid_wall,
+                                    yardstick_numpy_marching_squares_us=numpy_wall, present_route_us=grid_wall + numpy_wall,
+                                    call_over_sample_grid=call_wall / grid_wall, present_route_over_call=(grid_wall + numpy_wall) / call_wall))
+    s.close()
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--particles", default="16000000,1000000")
     ap.add_argument("--warmup", type=int, default=40)
     ap.add_argument("--calls", type=int, default=15)
     ap.add_argument("--lattices", default="513x385,1025x769,1920x1080")
+    ap.add_argument("--tiles", default=None, help="K1,K2,...: measure sphx_multi_surface_contour on K tiles (all on device 0) instead")
     args = ap.parse_args()
     for n in args.particles.split(","):
-        run(int(n), args)
+        if args.tiles:
+            for k in args.tiles.split(","):
+                run_tiles(int(n), int(k), args)
+        else:
+            run(int(n), args)
 
 
 if __name__ == "__main__":

@@ -15,7 +15,7 @@ from ._lib import (FLAG_DENSITY_ITER_CAP, FLAG_DIVERGENCE_ITER_CAP, FLAG_DENSE_C
                    KERNEL_SPIKY, KERNEL_WENDLAND_C2, VISCOSITY_PHYSICAL, VISCOSITY_XSPH, SphxError, SphxKernelTime, SphxParams, SphxStepStats)
 
 __all__ = ["SphxContext", "FluidParticleWorld", "TimeManager", "DFSPHSolver", "DFSPHMultiSolver", "default_params", "duration_from_secs_f32",
-           "duration_as_secs_f32", "SphxError", "WCSPHSolver", "VISCOSITY_XSPH", "VISCOSITY_PHYSICAL", "SAMPLE_FIELDS", "gauge_elevation", "contour_chain", "contour_lines",
+           "duration_as_secs_f32", "SphxError", "WCSPHSolver", "VISCOSITY_XSPH", "VISCOSITY_PHYSICAL", "SAMPLE_FIELDS", "gauge_elevation", "contour_chain", "contour_lines", "contour_merge",
            "sample_merge", "render_fit", "render_merge", "track_merge", "track_merge_frames", "write_png", "SCENE_RECT", "TRACK_FIELDS", "MULTI_TRACK_FIELDS", "FIELD_NAMES", "STATS_DTYPE", "STATS_FRAME_DTYPE"]
 
 
@@ -356,6 +356,48 @@ def contour_lines(segments):
         idx = order[first[k]:first[k + 1]]
         lines.append(np.concatenate([seg[idx[:1], 0], seg[idx, 1]]))
     return lines, [bool(c) for c in closed]
+
+
+def contour_merge(parts, cap=None):
+    """sphx_contour_merge: the parts the ranks of one run returned from MultiSolver.contour() (dicts with "segments", "cell", "count" and
+    optionally "tile") folded into the contour of the whole run by a stable merge on the cell word -> dict(segments [n, 2, 2], cell [n],
+    count, and tile [n] if every part has one).  cap: the most segments to return (None: all).  A part that holds fewer entries than
+    its count raises SphxError(ERR_CAPACITY); its .count is the total to ask every rank for.  contour_lines() takes the result's
+    segments as they are.  Host code; no GPU."""
+    parts = list(parts)
+    with_tile = bool(parts) and all("tile" in p for p in parts)
+    kept = []
+    arr = (_lib.SphxMultiContourOut * max(len(parts), 1))()
+    stored = np.zeros(max(len(parts), 1), np.uint32)
+    for k, p in enumerate(parts):
+        seg = np.ascontiguousarray(p["segments"], np.float32).reshape(-1, 4)
+        cel = np.ascontiguousarray(p["cell"], np.uint32)
+        cnt = np.array([p["count"]], np.uint32)
+        til = np.ascontiguousarray(p["tile"], np.int32) if with_tile else None
+        if len(cel) != len(seg) or (til is not None and len(til) != len(seg)):
+            raise ValueError("contour_merge: the arrays of a part differ in length")
+        kept.append((seg, cel, cnt, til))
+        stored[k] = len(seg)
+        arr[k].segments, arr[k].cell, arr[k].count = seg.ctypes.data or 1, cel.ctypes.data or 1, cnt.ctypes.data
+        arr[k].tile = (til.ctypes.data or 1) if with_tile else None
+    cap_ = int(sum(int(s) for s in stored[:len(parts)])) if cap is None else int(cap)
+    seg, cel, til = np.zeros((cap_, 2, 2), np.float32), np.zeros(cap_, np.uint32), np.full(cap_, -1, np.int32)
+    cnt = np.zeros(1, np.uint32)
+    o = _lib.SphxMultiContourOut()
+    o.segments, o.cell, o.count = seg.ctypes.data or 1, cel.ctypes.data or 1, cnt.ctypes.data
+    o.tile = (til.ctypes.data or 1) if with_tile else None
+    L = _lib.lib()
+    rc = L.sphx_contour_merge(arr, stored.ctypes.data_as(C.POINTER(C.c_uint32)), len(parts), cap_, C.byref(o))
+    if rc:
+        e = SphxError(rc, L.sphx_multi_last_error(None).decode())
+        e.count = int(cnt[0])
+        raise e
+    count = int(cnt[0])
+    n = min(count, cap_)
+    res = dict(segments=seg[:n], cell=cel[:n], count=count)
+    if with_tile:
+        res["tile"] = til[:n]
+    return res
 
 
 def _elevation(y, f):
@@ -1369,6 +1411,10 @@ class DFSPHMultiSolver(DFSPHSolver):
 
     def sample_grid(self, origin, spacing, shape, kernel=KERNEL_WENDLAND_C2, fields=SAMPLE_FIELDS, tiles=False):
         return self.multi().sample_grid(origin, spacing, shape, kernel, fields, tiles)
+
+    # the free surface of the tiled run (MultiSolver.contour: cut by the tiles, merged on the host in cell order)
+    def contour(self, origin, spacing, shape, iso=0.5, field="fraction", kind=KERNEL_WENDLAND_C2, cap=None, tiles=False):
+        return self.multi().contour(origin, spacing, shape, iso, field, kind, cap, tiles)
 
     # per-particle flow fields of the tiled run (MultiSolver.fields: computed by the tiles over their own arrays, no download)
     def fields(self, fields=FIELD_NAMES, by_id=False):

@@ -104,6 +104,10 @@ class SphxMultiSampleOut(C.Structure):  # sphx_multi_sample_out: host pointers
     _fields_ = [("density", C.c_void_p), ("fraction", C.c_void_p), ("velocity", C.c_void_p), ("count", C.c_void_p), ("tile", C.c_void_p)]
 
 
+class SphxMultiContourOut(C.Structure):  # sphx_multi_contour_out: host pointers
+    _fields_ = [("segments", C.c_void_p), ("cell", C.c_void_p), ("tile", C.c_void_p), ("count", C.c_void_p)]
+
+
 class SphxTileRect(C.Structure):  # sphx_tile_rect: cells, half-open
     _fields_ = [("x0", C.c_uint32), ("x1", C.c_uint32), ("y0", C.c_uint32), ("y1", C.c_uint32)]
 
@@ -322,6 +326,12 @@ SIGNATURES = {
     "sphx_tile_sample_points_fetch": (_i, [_vp, _vp, _u32, C.POINTER(_u32)]),
     "sphx_tile_sample_window": (_i, [_vp, _f, _f, _f, _f, _u32, _u32, _i, _u32, C.POINTER(_u32)]),
     "sphx_tile_sample_window_fetch": (_i, [_vp, C.POINTER(SphxSampleOut)]),
+    "sphx_multi_surface_contour": (_i, [_vp, _f, _f, _f, _f, _u32, _u32, _i, _i, _f, _u32, _u32, C.POINTER(SphxMultiContourOut)]),
+    "sphx_contour_merge": (_i, [C.POINTER(SphxMultiContourOut), C.POINTER(_u32), _u32, _u32, C.POINTER(SphxMultiContourOut)]),
+    "sphx_tile_contour_sample": (_i, [_vp, _f, _f, _f, _f, _u32, _u32, _i, _i, C.POINTER(_u32)]),
+    "sphx_tile_contour_border_fetch": (_i, [_vp, _vp, _u32]),
+    "sphx_tile_contour_cut": (_i, [_vp, _f, _u32, _vp, _u32]),
+    "sphx_tile_contour_fetch": (_i, [_vp, _vp, _vp, C.POINTER(_u32)]),
     "sphx_multi_particle_fields": (_i, [_vp, _u32, C.POINTER(SphxMultiFieldsOut), C.POINTER(C.c_uint64)]),
     "sphx_tile_owned_count": (_i, [_vp, C.POINTER(_u32)]),
     "sphx_tile_particle_fields_enqueue": (_i, [_vp, _u32, _u32]),

@@ -402,6 +402,18 @@ struct sphx_ctx {
     } tsample;
     uint32_t* contour_buf = nullptr;  // sphx_surface_contour: lattice values, workgroup offsets (+ the outputs' device copies on the host-pointer path), grown on demand
     size_t contour_cap = 0;           // ... in 4-byte words
+    // sphx_tile_contour_* (a tile context; contour_buf is its scratch too — sphx_surface_contour refuses a tile): the query in flight
+    // between _sample, _border_fetch, _cut and _fetch.  stage 0: none, 1: sampled (the border can be fetched, the cut is owed),
+    // 2: cut (count and segments can be fetched)
+    struct TileContour {
+        uint32_t stage = 0;
+        uint32_t win[4] = {0, 0, 0, 0};  // lattice window [0], [1]) x [2], [3]) of the tile
+        uint32_t ax = 0, ay = 0;         // apron column / row present (the window does not end at the lattice's last column / row)
+        uint32_t cells = 0, nblocks = 0, cap = 0;
+        float x0 = 0, y0 = 0, dx = 0, dy = 0, iso = 0;
+        uint32_t gcx = 0;                // nx - 1 of the whole lattice
+        size_t at_border = 0, at_apron = 0, at_off = 0, at_cnt = 0, at_seg = 0, at_cell = 0;  // word offsets in contour_buf
+    } tcontour;
     uint32_t* render_buf = nullptr;  // sphx_render: one owner code per pixel (+ the outputs' device copies on the host-pointer path), grown on demand
     size_t render_cap = 0;           // ... in 4-byte words
     float* fields_buf = nullptr;  // sphx_particle_fields: the requested outputs' device copies on the host-pointer path, grown on demand

@@ -201,10 +201,12 @@ __global__ __launch_bounds__(256) void k_tile_sample_indexed(Consts K, SampleArg
 }
 
 // lattice: k_sample_grid over the window [ix0, ix0 + wnx) x [iy0, iy0 + wny) of the lattice L — the index rectangle of the points this
-// tile owns (sphx_sample_window.hpp).  The point is formed from the GLOBAL index; the outputs go to window-sized arrays, row after row.
+// tile owns (sphx_sample_window.hpp).  The point is formed from the GLOBAL index; the outputs go to window-sized arrays, row after row
+// (W.pitch words apart).
 // A lane whose cell is not the tile's writes nothing (the host's window holds no such lane; the buffers are zeroed before the launch).
 struct SampleWindow {
     uint32_t ix0, iy0, wnx, wny, tiles_x;  // tiles_x = ceil(wnx / 16)
+    uint32_t pitch;                        // words per output row: wnx, or wnx + 1 where the contour keeps an apron column behind it
 };
 template <int KIND, bool DEN, bool FRAC, bool VEL>
 __global__ __launch_bounds__(256) void k_tile_sample_window(Consts K, SampleArgs a, SampleLattice L, SampleWindow W, uint32_t base) {
@@ -218,7 +220,7 @@ __global__ __launch_bounds__(256) void k_tile_sample_window(Consts K, SampleArgs
     const float qy = L.y0 + (float)(W.iy0 + jy) * L.dy;
     uint32_t cx, cy;
     cell_of(K, make_float2(qx, qy), cx, cy);
-    sample_point<KIND, DEN, FRAC, VEL>(K, a, qx, qy, inside && rect_has(K.tile, cx, cy, 0u), jy * W.wnx + jx);
+    sample_point<KIND, DEN, FRAC, VEL>(K, a, qx, qy, inside && rect_has(K.tile, cx, cy, 0u), jy * W.pitch + jx);
 }
 
 }  // namespace sphx
@@ -573,7 +575,7 @@ int sphx_tile_sample_window(sphx_ctx* c, float x0, float y0, float dx, float dy,
     hipStream_t st = c->stream;
     SPHX_HIP(c, hipMemsetAsync(c->sample_buf, 0, (n_d + n_f + n_v + n_c) * 4, st));  // (a lane that is not the owner writes nothing)
     const SampleLattice L{x0, y0, dx, dy, nx, ny, (nx + SAMPLE_TILE - 1) / SAMPLE_TILE};
-    const SampleWindow W{w.ix0, w.iy0, w.w(), w.h(), (w.w() + SAMPLE_TILE - 1) / SAMPLE_TILE};
+    const SampleWindow W{w.ix0, w.iy0, w.w(), w.h(), (w.w() + SAMPLE_TILE - 1) / SAMPLE_TILE, w.w()};
     const uint32_t rev = c->K.rev;
     SampleJob q{nullptr, 0, &L, a};
     q.window = &W;

@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "../../include/sphx.h"
+#include "sphx_contour_merge.hpp"
 #include "sphx_multi_edit.hpp"
 #include "sphx_multi_state_format.hpp"
 #include "sphx_render_merge.hpp"
@@ -2673,6 +2674,179 @@ int sphx_multi_sample_grid(sphx_multi* m, float x0, float y0, float dx, float dy
         m->err = std::string(fn) + ": the tiles' windows do not cover the lattice";
         return SPHX_ERR_HIP;
     }
+    return SPHX_OK;
+}
+
+}  // extern "C"
+
+// ---- free surface of a tiled run (include/sphx.h, "free surface of a tiled run"; the device passes are csrc/sphx_contour.inc, the
+// apron look-up and the merge csrc/sphx_contour_merge.hpp) --------------------------------------------------------------------------------
+namespace {
+
+namespace ch = sphx_contour_host;
+
+int contour_tile_failed(sphx_multi* m, size_t k, const char* call, int rc) {
+    m->tiles[k]->err = std::string(call) + ": " + sphx_last_error(m->tiles[k]->ctx);
+    return sample_tile_failed(m, k, rc);
+}
+
+// The borders of all `world` tiles as one vector (ch::border_offsets).  In-process every entry was fetched.  Rank mode: this rank filled
+// its own entries; each word crosses as (double)(bit pattern) with zeros from the other ranks, summed eight at a time — integers below
+// 2^32, so the sum is the word (the trick of stats_gather).
+int contour_share_borders(sphx_multi* m, std::vector<uint32_t>& borders) {
+    if (!m->rank_mode) return SPHX_OK;
+    TileDriver& t = *m->tiles[0];
+    for (size_t at = 0; at < borders.size(); at += 8) {
+        const int n = (int)std::min<size_t>(8, borders.size() - at);
+        double in[8] = {0}, out[8] = {0};
+        for (int k = 0; k < n; ++k) in[k] = (double)borders[at + k];
+        const int rc = t.comm->allreduce(in, n, 0, out);
+        if (rc) {
+            m->err = "sphx_multi_surface_contour: the windows' borders could not be exchanged between the ranks";
+            return t.fail(rc, m->err);
+        }
+        for (int k = 0; k < n; ++k) borders[at + k] = (uint32_t)out[k];
+    }
+    return SPHX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sphx_contour_merge(const sphx_multi_contour_out* parts, const uint32_t* stored, uint32_t n_parts, uint32_t cap_segments,
+                       const sphx_multi_contour_out* out) {
+    auto bad = [](const char* what) {
+        g_multi_error = std::string("sphx_contour_merge: ") + what;  // (no object to hang the message on: sphx_multi_last_error(NULL))
+        return SPHX_ERR_INVALID_ARGUMENT;
+    };
+    if (!out) return bad("out is NULL");
+    if (!out->count) return bad("out->count is NULL");
+    if (n_parts && (!parts || !stored)) return bad("parts or stored is NULL with n_parts > 0");
+    std::vector<ch::MergePart> ps(n_parts);
+    uint64_t total = 0;
+    bool truncated = false;
+    for (uint32_t p = 0; p < n_parts; ++p) {
+        const sphx_multi_contour_out& q = parts[p];
+        if (!q.count) return bad("a part has no count");
+        if (stored[p] > q.count[0]) return bad("a part stores more entries than its count");
+        if (stored[p] && !q.cell) return bad("a part has no cell array (the merge orders by it)");
+        if (stored[p] && ((out->segments && cap_segments && !q.segments) || (out->tile && cap_segments && !q.tile))) return bad("out asks for an array a part lacks");
+        total += q.count[0];
+        truncated = truncated || q.count[0] > stored[p];
+        ps[p] = ch::MergePart{q.segments, q.cell, q.tile, -1, stored[p]};
+    }
+    if (total > 0xffffffffull) return bad("the parts' counts sum to 2^32 or more");
+    out->count[0] = (uint32_t)total;
+    if (truncated) {
+        g_multi_error = "sphx_contour_merge: a part holds fewer entries than its count (call again with a capacity of at least the count)";
+        return SPHX_ERR_CAPACITY;
+    }
+    ch::merge(ps.data(), n_parts, cap_segments, ch::MergeOut{out->segments, out->cell, out->tile});
+    return SPHX_OK;
+}
+
+int sphx_multi_surface_contour(sphx_multi* m, float x0, float y0, float dx, float dy, uint32_t nx, uint32_t ny, int kernel_kind, int field, float iso,
+                               uint32_t cap_segments, uint32_t flags, const sphx_multi_contour_out* out) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    const char* const fn = "sphx_multi_surface_contour";
+    if (!out) return sample_bad(m, fn, "out is NULL");
+    if (!out->count) return sample_bad(m, fn, "out->count is NULL");
+    if (kernel_kind != SPHX_KERNEL_WENDLAND_C2 && kernel_kind != SPHX_KERNEL_POLY6 && kernel_kind != SPHX_KERNEL_SPIKY) return sample_bad(m, fn, "unknown kernel_kind");
+    if (field != SPHX_CONTOUR_FIELD_FRACTION && field != SPHX_CONTOUR_FIELD_DENSITY) return sample_bad(m, fn, "unknown field");
+    if (flags) return sample_bad(m, fn, "unknown flags bits (there is no device-pointer path across several devices)");
+    if (!std::isfinite(iso)) return sample_bad(m, fn, "iso must be finite");
+    if (m->world > 64) return sample_bad(m, fn, "more than 64 tiles");
+    if (m->rank_mode && cap_segments && !out->cell) return sample_bad(m, fn, "out->cell is NULL in rank mode (sphx_contour_merge orders the parts by it)");
+    if (!std::isfinite(x0) || !std::isfinite(y0)) return sample_bad(m, fn, "x0 / y0 must be finite");
+    if (!std::isfinite(dx) || !(dx > 0.0f)) return sample_bad(m, fn, "dx must be finite and > 0");
+    if (!std::isfinite(dy) || !(dy > 0.0f)) return sample_bad(m, fn, "dy must be finite and > 0");
+    if ((uint64_t)nx * ny >= (1ull << 31)) return sample_bad(m, fn, "nx * ny must be < 2^31");
+    if (nx < 2u || ny < 2u) {  // no cell (this covers nx * ny == 0)
+        out->count[0] = 0u;
+        return SPHX_OK;
+    }
+    int rc;
+    if ((rc = multi_state_ready(m, fn, true))) return rc;
+    if ((rc = sample_band(m))) return rc;
+    // every tile's window, on every rank by the same bisection over the layout's rectangles
+    const uint32_t world = (uint32_t)m->world;
+    const TileDriver& t0 = *m->tiles[0];
+    const auto rects = t0.layout.rects();
+    if (rects.size() != world) {
+        m->err = std::string(fn) + ": the layout does not name one rectangle per tile";
+        return SPHX_ERR_HIP;
+    }
+    std::vector<sh::Window> wins(world);
+    for (uint32_t g = 0; g < world; ++g)
+        wins[g] = sh::lattice_window(x0, y0, dx, dy, nx, ny, t0.grid_min[0], t0.grid_min[1], t0.cell_inv, rects[g].x0, rects[g].x1, rects[g].y0, rects[g].y1);
+    if (!ch::windows_cover(wins.data(), world, nx, ny)) {
+        m->err = std::string(fn) + ": the tiles' windows do not cover the lattice";
+        return SPHX_ERR_HIP;
+    }
+    const std::vector<size_t> off = ch::border_offsets(wins.data(), world);
+    const size_t n_local = m->tiles.size();
+    // 1. every local tile samples its padded window and packs its border, on its own stream and device
+    for (size_t k = 0; k < n_local; ++k) {
+        uint32_t win[4];
+        if ((rc = sphx_tile_contour_sample(m->tiles[k]->ctx, x0, y0, dx, dy, nx, ny, kernel_kind, field, win)))
+            return contour_tile_failed(m, k, "sphx_tile_contour_sample", rc);
+        const sh::Window& w = wins[track_tile_rank(m, k)];
+        if (win[0] != w.ix0 || win[1] != w.ix1 || win[2] != w.iy0 || win[3] != w.iy1) {
+            m->err = std::string(fn) + ": tile " + std::to_string(k) + " reports another window than its rectangle gives";
+            return SPHX_ERR_HIP;
+        }
+    }
+    // 2. the borders come back (one small copy and one wait per tile) and cross the ranks
+    std::vector<uint32_t> borders(off[world], 0u);
+    for (size_t k = 0; k < n_local; ++k) {
+        const uint32_t g = track_tile_rank(m, k);
+        if ((rc = sphx_tile_contour_border_fetch(m->tiles[k]->ctx, borders.data() + off[g], (uint32_t)(off[g + 1] - off[g]))))
+            return contour_tile_failed(m, k, "sphx_tile_contour_border_fetch", rc);
+    }
+    if ((rc = contour_share_borders(m, borders))) return rc;
+    // 3. every local tile gets its apron by node look-up and enqueues the cut (the aprons live until the parts are fetched)
+    std::vector<std::vector<uint32_t>> aprons(n_local);
+    std::vector<uint32_t> caps(n_local, 0u);
+    std::vector<size_t> idx;
+    for (size_t k = 0; k < n_local; ++k) {
+        const uint32_t g = track_tile_rank(m, k);
+        uint32_t bad_ix = 0, bad_iy = 0;
+        if (ch::apron_indices(wins.data(), off.data(), world, nx, ny, g, idx, &bad_ix, &bad_iy)) {
+            m->err = std::string(fn) + ": apron node (" + std::to_string(bad_ix) + ", " + std::to_string(bad_iy) + ") of tile " + std::to_string(g) +
+                     " is not in exactly one window's first row or column";
+            return SPHX_ERR_HIP;
+        }
+        aprons[k].resize(idx.size());
+        for (size_t i = 0; i < idx.size(); ++i) aprons[k][i] = borders[idx[i]];
+        caps[k] = (uint32_t)std::min<uint64_t>(cap_segments, 2ull * ch::window_cells(wins[g], nx, ny));
+        if ((rc = sphx_tile_contour_cut(m->tiles[k]->ctx, iso, caps[k], aprons[k].data(), (uint32_t)aprons[k].size())))
+            return contour_tile_failed(m, k, "sphx_tile_contour_cut", rc);
+    }
+    // 4. the parts: rank mode writes this rank's straight into out; in-process they are merged by cell word
+    if (m->rank_mode) {
+        uint32_t count = 0;
+        if ((rc = sphx_tile_contour_fetch(m->tiles[0]->ctx, out->segments, out->cell, &count))) return contour_tile_failed(m, 0, "sphx_tile_contour_fetch", rc);
+        out->count[0] = count;
+        const uint32_t got = std::min(count, caps[0]);
+        if (out->tile) std::fill(out->tile, out->tile + got, (int32_t)track_tile_rank(m, 0));
+        return SPHX_OK;
+    }
+    std::vector<std::vector<uint32_t>> cells(n_local);
+    std::vector<std::vector<float>> segs(n_local);
+    std::vector<ch::MergePart> parts(n_local);
+    uint64_t total = 0;
+    for (size_t k = 0; k < n_local; ++k) {
+        cells[k].resize(caps[k]);
+        if (out->segments) segs[k].resize(4 * (size_t)caps[k]);
+        uint32_t count = 0;
+        if ((rc = sphx_tile_contour_fetch(m->tiles[k]->ctx, out->segments && caps[k] ? segs[k].data() : nullptr, caps[k] ? cells[k].data() : nullptr, &count)))
+            return contour_tile_failed(m, k, "sphx_tile_contour_fetch", rc);
+        total += count;
+        parts[k] = ch::MergePart{out->segments ? segs[k].data() : nullptr, cells[k].data(), nullptr, (int32_t)k, std::min(count, caps[k])};
+    }
+    out->count[0] = (uint32_t)total;  // (2 * cells < 2^32)
+    ch::merge(parts.data(), (uint32_t)n_local, cap_segments, ch::MergeOut{out->segments, out->cell, out->tile});
     return SPHX_OK;
 }
 

@@ -376,6 +376,46 @@ class MultiSolver:
         self._chk(self.L.sphx_multi_sample_grid(self.h, origin[0], origin[1], dx, dy, nx, ny, kernel, 0, C.byref(o)))
         return outs
 
+    # ---- the free surface of the tiled run (the contract is in include/sphx.h, "free surface of a tiled run") ----
+    def contour(self, origin, spacing, shape, iso=0.5, field="fraction", kind=_lib.KERNEL_WENDLAND_C2, cap=None, tiles=False):
+        """sphx_multi_surface_contour: the contour `field == iso` of the lattice sample_grid(origin, spacing, shape) returns, cut by the
+        tiles on their devices — no download, and the lattice does not cross to the host.  Arguments and result as
+        SphxContext.contour (host path): dict(segments [n, 2, 2], cell [n], count), in ascending cell order; tiles=True adds "tile":
+        int32 [n], the tile that cut the segment's cell.  cap=None makes two calls, the count first and then the exact capacity, so
+        n = count; cap = 0 returns the count alone.  If the ghost band is spent, the halo exchange the next step owes happens now
+        (collective in rank mode).  Rank mode: this rank's part ("tile" is always returned; n = min(count of this rank, cap)); fold the
+        ranks' parts with yasph2d_amd.contour_merge."""
+        if field not in _lib.CONTOUR_FIELDS:
+            raise ValueError("field must be one of %s, not %r" % (sorted(_lib.CONTOUR_FIELDS), field))
+        dx, dy = (spacing, spacing) if np.ndim(spacing) == 0 else spacing
+        ny, nx = (int(v) for v in shape)
+        if nx < 0 or ny < 0:
+            raise ValueError("shape must be (ny, nx) with non-negative sizes")
+        want_tile = tiles or self.info()["local_tiles"] < self.info()["world"]
+        cnt = np.zeros(1, np.uint32)
+
+        def call(cap_):
+            seg, cel, til = np.zeros((cap_, 2, 2), np.float32), np.zeros(cap_, np.uint32), np.full(cap_, -1, np.int32)
+            o = _lib.SphxMultiContourOut()
+            o.count = cnt.ctypes.data
+            if cap_:
+                o.segments, o.cell = seg.ctypes.data, cel.ctypes.data
+                o.tile = til.ctypes.data if want_tile else None
+            self._chk(self.L.sphx_multi_surface_contour(self.h, origin[0], origin[1], dx, dy, nx, ny, kind, _lib.CONTOUR_FIELDS[field], iso, cap_, 0, C.byref(o)))
+            return seg, cel, til
+
+        if cap is None:
+            call(0)
+            cap = int(cnt[0])
+        cap = int(cap)
+        seg, cel, til = call(cap)
+        count = int(cnt[0])
+        n = min(count, cap)
+        res = dict(segments=seg[:n], cell=cel[:n], count=count)
+        if want_tile:
+            res["tile"] = til[:n]
+        return res
+
     # ---- per-particle flow fields of the tiled run (the contract is in include/sphx.h, "per-particle flow fields of a tiled run") ----
     def fields(self, fields=None, by_id=False):
         """sphx_multi_particle_fields: velocity gradient, divergence, vorticity and colour-field gradient (SphxContext.fields) at every
