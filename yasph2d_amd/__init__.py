@@ -976,6 +976,170 @@ class SphxContext:
             res["values"] = val
         return res
 
+    def query(self, points, radius=None, boundary=False, lists=True, nearest=True, cap=None, out=None):
+        """sphx_query_radius: the particles within `radius` of m query points, by the box rule of include/sphx.h ("neighbour queries").
+
+        points: float32 [m, 2], a numpy array (host path) or a torch tensor on the context's device (device path).  radius: None = the
+        smoothing length h (the largest allowed).  boundary=True answers over the boundary particles (the order of
+        download_boundary()) instead of the fluid (the order of download()).
+        Returns dict(offsets uint64 [m + 1] (CSR), count = the total number of entries; with lists: index, id uint32 [n] and dist_sq
+        float32 [n]; with nearest: nearest uint32 [m] (QUERY_NONE where nothing is accepted) and nearest_dist_sq float32 [m] (+inf
+        there)).  cap: the most entries to return (n = min(count, cap)); None makes a count-only call first and sizes the arrays
+        exactly, so n = count.
+        Device path: the results are torch tensors (int64 offsets, int32 index / id / nearest — torch has no unsigned arithmetic).
+        out = dict of contiguous tensors on the context's device to write in place: "offsets" int64 [m + 1], "index" / "id" int32
+        [cap], "dist_sq" float32 [cap], "nearest" int32 [m], "nearest_dist_sq" float32 [m], "count" int64 [1]; what is missing is
+        allocated according to lists / nearest / cap ("count" always).  Nothing behind min(count, cap) is touched; the dict
+        returned holds views of the first n entries and count as an int.  Like sample(), this path synchronises torch's current
+        stream before the call and the context's stream after it."""
+        if radius is None and self.params is None:
+            raise ValueError("radius=None needs the params the context was created with (a borrowed view has none): pass the radius")
+        r = float(np.float32(self.params.smoothing_length if radius is None else radius))
+        base = _lib.QUERY_BOUNDARY if boundary else 0
+        o = _lib.SphxQueryOut()
+        if _is_torch(points) or out is not None:
+            import torch
+
+            if not _is_torch(points) or points.device.type != "cuda" or points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 2:
+                raise ValueError("points must be a float32 [m, 2] tensor on the context's device")
+            pts = points.contiguous()
+            m = pts.shape[0]
+            dev = pts.device
+            given = dict(out or {})
+            want = dict(offsets=(torch.int64, m + 1), index=(torch.int32, None), id=(torch.int32, None), dist_sq=(torch.float32, None),
+                        nearest=(torch.int32, m), nearest_dist_sq=(torch.float32, m), count=(torch.int64, 1))
+            for k, t in given.items():
+                if k not in want:
+                    raise ValueError("out has no field %r" % (k,))
+                if not _is_torch(t) or t.device.type != "cuda" or not t.is_contiguous() or t.dtype != want[k][0] or t.dim() != 1:
+                    raise ValueError("out[%r] must be a contiguous 1-d %s tensor on the context's device" % (k, want[k][0]))
+                if want[k][1] is not None and t.numel() != want[k][1]:
+                    raise ValueError("out[%r] must hold %d elements" % (k, want[k][1]))
+            t_cnt = given.get("count")
+            if t_cnt is None:
+                t_cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+            t_off = given.get("offsets")
+            if t_off is None:
+                t_off = torch.empty(m + 1, dtype=torch.int64, device=dev)
+            t_near, t_nd2 = given.get("nearest"), given.get("nearest_dist_sq")
+            if nearest and out is None:
+                t_near = torch.empty(m, dtype=torch.int32, device=dev)
+                t_nd2 = torch.empty(m, dtype=torch.float32, device=dev)
+            ent = {k: given.get(k) for k in ("index", "id", "dist_sq")}
+            have = [t.numel() for t in ent.values() if t is not None]
+            if len(set(have)) > 1:
+                raise ValueError("out[\"index\"], out[\"id\"] and out[\"dist_sq\"] must be equally long")
+
+            def call(cap_, with_lists):
+                o.offsets, o.count = t_off.data_ptr(), t_cnt.data_ptr()
+                o.nearest = (t_near.data_ptr() or 1) if t_near is not None else None
+                o.nearest_dist_sq = (t_nd2.data_ptr() or 1) if t_nd2 is not None else None
+                for k, t in ent.items():
+                    setattr(o, k, (t.data_ptr() or 1) if with_lists and t is not None and cap_ else None)
+                torch.cuda.current_stream(dev).synchronize()
+                self._chk(self.L.sphx_query_radius(self.h, C.c_void_p(pts.data_ptr()), m, r, cap_, base | _lib.QUERY_DEVICE_POINTERS, C.byref(o)))
+                self.synchronize()
+                return int(t_cnt.item())
+
+            if have:
+                cap_ = have[0] if cap is None else min(int(cap), have[0])
+                count = call(cap_, True)
+            elif lists and out is None:
+                cap_ = call(0, False) if cap is None else int(cap)
+                ent = dict(index=torch.empty(cap_, dtype=torch.int32, device=dev), id=torch.empty(cap_, dtype=torch.int32, device=dev),
+                           dist_sq=torch.empty(cap_, dtype=torch.float32, device=dev))
+                count = call(cap_, True) if cap_ else (call(0, False) if cap is not None else cap_)
+            else:
+                cap_, count = 0, call(0, False)
+            n = min(count, cap_)
+            res = dict(offsets=t_off, count=count)
+            res.update({k: t[:n] for k, t in ent.items() if t is not None})
+            if t_near is not None:
+                res["nearest"] = t_near
+            if t_nd2 is not None:
+                res["nearest_dist_sq"] = t_nd2
+            return res
+        pts = np.ascontiguousarray(points, np.float32)
+        if pts.ndim != 2 or pts.shape[1] != 2:
+            raise ValueError("points must be a float32 [m, 2] array, not shape %s" % (pts.shape,))
+        m = len(pts)
+        cnt = np.zeros(1, np.uint64)
+        off = np.zeros(m + 1, np.uint64)
+        near = np.full(m, _lib.QUERY_NONE, np.uint32) if nearest else None
+        nd2 = np.full(m, np.inf, np.float32) if nearest else None
+        o.offsets, o.count = off.ctypes.data, cnt.ctypes.data
+        o.nearest, o.nearest_dist_sq = ((near.ctypes.data or 1), (nd2.ctypes.data or 1)) if nearest else (None, None)
+        res = dict(offsets=off)
+        if nearest:
+            res.update(nearest=near, nearest_dist_sq=nd2)
+        cap_ = int(cap) if cap is not None else 0
+        if cap is None or not lists:
+            self._chk(self.L.sphx_query_radius(self.h, _p(pts), m, r, 0, base, C.byref(o)))  # count only: one walk
+            cap_ = int(cnt[0]) if cap is None else cap_
+        if lists:
+            idx, ids, d2 = np.zeros(cap_, np.uint32), np.zeros(cap_, np.uint32), np.zeros(cap_, np.float32)
+            if cap is not None or cap_:
+                o.index, o.id, o.dist_sq = ((idx.ctypes.data, ids.ctypes.data, d2.ctypes.data) if cap_ else (None, None, None))
+                self._chk(self.L.sphx_query_radius(self.h, _p(pts), m, r, cap_, base, C.byref(o)))
+            n = min(int(cnt[0]), cap_)
+            res.update(index=idx[:n], id=ids[:n], dist_sq=d2[:n])
+        res["count"] = int(cnt[0])
+        return res
+
+    def select(self, rects, outside=False, cap=None, out=None):
+        """sphx_select: the particles sphx_remove(rects, outside) would remove, in ascending device index — and nothing is removed.
+
+        rects: as remove().  Returns dict(index uint32 [n] (the order of download()), id uint32 [n] (particle_id), count = the number
+        selected).  cap: the most to return (n = min(count, cap)); None makes a count-only call first, so n = count.
+        Device path: out = dict of contiguous int32 torch tensors on the context's device, "index" and / or "id" [cap] and optionally
+        "count" [1]; they are written in place (nothing behind min(count, cap) is touched) and views of the first n come back."""
+        arr, k = _rect_array(rects)
+        base = _lib.SELECT_OUTSIDE if outside else 0
+        o = _lib.SphxSelectOut()
+        if out is not None:
+            import torch
+
+            idx, ids, t_cnt = out.get("index"), out.get("id"), out.get("count")
+            some = next((t for t in (idx, ids, t_cnt) if t is not None), None)
+            if some is None or any(t is not None and (not _is_torch(t) or t.device.type != "cuda" or not t.is_contiguous() or t.dtype != torch.int32
+                                                      or t.dim() != 1) for t in (idx, ids, t_cnt)):
+                raise ValueError("out must hold contiguous 1-d int32 torch tensors on the context's device")
+            if idx is not None and ids is not None and idx.numel() != ids.numel():
+                raise ValueError("out[\"index\"] and out[\"id\"] must be equally long")
+            if t_cnt is None:
+                t_cnt = torch.zeros(1, dtype=torch.int32, device=some.device)
+            elif t_cnt.numel() != 1:
+                raise ValueError("out[\"count\"] must be an int32 [1] tensor")
+            have = idx.numel() if idx is not None else (ids.numel() if ids is not None else 0)
+            cap_ = have if cap is None else min(int(cap), have)
+            o.index = (idx.data_ptr() or 1) if idx is not None and cap_ else None
+            o.id = (ids.data_ptr() or 1) if ids is not None and cap_ else None
+            o.count = t_cnt.data_ptr()
+            torch.cuda.current_stream(some.device).synchronize()
+            self._chk(self.L.sphx_select(self.h, arr, k, base | _lib.SELECT_DEVICE_POINTERS, cap_, C.byref(o)))
+            self.synchronize()
+            count = int(t_cnt.item())
+            n = min(count, cap_)
+            res = dict(count=count)
+            if idx is not None:
+                res["index"] = idx[:n]
+            if ids is not None:
+                res["id"] = ids[:n]
+            return res
+        cnt = np.zeros(1, np.uint32)
+        o.count = cnt.ctypes.data
+        if cap is None:
+            self._chk(self.L.sphx_select(self.h, arr, k, base, 0, C.byref(o)))
+            cap_ = int(cnt[0])
+        else:
+            cap_ = int(cap)
+        idx, ids = np.zeros(cap_, np.uint32), np.zeros(cap_, np.uint32)
+        if cap is not None or cap_:
+            o.index, o.id = (idx.ctypes.data, ids.ctypes.data) if cap_ else (None, None)
+            self._chk(self.L.sphx_select(self.h, arr, k, base, cap_, C.byref(o)))
+        n = min(int(cnt[0]), cap_)
+        return dict(index=idx[:n], id=ids[:n], count=int(cnt[0]))
+
     def render(self, view=None, *, out=None, owner=False, rgba=True, **view_fields):
         """sphx_render: the particles drawn as discs (the contract is in include/sphx.h).
 

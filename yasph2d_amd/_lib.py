@@ -138,6 +138,21 @@ class SphxRect(C.Structure):
     _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("x1", C.c_float), ("y1", C.c_float)]
 
 
+QUERY_DEVICE_POINTERS, QUERY_BOUNDARY = 1, 2  # sphx_query_radius flags
+QUERY_NONE = 0xFFFFFFFF       # nearest of a point that accepts nothing
+QUERY_NONE_WORD = 0x7F800000  # ... and its nearest_dist_sq (+inf)
+SELECT_OUTSIDE, SELECT_DEVICE_POINTERS = 1, 2  # sphx_select flags
+
+
+class SphxQueryOut(C.Structure):  # 56 bytes
+    _fields_ = [("offsets", C.c_void_p), ("index", C.c_void_p), ("id", C.c_void_p), ("dist_sq", C.c_void_p), ("nearest", C.c_void_p),
+                ("nearest_dist_sq", C.c_void_p), ("count", C.c_void_p)]
+
+
+class SphxSelectOut(C.Structure):  # 24 bytes
+    _fields_ = [("index", C.c_void_p), ("id", C.c_void_p), ("count", C.c_void_p)]
+
+
 STATE_DEVICE_BUFFER = 1  # sphx_state_save / sphx_state_load flags
 STATE_SECTIONS = ("positions", "velocities", "particle_id", "density", "alpha", "kappa", "stiffness", "accel", "boundary")  # SPHX_STATE_SEC_*
 MULTI_STATE_SECTIONS = ("positions", "velocities", "particle_id", "density", "alpha", "kappa", "stiffness", "boundary")  # SPHX_MULTI_STATE_SEC_*
@@ -246,6 +261,8 @@ SIGNATURES = {
     "sphx_upload": (_i, [_vp, _vp, _vp, _u32]),
     "sphx_append": (_i, [_vp, _vp, _vp, _u32, C.POINTER(_u32)]),
     "sphx_remove": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32, C.POINTER(_u32)]),
+    "sphx_query_radius": (_i, [_vp, _vp, _u32, _f, _u64, _u32, C.POINTER(SphxQueryOut)]),
+    "sphx_select": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32, _u32, C.POINTER(SphxSelectOut)]),
     "sphx_state_size": (_i, [_vp, C.POINTER(_u64)]),
     "sphx_state_save": (_i, [_vp, _vp, _u64, _u32, C.POINTER(_u64)]),
     "sphx_state_load": (_i, [_vp, _vp, _u64, _u32]),

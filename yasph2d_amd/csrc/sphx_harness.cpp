@@ -8,7 +8,14 @@
 //                [--load-state FILE] [--save-state FILE[:at=STEP]] [--track ID[,ID...] [--track-every E] --track-out FILE] [--fields-out FILE]
 //                [--stats-out FILE [--stats-every K]]
 //                [--contour-out FILE [--contour-grid x0,y0,dx,dy,nx,ny] [--contour-iso V]]
+//                [--query-out FILE --query-points x,y[;x,y...] [--query-radius R]] [--select-out FILE --select x0,y0,x1,y1]
 //                [--help]
+//
+// --query-out: after the last step, the fluid particles within R (default: the smoothing length, the largest allowed) of each of the
+// --query-points in the final state (sphx_query_radius) as the CSV "point,slot,id,dist_sq": one line per entry, point after point in the
+// order given, within a point in ascending slot (%.9g, which round-trips fp32).  The JSON line gains "query_entries".
+// --select-out: after the last step, the fluid particles of the final state inside the --select rectangle (sphx_select; bounds may be
+// inf / -inf) as the CSV "slot,id" in ascending slot.  The JSON line gains "selected".
 //
 // --contour-out: after the last step, the free surface of the final state (sphx_surface_contour of the fluid fraction, Wendland kernel, at
 // V = 0.5 unless --contour-iso says otherwise; stitched by sphx_contour_chain) as the CSV "line,closed,x,y": the points of line 0, then of
@@ -123,6 +130,7 @@ static const char* const USAGE =
     "             [--load-state FILE] [--save-state FILE[:at=STEP]] [--track ID[,ID...] [--track-every E] --track-out FILE] [--fields-out FILE]\n"
     "             [--stats-out FILE [--stats-every K]]\n"
     "             [--contour-out FILE [--contour-grid x0,y0,dx,dy,nx,ny] [--contour-iso V]]\n"
+    "             [--query-out FILE --query-points x,y[;x,y...] [--query-radius R]] [--select-out FILE --select x0,y0,x1,y1]\n"
     "             [--help]\n"
     "  --load-state FILE            start from a solver state file (sphx_solver_load) instead of the scene\n"
     "  --save-state FILE[:at=STEP]  write a solver state file (sphx_solver_save) after STEP steps of this run; default: after the last step\n"
@@ -135,6 +143,11 @@ static const char* const USAGE =
     "  --contour-out FILE           write the final state's free surface (sphx_surface_contour + sphx_contour_chain) as CSV: line,closed,x,y\n"
     "  --contour-grid x0,y0,dx,dy,nx,ny  ... on this lattice (default: 513 x 385 nodes over the camera rectangle of the scene)\n"
     "  --contour-iso V              ... at fraction V (default 0.5)\n"
+    "  --query-out FILE             write the final state's fluid particles around the query points (sphx_query_radius) as CSV: point,slot,id,dist_sq\n"
+    "  --query-points x,y[;x,y...]  ... the points\n"
+    "  --query-radius R             ... within R (default and largest: the smoothing length)\n"
+    "  --select-out FILE            write the final state's fluid particles inside a rectangle (sphx_select) as CSV: slot,id\n"
+    "  --select x0,y0,x1,y1         ... the rectangle (inf allowed)\n"
     "Prints one JSON line with the throughput, the timer's final step and a checksum of the final state.\n";
 
 static bool parse_list(const std::string& s, size_t count, bool allow_inf, double* out) {
@@ -175,6 +188,8 @@ int main(int argc, char** argv) {
     bool want_fields = false;
     std::string contour_out, contour_grid_arg, contour_iso_arg;
     bool want_contour = false, want_contour_grid = false, want_contour_iso = false;
+    std::string query_out, query_points_arg, query_radius_arg, select_out, select_arg;
+    bool want_query = false, want_query_points = false, want_query_radius = false, want_select_out = false, want_select = false;
     auto add_rect = [&](std::vector<sphx_rect>& to, const char* opt, const std::string& arg) {
         double v[4];
         if (!parse_list(arg, 4, true, v) || drain_rects.size() + keep_rects.size() >= SPHX_REMOVE_MAX_RECTS) {
@@ -215,6 +230,11 @@ int main(int argc, char** argv) {
         else if (s == "--contour-out") contour_out = a + 1 < argc ? argv[++a] : "", want_contour = true;
         else if (s == "--contour-grid") contour_grid_arg = next(), want_contour_grid = true;
         else if (s == "--contour-iso") contour_iso_arg = next(), want_contour_iso = true;
+        else if (s == "--query-out") query_out = a + 1 < argc ? argv[++a] : "", want_query = true;
+        else if (s == "--query-points") query_points_arg = a + 1 < argc ? argv[++a] : "", want_query_points = true;
+        else if (s == "--query-radius") query_radius_arg = next(), want_query_radius = true;
+        else if (s == "--select-out") select_out = a + 1 < argc ? argv[++a] : "", want_select_out = true;
+        else if (s == "--select") select_arg = a + 1 < argc ? argv[++a] : "", want_select = true;
         else if (s == "--help" || s == "-h") {
             std::fputs(USAGE, stdout);
             return 0;
@@ -259,6 +279,34 @@ int main(int argc, char** argv) {
                                  "nx * ny < 2^31] [--contour-iso V: finite])\n");
             return 2;
         }
+    }
+    std::vector<float> query_xy;
+    double query_radius = 0.0;  // (0: the smoothing length)
+    if (want_query || want_query_points || want_query_radius) {
+        bool ok = want_query && !query_out.empty() && want_query_points && !query_points_arg.empty();
+        for (size_t p = 0; ok && p <= query_points_arg.size();) {
+            const size_t q = std::min(query_points_arg.find(';', p), query_points_arg.size());
+            double v[2] = {0.0, 0.0};
+            ok = parse_list(query_points_arg.substr(p, q - p), 2, false, v);
+            query_xy.push_back((float)v[0]);
+            query_xy.push_back((float)v[1]);
+            p = q + 1;
+        }
+        if (ok && want_query_radius) ok = parse_double(query_radius_arg, &query_radius) && query_radius > 0.0;
+        if (!ok) {
+            std::fprintf(stderr, "invalid --query options (--query-out FILE --query-points x,y[;x,y...]: finite [--query-radius R: finite, > 0])\n");
+            return 2;
+        }
+    }
+    sphx_rect select_rect{0.0f, 0.0f, 0.0f, 0.0f};
+    if (want_select_out || want_select) {
+        double v[4] = {0.0, 0.0, 0.0, 0.0};
+        const bool ok = want_select_out && !select_out.empty() && want_select && parse_list(select_arg, 4, true, v);
+        if (!ok) {
+            std::fprintf(stderr, "invalid --select options (--select-out FILE --select x0,y0,x1,y1; inf allowed)\n");
+            return 2;
+        }
+        select_rect = sphx_rect{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
     }
     uint32_t stats_every = 1;
     if (want_stats || want_stats_every) {
@@ -687,6 +735,65 @@ int main(int argc, char** argv) {
         }
         char buf[96];
         std::snprintf(buf, sizeof(buf), ", \"contour_segments\": %u, \"contour_lines\": %u", total, lines);
+        gauge_json += buf;
+    }
+    if (want_query) {
+        const uint32_t qm = (uint32_t)(query_xy.size() / 2);
+        const float qr = want_query_radius ? (float)query_radius : params.smoothing_length;
+        uint64_t total = 0;
+        std::vector<uint64_t> off((size_t)qm + 1);
+        sphx_query_out qo{};
+        qo.offsets = off.data();
+        qo.count = &total;
+        int rc = sphx_query_radius(solver->ctx(), query_xy.data(), qm, qr, 0u, 0u, &qo);
+        std::vector<uint32_t> slot((size_t)total), id((size_t)total);
+        std::vector<float> d2((size_t)total);
+        if (rc == SPHX_OK && total) {
+            qo.index = slot.data(), qo.id = id.data(), qo.dist_sq = d2.data();
+            rc = sphx_query_radius(solver->ctx(), query_xy.data(), qm, qr, total, 0u, &qo);
+        }
+        if (rc != SPHX_OK) {
+            std::fprintf(stderr, "--query-out: %s (status %d)\n", sphx_last_error(solver->ctx()), rc);
+            return 1;
+        }
+        FILE* f = std::fopen(query_out.c_str(), "w");
+        bool ok = f != nullptr && std::fputs("point,slot,id,dist_sq\n", f) >= 0;
+        for (uint32_t k = 0; ok && k < qm; ++k)
+            for (uint64_t e = off[k]; ok && e < off[k + 1] && e < slot.size(); ++e)
+                ok = std::fprintf(f, "%u,%u,%u,%.9g\n", k, slot[e], id[e], (double)d2[e]) > 0;
+        if (f) ok = std::fclose(f) == 0 && ok;
+        if (!ok) {
+            std::fprintf(stderr, "cannot write %s\n", query_out.c_str());
+            return 1;
+        }
+        char buf[64];
+        std::snprintf(buf, sizeof(buf), ", \"query_entries\": %llu", (unsigned long long)total);
+        gauge_json += buf;
+    }
+    if (want_select_out) {
+        uint32_t total = 0;
+        sphx_select_out so{};
+        so.count = &total;
+        int rc = sphx_select(solver->ctx(), &select_rect, 1u, 0u, 0u, &so);
+        std::vector<uint32_t> slot(total), id(total);
+        if (rc == SPHX_OK && total) {
+            so.index = slot.data(), so.id = id.data();
+            rc = sphx_select(solver->ctx(), &select_rect, 1u, 0u, total, &so);
+        }
+        if (rc != SPHX_OK) {
+            std::fprintf(stderr, "--select-out: %s (status %d)\n", sphx_last_error(solver->ctx()), rc);
+            return 1;
+        }
+        FILE* f = std::fopen(select_out.c_str(), "w");
+        bool ok = f != nullptr && std::fputs("slot,id\n", f) >= 0;
+        for (size_t e = 0; ok && e < slot.size(); ++e) ok = std::fprintf(f, "%u,%u\n", slot[e], id[e]) > 0;
+        if (f) ok = std::fclose(f) == 0 && ok;
+        if (!ok) {
+            std::fprintf(stderr, "cannot write %s\n", select_out.c_str());
+            return 1;
+        }
+        char buf[64];
+        std::snprintf(buf, sizeof(buf), ", \"selected\": %u", total);
         gauge_json += buf;
     }
     if (want_edit) {

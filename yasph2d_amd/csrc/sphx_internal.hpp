@@ -402,6 +402,12 @@ struct sphx_ctx {
     } tsample;
     uint32_t* contour_buf = nullptr;  // sphx_surface_contour: lattice values, workgroup offsets (+ the outputs' device copies on the host-pointer path), grown on demand
     size_t contour_cap = 0;           // ... in 4-byte words
+    // sphx_query_radius / sphx_select (sphx_query.inc): workgroup offsets, prefixes and the host-pointer path's points / per-point outputs;
+    // and the entries' device copies of the host-pointer paths, sized once the total is known.  Both grown on demand.
+    uint32_t* query_buf = nullptr;
+    size_t query_cap = 0;             // ... in 4-byte words
+    uint32_t* query_ent = nullptr;
+    size_t query_ent_cap = 0;         // ... in 4-byte words
     // sphx_tile_contour_* (a tile context; contour_buf is its scratch too — sphx_surface_contour refuses a tile): the query in flight
     // between _sample, _border_fetch, _cut and _fetch.  stage 0: none, 1: sampled (the border can be fetched, the cut is owed),
     // 2: cut (count and segments can be fetched)

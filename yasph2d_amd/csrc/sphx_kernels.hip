@@ -2936,3 +2936,5 @@ __global__ __launch_bounds__(64) void k_publish(DevScalars* scal, Mailbox* mb, u
 #include "sphx_multi_edit.inc"
 // the iso-contour of a sampled field as ordered segments, and the host stitcher that makes polylines of them (kernels + C ABI)
 #include "sphx_contour.inc"
+// the cell grids as a search service: the particles around given points and in given rectangles, with identities (kernels + C ABI)
+#include "sphx_query.inc"

@@ -1801,7 +1801,7 @@ void sphx_destroy(sphx_ctx* c) {
     dev_free(&c->bpos); dev_free(&c->bpos2); dev_free(&c->bid); dev_free(&c->bid2); dev_free(&c->nb_list); dev_free(&c->nb_wave); dev_free(&c->nb_counts); dev_free(&c->nb_remote);
     dev_free(&c->scan_partials); dev_free(&c->scan_state); dev_free(&c->d_scal); dev_free(&c->tile_blk); dev_free(&c->sample_buf); dev_free(&c->render_buf); dev_free(&c->edit_buf); dev_free(&c->state_dig); dev_free(&c->mstate_buf);
     dev_free(&c->track.set_buf); dev_free(&c->track.rec); dev_free(&c->track.scratch); dev_free(&c->fields_buf);
-    dev_free(&c->stats.scratch); dev_free(&c->stats.rec); dev_free(&c->tsample.null_grid); dev_free(&c->contour_buf);
+    dev_free(&c->stats.scratch); dev_free(&c->stats.rec); dev_free(&c->tsample.null_grid); dev_free(&c->contour_buf); dev_free(&c->query_buf); dev_free(&c->query_ent);
     free_grid(c->gdyn);
     free_grid(c->gstat);
     if (c->mbox) hipHostFree((void*)c->mbox);
