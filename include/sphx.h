@@ -21,7 +21,7 @@
  *       surface (sphx_set_boundary, sphx_upload, sphx_append, sphx_remove, sphx_download*, sphx_num_*, sphx_view_*, sphx_sample_*, sphx_render*, sphx_state_*, sphx_track_*, sphx_download_by_id, sphx_particle_fields, sphx_fluid_stats, sphx_stats_*, sphx_query_radius, sphx_select), the Solver trait (sphx_clear_cached,
  *       sphx_step_begin[_law], sphx_step_finish, sphx_wcsph_step_*), the same trait over a device list (sphx_multi_create[_rank],
  *       sphx_multi_destroy, sphx_multi_set_boundary, sphx_multi_upload, sphx_multi_clear_cached, sphx_multi_step_begin/finish,
- *       sphx_multi_simulation_step[s], sphx_multi_download, sphx_multi_sample_*, sphx_sample_merge, sphx_multi_num_owned, sphx_multi_last_error, sphx_comm_ops) and
+ *       sphx_multi_simulation_step[s], sphx_multi_download, sphx_multi_sample_*, sphx_sample_merge, sphx_multi_query_radius, sphx_multi_select, sphx_query_merge, sphx_multi_num_owned, sphx_multi_last_error, sphx_comm_ops) and
  *       the status / flag codes.
  *   INSPECTION — parity tests and tools, not on the hot path, may change with the data layout:
  *       sphx_update_neighborhood, sphx_update_densities, sphx_compute_alpha (the pieces benches/ drives), sphx_download_solver_state,
@@ -79,7 +79,9 @@ extern "C" {
                             * 5 (additive): sphx_surface_contour, sphx_contour_chain, sphx_contour_out, SPHX_CONTOUR_*
                             * 5 (additive): sphx_multi_surface_contour, sphx_multi_contour_out, sphx_contour_merge,
                             *    sphx_tile_contour_sample / _border_fetch / _cut / _fetch
-                            * 5 (additive): sphx_query_radius, sphx_select, sphx_query_out, sphx_select_out, SPHX_QUERY_*, SPHX_SELECT_* */
+                            * 5 (additive): sphx_query_radius, sphx_select, sphx_query_out, sphx_select_out, SPHX_QUERY_*, SPHX_SELECT_*
+                            * 5 (additive): sphx_multi_query_radius, sphx_multi_select, sphx_query_merge, sphx_multi_query_out,
+                            *    sphx_multi_select_out, sphx_tile_query_radius / _query_fetch / _select / _select_fetch, sphx_tile_query_part */
 
 /* ---- status codes ---- */
 enum {
@@ -427,7 +429,7 @@ int sphx_remove(sphx_ctx* ctx, const sphx_rect* rects, uint32_t n_rects, uint32_
  *   Determinism: no atomic decides a position; two calls on one state return the same bytes.
  *   When allowed, refusals, side effects: as sphx_sample_points (the same SPHX_ERR_NOT_READY rules; the call only reads, a run with
  *     queries between its steps is bit-identical to one without).  A tile context is refused with SPHX_ERR_INVALID_ARGUMENT; a tiled
- *     run has no counterpart yet.  m == 0 succeeds with *count = 0 (and offsets[0] = 0 when offsets is given).
+ *     run is served by sphx_multi_query_radius and sphx_multi_select ("neighbour queries of a tiled run").  m == 0 succeeds with *count = 0 (and offsets[0] = 0 when offsets is given).
  *   Argument errors (SPHX_ERR_INVALID_ARGUMENT, the message names the argument): out or out->count NULL, xy NULL with m > 0, unknown
  *     flag bits, m >= 2^31, a bad radius, a device offsets or count pointer that is not 8-byte aligned.
  * SPHX_QUERY_DEVICE_POINTERS: xy and every pointer of out are device pointers; everything is enqueued on the context's stream without
@@ -1482,6 +1484,104 @@ int sphx_tile_remove_mark(sphx_ctx* tile_ctx, const sphx_rect* rects, uint32_t n
 int sphx_tile_remove_fetch(sphx_ctx* tile_ctx, uint32_t* out_removed_owned);
 int sphx_tile_append(sphx_ctx* tile_ctx, const float* pos_xy, const float* vel_xy /* NULL = 0 */, const uint32_t* ids, uint32_t n_new);
 int sphx_tile_grow(sphx_ctx* tile_ctx, uint32_t capacity);
+
+/* ---- neighbour queries of a tiled run (csrc/sphx_tiles.cpp; device passes csrc/sphx_query.inc, the fold csrc/sphx_query_merge.hpp;
+ * DESIGN.md section 4s) ------------------------------------------------------------------------------------------------------------
+ * sphx_query_radius / sphx_select for a sphx_multi, without sphx_multi_download and a second context.
+ * sphx_multi_query_radius:
+ * Who answers: the tile whose owned cell rectangle contains cell_of(q), as in "sampling the fields of a tiled run": exactly one tile
+ *   per point.  A NaN coordinate goes to cell 0 and fails every distance test, as in the single call.
+ * What it computes: the contract of sphx_query_radius, word for word, over THAT TILE'S OWN ARRAYS — candidates, acceptance, entry
+ *   order, nearest and its tie rule, the box rule, the radius rule and the capacity rule (nothing at or behind cap_entries is ever
+ *   written; offsets and count describe the FULL result).  Ghosts are candidates like any other particle.  With SPHX_QUERY_BOUNDARY the
+ *   set is the tile's clipped boundary.  Consequences: (a) in every mode the result is bit-identical to the restatement of that
+ *   contract (tests/query_reference.py) over the answering tile's own downloads, ids translated as below; (b) in tiling-invariant mode
+ *   offsets, id, dist_sq, nearest_id, nearest_dist_sq and count are byte for byte those of sphx_query_radius on a single context in the
+ *   same mode (slot is tile-local by definition); (c) for radius <= 0.9 * smoothing_length the result is every particle of the whole
+ *   run within the radius, whatever the tiling (a margin of 0.1 cell, far more than the rounding of the cell function: about 1e-3 cell
+ *   at the reference's grid origin).
+ * Ids: a fluid entry carries the particle id as sphx_multi_download reports it (owner bit cleared; the candidate may be a ghost).  A
+ *   boundary entry carries the index of the particle in the array given to sphx_multi_set_boundary: every tile keeps the map from its
+ *   clipped set to the caller's order, renewed whenever the boundary is clipped again (a re-partition), and the host translates.
+ *   slot is the index in the ANSWERING tile's own download (sphx_download / sphx_download_boundary on sphx_multi_tile_ctx).
+ * The ghost band: unlike sampling, a query reads only positions and ids of ring-1 ghosts.  Positions of ghosts are exact after every
+ *   exchange, and at every point where the call is allowed no advection is pending (a finished step's own exchange has applied it).  So
+ *   no halo exchange is ever triggered, the call only reads (the sweep direction is put back), sphx_multi_info().exchanges never moves
+ *   and the call is NOT COLLECTIVE: a rank may call alone, with points of its own.
+ * When allowed: after sphx_multi_upload, after every finished step and after sphx_multi_append / _remove / _state_load — each of them
+ *   ends with the re-grid of every tile, which is all the tile's state test asks for (the cell grids belong to the positions, no
+ *   advection pending, no step open): they hold without a refresh.  SPHX_ERR_NOT_READY where sphx_multi_sample_points returns it.
+ * A tile without any particle answers with empty lists over the fluid, and over its static grid with SPHX_QUERY_BOUNDARY.
+ * SPHX_ERR_INVALID_ARGUMENT (sphx_multi_last_error names the argument): m, out or out->count NULL, xy NULL with m > 0, m >= 2^31, a bad
+ *   radius, any flag bit but SPHX_QUERY_BOUNDARY, more than 64 tiles, rank mode without out->tile.  A refused call touches no tile.
+ *   m == 0 succeeds with *count = 0 (and offsets[0] = 0).
+ * Determinism: no atomic decides a position; two calls return the same bytes.
+ * In-process (sphx_multi_create): every point is answered; out->tile is optional.  Rank mode (sphx_multi_create_rank): the call returns
+ *   this rank's part — offsets over the rank's own entries, a point the rank does not answer has an empty range, tile = -1, nearest_*
+ *   SPHX_QUERY_NONE and +inf; count is the rank's total.  sphx_query_merge(m, parts, parts_cap, n_parts, cap_entries, out) folds such
+ *   parts into one result in the caller's order: pure host code; per point the part with tile >= 0, the lowest tile if several have
+ *   one, an empty range and -1 if none.  A part holds min(its count, parts_cap[p]) entries; if the result needs an entry that a part
+ *   truncated the call returns SPHX_ERR_CAPACITY.  Every part carries offsets, tile and the arrays out asks for; n_parts == 0 gives the
+ *   all-absent answer; nothing at or behind cap_entries is written.
+ * sphx_multi_select: sphx_remove's predicate, bit for bit, evaluated by every tile on the particles it OWNS (a ghost never answers),
+ *   in the order of sphx_multi_download — tiles in rank order, each in ascending local index; tile and slot say where each particle
+ *   lives, id is the id with the owner bit cleared.  count is 64-bit; the capacity rule is that of the query.  Allowed wherever
+ *   sphx_multi_download is (SPHX_ERR_NOT_READY inside an open step and before the first upload); it only reads.  Rank mode: this rank's
+ *   part; the whole answer is the parts concatenated in rank order, as for sphx_multi_particle_fields.  Argument errors: sphx_select's
+ *   (without a device-pointer flag), more than 64 tiles.
+ * Device work per tile: all m points go up (8 bytes each); a stable selection (count per workgroup, scan, write) lists the points the
+ *   tile owns in ascending index; the counting and the emitting walk of sphx_query_radius run over that list with every lane live, so
+ *   the K tiles together walk m points; per answered point 24 bytes and per kept entry 12 bytes come back.  Figures: DESIGN.md 4s.
+ * One tile (INTERNAL, accepted only on a tile context — sphx_query_radius and sphx_select keep refusing one):
+ *   sphx_tile_query_radius enqueues upload, selection and the counting walk.  sphx_tile_query_fetch is called twice: with part->point
+ *   and part->offset NULL it reads the two totals (the one synchronisation), enqueues the emitting walk for kept = min(total,
+ *   cap_entries) entries and reports n_points, total and kept; with arrays of those sizes it copies the records (point: ascending point
+ *   indices; offset: the tile-local first entry of each) and the kept entries, and ends the query.  sphx_tile_select enqueues the flag
+ *   and scan passes; sphx_tile_select_fetch reports the total and, given cap > 0 and an array, emits and copies min(total, cap) pairs
+ *   (it may be called again until the next enqueue). */
+typedef struct sphx_multi_query_out {      /* host arrays */
+    uint64_t* offsets;          /* [m+1] CSR over the caller's points, or NULL */
+    uint32_t* id;               /* [cap_entries] particle id as sphx_multi_download reports it (owner bit cleared); with
+                                   SPHX_QUERY_BOUNDARY the index of the particle in the array given to sphx_multi_set_boundary; or NULL */
+    float*    dist_sq;          /* [cap_entries] or NULL */
+    uint32_t* slot;             /* [cap_entries] index in the ANSWERING tile's own download (sphx_multi_tile_ctx; boundary: in its
+                                   sphx_download_boundary), or NULL */
+    uint32_t* nearest_id;       /* [m]  SPHX_QUERY_NONE if none, or NULL */
+    uint32_t* nearest_slot;     /* [m]  likewise, or NULL */
+    float*    nearest_dist_sq;  /* [m]  0x7F800000 if none, or NULL */
+    int32_t*  tile;             /* [m]  global rank of the answering tile, -1: none of the local tiles; required in rank mode */
+    uint64_t* count;            /* [1]  total entries; required */
+} sphx_multi_query_out;         /* 72 bytes */
+int sphx_multi_query_radius(sphx_multi* m, const float* xy /* host */, uint32_t n, float radius, uint64_t cap_entries,
+                            uint32_t flags /* SPHX_QUERY_BOUNDARY or 0 */, const sphx_multi_query_out* out);
+int sphx_query_merge(uint32_t m, const sphx_multi_query_out* parts, const uint64_t* parts_cap, uint32_t n_parts, uint64_t cap_entries,
+                     const sphx_multi_query_out* out);   /* pure host code */
+typedef struct sphx_multi_select_out {
+    uint32_t* id;     /* [cap] or NULL */
+    int32_t*  tile;   /* [cap] global rank of the owning tile, or NULL */
+    uint32_t* slot;   /* [cap] index in that tile's own download, or NULL */
+    uint64_t* count;  /* [1] number selected by the local tiles; required */
+} sphx_multi_select_out;        /* 32 bytes */
+int sphx_multi_select(sphx_multi* m, const sphx_rect* rects, uint32_t n_rects, uint32_t flags /* SPHX_SELECT_OUTSIDE or 0 */, uint64_t cap,
+                      const sphx_multi_select_out* out);
+typedef struct sphx_tile_query_part {      /* host arrays */
+    uint32_t  n_points;         /* out: points this tile answers */
+    uint32_t  reserved;
+    uint64_t  total;            /* out: their entries */
+    uint64_t  kept;             /* out: min(total, cap_entries) */
+    uint32_t* point;            /* [n_points] ascending point indices */
+    uint64_t* offset;           /* [n_points] first entry of each, tile-local */
+    uint32_t* nearest_slot;     /* [n_points] each, or NULL */
+    uint32_t* nearest_id;
+    float*    nearest_dist_sq;
+    uint32_t* slot;             /* [kept] each, or NULL */
+    uint32_t* id;
+    float*    dist_sq;
+} sphx_tile_query_part;         /* 88 bytes */
+int sphx_tile_query_radius(sphx_ctx* tile_ctx, const float* xy /* host, [2m] */, uint32_t m, float radius, uint32_t flags, uint32_t want_nearest);
+int sphx_tile_query_fetch(sphx_ctx* tile_ctx, uint64_t cap_entries, sphx_tile_query_part* part);
+int sphx_tile_select(sphx_ctx* tile_ctx, const sphx_rect* rects, uint32_t n_rects, uint32_t flags);
+int sphx_tile_select_fetch(sphx_ctx* tile_ctx, uint32_t cap, uint32_t* slot /* host, [cap] */, uint32_t* id, uint32_t* out_total);
 
 /* ---- single-node scalar reductions through POSIX shared memory ---------------------------------------------------------------
  * The three per-step scalars of the tile driver (vmax, two residual sums) already sit in host memory (pinned mailbox) on every

@@ -16,7 +16,7 @@ from ._lib import (FLAG_DENSITY_ITER_CAP, FLAG_DIVERGENCE_ITER_CAP, FLAG_DENSE_C
 
 __all__ = ["SphxContext", "FluidParticleWorld", "TimeManager", "DFSPHSolver", "DFSPHMultiSolver", "default_params", "duration_from_secs_f32",
            "duration_as_secs_f32", "SphxError", "WCSPHSolver", "VISCOSITY_XSPH", "VISCOSITY_PHYSICAL", "SAMPLE_FIELDS", "gauge_elevation", "contour_chain", "contour_lines", "contour_merge",
-           "sample_merge", "render_fit", "render_merge", "track_merge", "track_merge_frames", "write_png", "SCENE_RECT", "TRACK_FIELDS", "MULTI_TRACK_FIELDS", "FIELD_NAMES", "STATS_DTYPE", "STATS_FRAME_DTYPE"]
+           "sample_merge", "query_merge", "render_fit", "render_merge", "track_merge", "track_merge_frames", "write_png", "SCENE_RECT", "TRACK_FIELDS", "MULTI_TRACK_FIELDS", "FIELD_NAMES", "STATS_DTYPE", "STATS_FRAME_DTYPE"]
 
 
 def _p(a):
@@ -397,6 +397,57 @@ def contour_merge(parts, cap=None):
     res = dict(segments=seg[:n], cell=cel[:n], count=count)
     if with_tile:
         res["tile"] = til[:n]
+    return res
+
+
+_QUERY_ENTRY = (("id", np.uint32), ("dist_sq", np.float32), ("slot", np.uint32))
+_QUERY_POINT = (("nearest_id", np.uint32), ("nearest_slot", np.uint32), ("nearest_dist_sq", np.float32))
+
+
+def query_merge(parts, cap=None):
+    """sphx_query_merge: the parts the ranks of one run returned from MultiSolver.query() for the SAME points (dicts with "offsets",
+    "tile", "count" and the lists / nearest arrays) folded into the answer of the whole run in the caller's point order -> a dict like
+    MultiSolver.query(tiles=True)'s, with the arrays every part has.  Per point the part with tile >= 0 answers (the lowest tile if
+    several do); nobody: an empty range, tile -1.  cap: the most entries to return (None: all).  A part that holds fewer entries than
+    the result needs raises SphxError(ERR_CAPACITY).  Host code; no GPU."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("query_merge: no parts (the number of points is taken from them)")
+    m = len(parts[0]["offsets"]) - 1
+    entry = [(f, t) for f, t in _QUERY_ENTRY if all(f in p for p in parts)]
+    point = [(f, t) for f, t in _QUERY_POINT if all(f in p for p in parts)]
+    arr = (_lib.SphxMultiQueryOut * len(parts))()
+    held = np.zeros(len(parts), np.uint64)
+    keep = []
+    for k, p in enumerate(parts):
+        off = np.ascontiguousarray(p["offsets"], np.uint64)
+        til = np.ascontiguousarray(p["tile"], np.int32)
+        if len(off) != m + 1 or len(til) != m:
+            raise ValueError("query_merge: the parts answer different point sets")
+        keep += [off, til]
+        arr[k].offsets, arr[k].tile = off.ctypes.data, til.ctypes.data or 1
+        for f, t in entry + point:
+            a = np.ascontiguousarray(p[f], t)
+            keep.append(a)
+            setattr(arr[k], f, a.ctypes.data or 1)
+        held[k] = min(len(p[f]) for f, _ in entry) if entry else 0
+    cap_ = sum(int(p["offsets"][m]) for p in parts) if cap is None else int(cap)  # (None: an upper bound, the parts' totals together)
+    res = dict(offsets=np.zeros(m + 1, np.uint64), tile=np.full(m, -1, np.int32))
+    res.update({f: np.zeros(cap_, t) for f, t in entry})
+    res.update({f: np.zeros(m, t) for f, t in point})
+    cnt = np.zeros(1, np.uint64)
+    o = _lib.SphxMultiQueryOut()
+    o.count = cnt.ctypes.data
+    for f, a in res.items():
+        setattr(o, f, a.ctypes.data or 1)
+    L = _lib.lib()
+    rc = L.sphx_query_merge(m, arr, held.ctypes.data_as(C.POINTER(C.c_uint64)), len(parts), cap_, C.byref(o))
+    if rc:
+        raise SphxError(rc, L.sphx_multi_last_error(None).decode())
+    n = min(int(cnt[0]), cap_)
+    for f, _ in entry:
+        res[f] = res[f][:n]
+    res["count"] = int(cnt[0])
     return res
 
 
@@ -1583,6 +1634,14 @@ class DFSPHMultiSolver(DFSPHSolver):
     # per-particle flow fields of the tiled run (MultiSolver.fields: computed by the tiles over their own arrays, no download)
     def fields(self, fields=FIELD_NAMES, by_id=False):
         return self.multi().fields(fields, by_id)
+
+    # neighbour queries of the tiled run (MultiSolver.query / select: answered by the tiles over their own arrays, nothing is exchanged;
+    # the borrowed view has no params, so the radius is required)
+    def query(self, points, radius=None, boundary=False, lists=True, nearest=True, cap=None, tiles=False):
+        return self.multi().query(points, radius, boundary, lists, nearest, cap, tiles)
+
+    def select(self, rects, outside=False, cap=None, by_id=False):
+        return self.multi().select(rects, outside, cap, by_id)
 
     # following particles by id (MultiSolver.track and friends; the recorder fires behind every step of simulation_steps(k))
     def track(self, ids):

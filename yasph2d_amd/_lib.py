@@ -153,6 +153,21 @@ class SphxSelectOut(C.Structure):  # 24 bytes
     _fields_ = [("index", C.c_void_p), ("id", C.c_void_p), ("count", C.c_void_p)]
 
 
+class SphxMultiQueryOut(C.Structure):  # sphx_multi_query_out: host pointers, 72 bytes
+    _fields_ = [("offsets", C.c_void_p), ("id", C.c_void_p), ("dist_sq", C.c_void_p), ("slot", C.c_void_p), ("nearest_id", C.c_void_p),
+                ("nearest_slot", C.c_void_p), ("nearest_dist_sq", C.c_void_p), ("tile", C.c_void_p), ("count", C.c_void_p)]
+
+
+class SphxMultiSelectOut(C.Structure):  # sphx_multi_select_out: host pointers, 32 bytes
+    _fields_ = [("id", C.c_void_p), ("tile", C.c_void_p), ("slot", C.c_void_p), ("count", C.c_void_p)]
+
+
+class SphxTileQueryPart(C.Structure):  # sphx_tile_query_part: host pointers, 88 bytes
+    _fields_ = [("n_points", C.c_uint32), ("reserved", C.c_uint32), ("total", C.c_uint64), ("kept", C.c_uint64), ("point", C.c_void_p),
+                ("offset", C.c_void_p), ("nearest_slot", C.c_void_p), ("nearest_id", C.c_void_p), ("nearest_dist_sq", C.c_void_p),
+                ("slot", C.c_void_p), ("id", C.c_void_p), ("dist_sq", C.c_void_p)]
+
+
 STATE_DEVICE_BUFFER = 1  # sphx_state_save / sphx_state_load flags
 STATE_SECTIONS = ("positions", "velocities", "particle_id", "density", "alpha", "kappa", "stiffness", "accel", "boundary")  # SPHX_STATE_SEC_*
 MULTI_STATE_SECTIONS = ("positions", "velocities", "particle_id", "density", "alpha", "kappa", "stiffness", "boundary")  # SPHX_MULTI_STATE_SEC_*
@@ -337,6 +352,13 @@ SIGNATURES = {
     "sphx_multi_sample_points": (_i, [_vp, _vp, _u32, _i, _u32, C.POINTER(SphxMultiSampleOut)]),
     "sphx_multi_sample_grid": (_i, [_vp, _f, _f, _f, _f, _u32, _u32, _i, _u32, C.POINTER(SphxMultiSampleOut)]),
     "sphx_sample_merge": (_i, [_u32, C.POINTER(SphxMultiSampleOut), _u32, C.POINTER(SphxMultiSampleOut)]),
+    "sphx_multi_query_radius": (_i, [_vp, _vp, _u32, _f, _u64, _u32, C.POINTER(SphxMultiQueryOut)]),
+    "sphx_query_merge": (_i, [_u32, C.POINTER(SphxMultiQueryOut), C.POINTER(_u64), _u32, _u64, C.POINTER(SphxMultiQueryOut)]),
+    "sphx_multi_select": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32, _u64, C.POINTER(SphxMultiSelectOut)]),
+    "sphx_tile_query_radius": (_i, [_vp, _vp, _u32, _f, _u32, _u32]),
+    "sphx_tile_query_fetch": (_i, [_vp, _u64, C.POINTER(SphxTileQueryPart)]),
+    "sphx_tile_select": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32]),
+    "sphx_tile_select_fetch": (_i, [_vp, _u32, _vp, _vp, C.POINTER(_u32)]),
     "sphx_multi_tile_rects": (_i, [_vp, C.POINTER(SphxTileRect), C.POINTER(_u32)]),
     "sphx_multi_ghost_rings": (_i, [_vp, C.POINTER(C.c_double)]),
     "sphx_tile_sample_points": (_i, [_vp, _vp, _u32, _i, _u32]),

@@ -408,6 +408,23 @@ struct sphx_ctx {
     size_t query_cap = 0;             // ... in 4-byte words
     uint32_t* query_ent = nullptr;
     size_t query_ent_cap = 0;         // ... in 4-byte words
+    // sphx_tile_query_* / sphx_tile_select* (a tile context; query_buf, query_ent and edit_buf are its scratch too — sphx_query_radius and
+    // sphx_select refuse a tile): the call in flight between the enqueue half and the fetch half.  An enqueue of either drops both.
+    struct TileQuery {
+        uint32_t stage = 0;  // 0: none, 1: counted (the totals are on the device), 2: sized (totals read, entries and offsets final on the stream)
+        uint32_t m = 0, boundary = 0, nearest = 0;
+        float r2 = 0.0f;
+        size_t at_pref = 0, at_cnt = 0, at_xy = 0, at_own = 0, at_list = 0, at_near = 0;  // word offsets in query_buf
+        uint32_t nbp = 0;    // workgroups of the selection passes
+        uint32_t n_own = 0;  // points this tile answers
+        uint64_t total = 0, kept = 0;
+    } tquery;
+    struct TileSelect {
+        uint32_t stage = 0;  // 0: none, 1: flagged and scanned, 2: the total has been read
+        uint32_t n = 0, nb = 0, total = 0;
+        sphx_rect r[SPHX_REMOVE_MAX_RECTS] = {};
+        uint32_t n_rects = 0, outside = 0;  // (outside: as the kernels take it, i.e. the call's predicate inverted)
+    } tselect;
     // sphx_tile_contour_* (a tile context; contour_buf is its scratch too — sphx_surface_contour refuses a tile): the query in flight
     // between _sample, _border_fetch, _cut and _fetch.  stage 0: none, 1: sampled (the border can be fetched, the cut is owed),
     // 2: cut (count and segments can be fetched)

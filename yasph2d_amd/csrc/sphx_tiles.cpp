@@ -43,6 +43,7 @@
 #include "sphx_contour_merge.hpp"
 #include "sphx_multi_edit.hpp"
 #include "sphx_multi_state_format.hpp"
+#include "sphx_query_merge.hpp"
 #include "sphx_render_merge.hpp"
 #include "sphx_render_window.hpp"
 #include "sphx_sample_window.hpp"
@@ -482,6 +483,7 @@ struct TileDriver {
     uint32_t n_local = 0;
     std::vector<float> boundary;
     std::vector<uint32_t> bcx, bcy;
+    std::vector<uint32_t> clip_map;  // clipped boundary index -> index in `boundary` (the caller's order), renewed by every clip_boundary()
     float grid_min[2], cell_inv;
     // step in flight
     float step_dt_prev = 0, step_vmax = 0;
@@ -599,10 +601,12 @@ struct TileDriver {
         const uint32_t m = halo_max + 2 + (O.rebalance_every ? boundary_margin : 0);
         clip_rect = rect;
         std::vector<float> keep;
+        clip_map.clear();  // (sphx_multi_query_radius: a tile's boundary_id indexes the clipped set; this is the way back to the caller's order)
         for (size_t i = 0; i < bcx.size(); ++i)
             if (in_rect(bcx[i], bcy[i], rect, m)) {
                 keep.push_back(boundary[2 * i]);
                 keep.push_back(boundary[2 * i + 1]);
+                clip_map.push_back((uint32_t)i);
             }
         TCHK(sphx_set_boundary(ctx, keep.empty() ? nullptr : keep.data(), (uint32_t)(keep.size() / 2)));
         return SPHX_OK;
@@ -1180,6 +1184,61 @@ struct TileDriver {
         if (fields & SPHX_SAMPLE_FIELD_COUNT) win->count = p;
         const int rc = sphx_tile_sample_window_fetch(ctx, win);
         if (rc) err = std::string("sphx_tile_sample_window_fetch: ") + sphx_last_error(ctx);
+        return rc;
+    }
+
+    // sphx_multi_query_radius: a query reads positions and ids of ring-1 ghosts only, and those are exact after every exchange (they move
+    // with the advection that rides on one, and none is pending where the call is allowed): no sample_band(), nothing is exchanged.
+    // first half: upload, selection and the counting walk go onto the tile's stream
+    int query_enqueue(const float* xy, uint32_t n, float radius, uint32_t flags, bool nearest) {
+        const int rc = sphx_tile_query_radius(ctx, xy, n, radius, flags, nearest ? 1u : 0u);
+        if (rc) err = std::string("sphx_tile_query_radius: ") + sphx_last_error(ctx);
+        return rc;
+    }
+    // ... second half, step 1: the totals come back, the emitting walk goes onto the stream
+    sphx_tile_query_part query_part{};
+    std::vector<uint32_t> query_host;   // the part's arrays on the host (grown on demand, kept between calls)
+    std::vector<uint64_t> query_host_off;
+    int query_size(uint64_t cap_entries) {
+        query_part = sphx_tile_query_part{};
+        const int rc = sphx_tile_query_fetch(ctx, cap_entries, &query_part);
+        if (rc) err = std::string("sphx_tile_query_fetch: ") + sphx_last_error(ctx);
+        return rc;
+    }
+    // ... step 2: the records of the answered points and the kept entries come back
+    int query_fetch(uint64_t cap_entries, bool nearest, bool lists) {
+        const size_t n = query_part.n_points, kept = lists ? (size_t)query_part.kept : 0;
+        const size_t words = n + (nearest ? 3 * n : 0) + 3 * kept;
+        if (query_host.size() < words + 1) query_host.resize(words + 1);
+        if (query_host_off.size() < n + 1) query_host_off.resize(n + 1);
+        uint32_t* p = query_host.data();
+        query_part.point = p, p += n;
+        query_part.offset = query_host_off.data();
+        if (nearest) {
+            query_part.nearest_slot = p, p += n;
+            query_part.nearest_id = p, p += n;
+            query_part.nearest_dist_sq = (float*)p, p += n;
+        }
+        if (kept) {
+            query_part.slot = p, p += kept;
+            query_part.id = p, p += kept;
+            query_part.dist_sq = (float*)p;
+        }
+        const int rc = sphx_tile_query_fetch(ctx, cap_entries, &query_part);
+        if (rc) err = std::string("sphx_tile_query_fetch: ") + sphx_last_error(ctx);
+        return rc;
+    }
+    // sphx_multi_select: the flag and scan passes; then the total; then the pairs
+    std::vector<uint32_t> select_host;
+    int select_enqueue(const sphx_rect* rects, uint32_t n_rects, uint32_t flags) {
+        const int rc = sphx_tile_select(ctx, rects, n_rects, flags);
+        if (rc) err = std::string("sphx_tile_select: ") + sphx_last_error(ctx);
+        return rc;
+    }
+    int select_fetch(uint32_t cap, uint32_t* out_total) {
+        if (select_host.size() < 2 * (size_t)cap + 2) select_host.resize(2 * (size_t)cap + 2);
+        const int rc = sphx_tile_select_fetch(ctx, cap, cap ? select_host.data() : nullptr, cap ? select_host.data() + cap : nullptr, out_total);
+        if (rc) err = std::string("sphx_tile_select_fetch: ") + sphx_last_error(ctx);
         return rc;
     }
 };
@@ -2908,6 +2967,171 @@ int sphx_multi_particle_fields(sphx_multi* m, uint32_t flags, const sphx_multi_f
         if (out->tile) std::fill(out->tile + at, out->tile + at + got, (int32_t)track_tile_rank(m, k));
         at += got;
     }
+    return SPHX_OK;
+}
+
+}  // extern "C"
+
+// ---- neighbour queries of a tiled run (include/sphx.h, "neighbour queries of a tiled run"; the device passes are csrc/sphx_query.inc,
+// the fold csrc/sphx_query_merge.hpp) --------------------------------------------------------------------------------------------------
+namespace {
+
+namespace qh = sphx_query_host;
+static_assert(qh::ERR_CAPACITY == SPHX_ERR_CAPACITY && qh::OK == SPHX_OK && qh::NONE == SPHX_QUERY_NONE, "the fold's codes are the header's");
+
+qh::Out query_out(const sphx_multi_query_out& o, uint64_t cap) {
+    qh::Out r;
+    r.offsets = o.offsets;
+    r.id = o.id;
+    r.d2 = (uint32_t*)o.dist_sq;
+    r.slot = o.slot;
+    r.nearest_id = o.nearest_id;
+    r.nearest_slot = o.nearest_slot;
+    r.nearest_d2 = (uint32_t*)o.nearest_dist_sq;
+    r.tile = o.tile;
+    r.count = o.count;
+    r.cap = cap;
+    return r;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sphx_query_merge(uint32_t m, const sphx_multi_query_out* parts, const uint64_t* parts_cap, uint32_t n_parts, uint64_t cap_entries,
+                     const sphx_multi_query_out* out) {
+    auto bad = [](const char* what) {
+        g_multi_error = std::string("sphx_query_merge: ") + what;  // (no object to hang the message on: sphx_multi_last_error(NULL))
+        return SPHX_ERR_INVALID_ARGUMENT;
+    };
+    if (!out) return bad("out is NULL");
+    if (!out->count) return bad("out->count is NULL");
+    if (n_parts && !parts) return bad("parts is NULL with n_parts > 0");
+    if (m >= (1u << 31)) return bad("m must be < 2^31");
+    const bool lists = out->id || out->dist_sq || out->slot;
+    if (n_parts && lists && !parts_cap) return bad("parts_cap is NULL while out asks for entries");
+    std::vector<qh::Part> ps(n_parts);
+    for (uint32_t p = 0; p < n_parts; ++p) {
+        const sphx_multi_query_out& q = parts[p];
+        if (!q.offsets) return bad("a part has no offsets array");
+        if (!q.tile) return bad("a part has no tile array");
+        if ((out->id && !q.id) || (out->dist_sq && !q.dist_sq) || (out->slot && !q.slot) || (out->nearest_id && !q.nearest_id) ||
+            (out->nearest_slot && !q.nearest_slot) || (out->nearest_dist_sq && !q.nearest_dist_sq))
+            return bad("out asks for an array a part lacks");
+        qh::Part& r = ps[p];
+        r.n = m;
+        r.offset = q.offsets;
+        r.total = q.offsets[m];
+        r.tile = q.tile;
+        r.nearest_id = q.nearest_id;
+        r.nearest_slot = q.nearest_slot;
+        r.nearest_d2 = (const uint32_t*)q.nearest_dist_sq;
+        r.id = q.id;
+        r.d2 = (const uint32_t*)q.dist_sq;
+        r.slot = q.slot;
+        r.held = parts_cap ? std::min<uint64_t>(q.offsets[m], parts_cap[p]) : 0u;
+    }
+    const int rc = qh::merge(m, ps.data(), n_parts, query_out(*out, cap_entries));
+    if (rc) g_multi_error = "sphx_query_merge: the result needs an entry that a part truncated (its parts_cap is below its count)";
+    return rc;
+}
+
+int sphx_multi_query_radius(sphx_multi* m, const float* xy, uint32_t n, float radius, uint64_t cap_entries, uint32_t flags, const sphx_multi_query_out* out) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    const char* const fn = "sphx_multi_query_radius";
+    if (!out) return sample_bad(m, fn, "out is NULL");
+    if (!out->count) return sample_bad(m, fn, "out->count is NULL");
+    if (n && !xy) return sample_bad(m, fn, "xy is NULL with m > 0");
+    if (flags & ~(uint32_t)SPHX_QUERY_BOUNDARY) return sample_bad(m, fn, "unknown flags bits (there is no device-pointer path across several devices)");
+    if (n >= (1u << 31)) return sample_bad(m, fn, "m must be < 2^31");
+    if (!std::isfinite(radius) || !(radius > 0.0f) || radius > m->P.smoothing_length)
+        return sample_bad(m, fn, "radius must be finite, > 0 and <= smoothing_length");
+    if (m->world > 64) return sample_bad(m, fn, "more than 64 tiles");
+    if (m->rank_mode && !out->tile) return sample_bad(m, fn, "out->tile is NULL in rank mode (it says which points this rank answered)");
+    if (n == 0) {
+        out->count[0] = 0u;
+        if (out->offsets) out->offsets[0] = 0u;
+        return SPHX_OK;
+    }
+    int rc;
+    if ((rc = multi_state_ready(m, fn, true))) return rc;
+    const bool lists = out->id || out->dist_sq || out->slot;
+    const bool nearest = out->nearest_id || out->nearest_slot || out->nearest_dist_sq;
+    const uint64_t cap = lists ? cap_entries : 0u;
+    // every local tile enqueues on its own stream and device first; then the totals are read and the emitting walks enqueued; then the
+    // parts are collected: the tiles' passes overlap.  No tile exchanges anything (TileDriver::query_enqueue).
+    for (size_t k = 0; k < m->tiles.size(); ++k)
+        if ((rc = m->tiles[k]->query_enqueue(xy, n, radius, flags, nearest))) return sample_tile_failed(m, k, rc);
+    for (size_t k = 0; k < m->tiles.size(); ++k)
+        if ((rc = m->tiles[k]->query_size(cap))) return sample_tile_failed(m, k, rc);
+    std::vector<qh::Part> ps(m->tiles.size());
+    for (size_t k = 0; k < m->tiles.size(); ++k) {
+        TileDriver& t = *m->tiles[k];
+        if ((rc = t.query_fetch(cap, nearest, lists))) return sample_tile_failed(m, k, rc);
+        const sphx_tile_query_part& q = t.query_part;
+        qh::Part& r = ps[k];
+        r.point = q.point;
+        r.n = q.n_points;
+        r.offset = q.offset;
+        r.total = q.total;
+        r.rank = (int32_t)track_tile_rank(m, k);
+        r.nearest_id = q.nearest_id;
+        r.nearest_slot = q.nearest_slot;
+        r.nearest_d2 = (const uint32_t*)q.nearest_dist_sq;
+        r.id = q.id;
+        r.d2 = (const uint32_t*)q.dist_sq;
+        r.slot = q.slot;
+        r.held = lists ? q.kept : 0u;
+        if (flags & SPHX_QUERY_BOUNDARY) r.id_map = t.clip_map.data(), r.id_map_n = (uint32_t)t.clip_map.size();
+        for (uint32_t j = 0; j < q.n_points; ++j)
+            if (q.point[j] >= n || (j && q.point[j] <= q.point[j - 1])) {
+                m->err = std::string(fn) + ": tile " + std::to_string(k) + " returned a record outside the point set";
+                return SPHX_ERR_HIP;
+            }
+    }
+    if ((rc = qh::merge(n, ps.data(), (uint32_t)ps.size(), query_out(*out, cap)))) {
+        m->err = std::string(fn) + ": a tile kept fewer entries than the merged list needs";
+        return rc;
+    }
+    return SPHX_OK;
+}
+
+int sphx_multi_select(sphx_multi* m, const sphx_rect* rects, uint32_t n_rects, uint32_t flags, uint64_t cap, const sphx_multi_select_out* out) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    const char* const fn = "sphx_multi_select";
+    if (!out) return sample_bad(m, fn, "out is NULL");
+    if (!out->count) return sample_bad(m, fn, "out->count is NULL");
+    if (n_rects > SPHX_REMOVE_MAX_RECTS) return sample_bad(m, fn, "n_rects is larger than SPHX_REMOVE_MAX_RECTS");
+    if (n_rects && !rects) return sample_bad(m, fn, "rects is NULL with n_rects > 0");
+    if (flags & ~(uint32_t)SPHX_SELECT_OUTSIDE) return sample_bad(m, fn, "unknown flags bits (there is no device-pointer path across several devices)");
+    for (uint32_t k = 0; k < n_rects; ++k)
+        if (std::isnan(rects[k].x0) || std::isnan(rects[k].y0) || std::isnan(rects[k].x1) || std::isnan(rects[k].y1))
+            return sample_bad(m, fn, "a rectangle bound is NaN (rects)");
+    if (m->world > 64) return sample_bad(m, fn, "more than 64 tiles");
+    int rc;
+    if ((rc = multi_state_ready(m, fn, true))) return rc;
+    for (size_t k = 0; k < m->tiles.size(); ++k)
+        if ((rc = m->tiles[k]->select_enqueue(rects, n_rects, flags))) return sample_tile_failed(m, k, rc);
+    std::vector<uint32_t> totals(m->tiles.size(), 0u);
+    for (size_t k = 0; k < m->tiles.size(); ++k)
+        if ((rc = m->tiles[k]->select_fetch(0u, &totals[k]))) return sample_tile_failed(m, k, rc);
+    const bool lists = out->id || out->tile || out->slot;
+    uint64_t at = 0;
+    for (size_t k = 0; k < m->tiles.size(); ++k) {
+        const uint32_t got = (lists && at < cap) ? (uint32_t)std::min<uint64_t>(totals[k], cap - at) : 0u;
+        if (got) {
+            TileDriver& t = *m->tiles[k];
+            if (out->id || out->slot) {
+                uint32_t again = 0;
+                if ((rc = t.select_fetch(got, &again))) return sample_tile_failed(m, k, rc);
+                if (out->slot) std::memcpy(out->slot + at, t.select_host.data(), (size_t)got * 4);
+                if (out->id) std::memcpy(out->id + at, t.select_host.data() + got, (size_t)got * 4);
+            }
+            if (out->tile) std::fill(out->tile + at, out->tile + at + got, (int32_t)track_tile_rank(m, k));
+        }
+        at += totals[k];
+    }
+    out->count[0] = at;
     return SPHX_OK;
 }
 

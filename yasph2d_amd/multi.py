@@ -416,6 +416,88 @@ class MultiSolver:
             res["tile"] = til[:n]
         return res
 
+    # ---- neighbour queries of the tiled run (the contract is in include/sphx.h, "neighbour queries of a tiled run") ----
+    def _in_rank_mode(self):
+        i = self.info()
+        return i["local_tiles"] < i["world"]
+
+    def query(self, points, radius=None, boundary=False, lists=True, nearest=True, cap=None, tiles=False):
+        """sphx_multi_query_radius: the particles within `radius` of m query points (float32 [m, 2], numpy), each point answered by the
+        tile that owns its cell over that tile's own arrays, ghosts included — no download.  radius: None = the smoothing length h.
+        boundary=True answers over the boundary particles instead of the fluid.
+        Returns dict(offsets uint64 [m + 1] (CSR), count; with lists: id uint32 [n] (the particle id download() reports; boundary: the
+        index in the array given to set_boundary), dist_sq float32 [n], slot uint32 [n] (the index in the answering tile's own
+        download); with nearest: nearest_id, nearest_slot uint32 [m] (_lib.QUERY_NONE where nothing is accepted), nearest_dist_sq
+        float32 [m] (+inf there); with tiles=True (always in rank mode): tile int32 [m], the tile that answered).  cap: the most entries
+        to return (n = min(count, cap)); None makes two calls, the count first, so n = count.
+        Nothing is exchanged and the run is untouched; the call is not collective.  Rank mode: this rank's part — empty ranges, tile -1
+        and no nearest for the points other ranks answer; fold the ranks' parts with yasph2d_amd.query_merge."""
+        if radius is None and self.params is None:
+            raise ValueError("radius=None needs the params the multi was created with (a borrowed view has none): pass the radius")
+        r = float(np.float32(self.params.smoothing_length if radius is None else radius))
+        pts = np.ascontiguousarray(points, np.float32)
+        if pts.ndim != 2 or pts.shape[1] != 2:
+            raise ValueError("points must be a float32 [m, 2] array, not shape %s" % (pts.shape,))
+        m = len(pts)
+        flags = _lib.QUERY_BOUNDARY if boundary else 0
+        want_tile = tiles or self._in_rank_mode()
+        cnt, off = np.zeros(1, np.uint64), np.zeros(m + 1, np.uint64)
+        o = _lib.SphxMultiQueryOut()
+        o.offsets, o.count = off.ctypes.data, cnt.ctypes.data
+        res = dict(offsets=off)
+        if nearest:
+            res.update(nearest_id=np.full(m, _lib.QUERY_NONE, np.uint32), nearest_slot=np.full(m, _lib.QUERY_NONE, np.uint32),
+                       nearest_dist_sq=np.full(m, np.inf, np.float32))
+            for f in ("nearest_id", "nearest_slot", "nearest_dist_sq"):
+                setattr(o, f, res[f].ctypes.data or 1)
+        if want_tile:
+            res["tile"] = np.full(m, -1, np.int32)
+            o.tile = res["tile"].ctypes.data or 1
+        cap_ = int(cap) if cap is not None else 0
+        if cap is None or not lists:
+            self._chk(self.L.sphx_multi_query_radius(self.h, _p(pts), m, r, 0, flags, C.byref(o)))  # count only: one walk
+            cap_ = int(cnt[0]) if cap is None else cap_
+        if lists:
+            ids, d2, slot = np.zeros(cap_, np.uint32), np.zeros(cap_, np.float32), np.zeros(cap_, np.uint32)
+            if cap is not None or cap_:
+                o.id, o.dist_sq, o.slot = (ids.ctypes.data, d2.ctypes.data, slot.ctypes.data) if cap_ else (None, None, None)
+                self._chk(self.L.sphx_multi_query_radius(self.h, _p(pts), m, r, cap_, flags, C.byref(o)))
+            n = min(int(cnt[0]), cap_)
+            res.update(id=ids[:n], dist_sq=d2[:n], slot=slot[:n])
+        res["count"] = int(cnt[0])
+        return res
+
+    def select(self, rects, outside=False, cap=None, by_id=False):
+        """sphx_multi_select: the particles sphx_multi_remove(rects, outside) would remove — and nothing is removed.  Every tile answers
+        for the particles it owns; the result is in the order of download().  Returns dict(id uint32 [n], tile int32 [n] (the owning
+        tile), slot uint32 [n] (the index in tile_context(tile).download()), count).  cap: the most to return (n = min(count, cap));
+        None makes two calls, the count first.  by_id=True sorts the rows by id on the host.  Rank mode: this rank's part; the whole
+        answer is the ranks' parts concatenated in rank order."""
+        from . import _rect_array
+
+        arr, k = _rect_array(rects)
+        flags = _lib.SELECT_OUTSIDE if outside else 0
+        cnt = np.zeros(1, np.uint64)
+        o = _lib.SphxMultiSelectOut()
+        o.count = cnt.ctypes.data
+        if cap is None:
+            self._chk(self.L.sphx_multi_select(self.h, arr, k, flags, 0, C.byref(o)))
+            cap_ = int(cnt[0])
+        else:
+            cap_ = int(cap)
+        ids, til, slot = np.zeros(cap_, np.uint32), np.full(cap_, -1, np.int32), np.zeros(cap_, np.uint32)
+        if cap_:
+            o.id, o.tile, o.slot = ids.ctypes.data, til.ctypes.data, slot.ctypes.data
+        if cap is not None or cap_:
+            self._chk(self.L.sphx_multi_select(self.h, arr, k, flags, cap_, C.byref(o)))
+        n = min(int(cnt[0]), cap_)
+        res = dict(id=ids[:n], tile=til[:n], slot=slot[:n])
+        if by_id:
+            order = np.argsort(res["id"], kind="stable")
+            res = {f: a[order] for f, a in res.items()}
+        res["count"] = int(cnt[0])
+        return res
+
     # ---- per-particle flow fields of the tiled run (the contract is in include/sphx.h, "per-particle flow fields of a tiled run") ----
     def fields(self, fields=None, by_id=False):
         """sphx_multi_particle_fields: velocity gradient, divergence, vorticity and colour-field gradient (SphxContext.fields) at every
