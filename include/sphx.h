@@ -740,6 +740,11 @@ int sphx_debug_rigid_predict_counts(sphx_ctx* ctx, uint64_t out[4]);
  * ran ahead for the next one (where a rigid pass left the array to its reader, the fill it left out is queued first; the course of
  * the run does not change).  out_xy holds 2 * N floats.  Waits for the stream. */
 int sphx_debug_download_accel(sphx_ctx* ctx, float* out_xy);
+/* Test aid: sphx_download's arrays between sphx_wcsph_step_begin and sphx_wcsph_step_finish, where sphx_download is refused like in
+ * every open step: the re-sorted, leap-frogged positions, the velocities at the half step (wscsph.rs:148), the Poly6 densities and
+ * the ids.  Any pointer may be NULL.  Outside a WCSPH step: SPHX_ERR_NOT_READY.  Waits for the stream; the course of the run does not
+ * change. */
+int sphx_debug_download_wcsph_half_step(sphx_ctx* ctx, float* pos_xy, float* vel_xy, float* density, uint32_t* particle_id);
 
 /* ---- Solver trait (solver/mod.rs:12-18) ---------------------------------------------------------------------- */
 /* Solver::clear_cached_data (dfsph.rs:406-412) */

@@ -17,7 +17,20 @@ from dfsph_reference64 import Restatement, brute_force_neighbors
 U = 2.0 ** -24
 C = 2.0
 # roundings outside the neighbour sum, per output
-K = dict(density=8, alpha=16, vmax_sq=16, predict=12, k=16, velocity=16, residual=8, position=4)
+K = dict(density=8, alpha=16, vmax_sq=16, predict=12, k=16, velocity=16, residual=8, position=4,
+         # WCSPH (tests/wcsph_lockstep.py), counted on the Rust expressions as the entries above were:
+         # wscsph.rs:93-105 per neighbour: ri_to_rj 1, r_sq 3, sqrt 1, pi + pj 1, -mass * 1, 2 rhoi rhoj 2, / 1, h - r 1, n_grad hsubr hsubr 2,
+         # r + eps 1, / 1, * ri_to_rj 1, pressure_unsmoothed * 1, += 1 (18); the viscous term (xsph.rs:22 with poly6.rs:24-28, the
+         # longer of the two models): hsq - r_sq 1, n d d d 3, eps * m 1, * W 1, rhoj * dt 1, / 1, vj - vi 1, * 1, += 1 (11); the two
+         # pressures' own roundings are in their magnitude.  29 -> 32.
+         wcsph_accel=32,
+         # wscsph.rs:148-149 from the state before: 0.5 dt exact, * a 1, v += 1, v * dt 1, pos += 1.  4.
+         leapfrog=4,
+         # wscsph.rs:162 from an implementation's own v and a: a * dt 1, v + 1, magnitude2 3 (5), each of the first two doubled in the
+         # square (7).  -> 8.
+         wcsph_vmax_sq=8,
+         # wscsph.rs:176 on the restated accelerations: 0.5 * dt 0, * a 1, += 1 on top of the accelerations' own 32.  -> 36.
+         wcsph_velocity=36)
 WHOLE_DOMAIN = (0, 65536, 0, 65536)
 PARTICLE_DENSITY = 10000.0  # the default_params() argument the parameter block was made with
 
@@ -209,9 +222,10 @@ def _abs(x):
     return np.abs(np.asarray(x, np.float64))
 
 
-def check_trace(trace, ref, bounds, where="", rows=None):
+def check_trace(trace, ref, bounds, where="", rows=None, model=None):
     """Applies `ref` to every recorded sub-step; the ratios go to `bounds`.  rows: compare these particles (slots) only — the
-    residual sums and vmax, which need every particle, are then not compared."""
+    residual sums and vmax, which need every particle, are then not compared.  model: ("xsph", epsilon) or ("physical", mu), handed
+    to ref.nonpressure (None: the model `ref` was made with)."""
     acc, folded = None, False
     for step, (op, ret, pre, post) in enumerate(trace):
         name = op[0]
@@ -242,14 +256,15 @@ def check_trace(trace, ref, bounds, where="", rows=None):
                 assert unchanged, tag + ": a re-grid changed velocities"
         elif name == "nonpressure":
             dt_prev = float(op[1])
-            acc = ref.nonpressure(X, pre["vel"], pre["density"], sl, dt_prev)
+            acc = ref.nonpressure(X, pre["vel"], pre["density"], sl, dt_prev, model)
             if rows is None:
                 vsq, vsq_m = ref.max_velocity_sq(pre["vel"], acc[0], acc[1], dt_prev)
                 bounds.check("vmax_sq", [ret], [vsq], [vsq_m], [n.max(initial=0)], "vmax_sq", None, tag)
             assert np.array_equal(post["vel"].view(np.uint32), pre["vel"].view(np.uint32)), tag + ": the non-pressure pass changed v"
         elif name in ("predict", "predict_iteration"):
             dt = float(op[1])
-            acc = ref.nonpressure(X, pre["vel"], pre["density"], sl, float(op[2]))  # the state of the non-pressure pass, unchanged
+            # (the state of the non-pressure pass, unchanged)
+            acc = ref.nonpressure(X, pre["vel"], pre["density"], sl, float(op[2]), model)
             vs, vs_m = ref.predict(pre["vel"][r], acc[0], acc[1], dt)
             if name == "predict":
                 bounds.check("predict", post["vel"][r], vs, vs_m, n, "predict", ids, tag)
@@ -364,9 +379,9 @@ class AlphaWithoutMass(Restatement):
 class DensityErrorWithDtPrev(Restatement):
     """dt_prev in place of dt in compute_density_error"""
 
-    def nonpressure(self, X, V, rho, sl, dt_prev):
+    def nonpressure(self, X, V, rho, sl, dt_prev, model=None):
         self.dt_prev = dt_prev
-        return super().nonpressure(X, V, rho, sl, dt_prev)
+        return super().nonpressure(X, V, rho, sl, dt_prev, model)
 
     def compute_density_error(self, X, V, rho, sl, dt):
         return super().compute_density_error(X, V, rho, sl, self.dt_prev)
@@ -423,8 +438,7 @@ MUTANTS = [DropLastEntry, BoundaryScaled, AlphaWithoutMass, DensityErrorWithDtPr
 def mutant(cls, params=None, particle_density=PARTICLE_DENSITY):
     import yasph2d_amd as y
 
-    p = y.default_params() if params is None else params
-    return cls(p.smoothing_length, p.fluid_density, particle_density, tuple(p.gravity))
+    return cls.from_params(y.default_params() if params is None else params, particle_density)
 
 
 # ------------------------------------------------------------------------------------------------------------------ whole steps

@@ -1,4 +1,5 @@
-"""A float64 restatement of the reference DFSPH step, written from the yasph2d Rust sources alone.
+"""A float64 restatement of the reference DFSPH and WCSPH steps and of both viscosity models, written from the yasph2d Rust
+sources alone.
 
 Every function below names the lines of the reference it restates (paths relative to yasph2d's `src/sph/`).  It is plain numpy in
 float64 and shares no code with the oracle or the HIP kernels: the inputs are the fp32 state of an implementation (positions,
@@ -12,9 +13,10 @@ operand size enters to first order: k d^(k-1) |dq| is the rounding of d^k when q
 exact zero).  An fp32 evaluation of the expression in any order then lies within a few units of 2^-24 M per term of its sum;
 `tests/dfsph_lockstep.py` turns that into the bound it asserts.
 
-Only four inputs are taken from the library's parameters: the smoothing length, the fluid density, the particle density and gravity
-(all fp32).  The kernel normalisers, the particle mass and the radius are derived here in float64 from the Rust formulas, so a wrong
-constant in an implementation shows up as a mismatch.
+Only these inputs are taken from the library's parameters: the smoothing length, the fluid density, the particle density, gravity
+and the viscosity model with its coefficient (all fp32).  The kernel normalisers (Wendland, Poly6, Spiky and its gradient, the
+viscosity kernel's Laplacian), the particle mass, the radius, the WCSPH stiffness and its boundary force factor are derived here in
+float64 from the Rust formulas, so a wrong constant in an implementation shows up as a mismatch.
 """
 import numpy as np
 
@@ -26,6 +28,10 @@ MIN_NEIGHBORS = 9             # dfsph.rs:261, "particle deficiency"
 MIN_DISTANCE_SQ = 1.0e-10     # neighborhood_search.rs:323
 MAX_NUM_NEIGHBORS = 64        # neighborhood_search.rs:322
 XSPH_EPSILON = 0.05           # viscositymodel/xsph.rs:14
+FLUID_VISCOSITY = 1.0016 / 1000.0  # viscositymodel/physical.rs:14
+DIVISION_EPSILON = 1.0e-10    # smoothing_kernel/kernel.rs:9
+TAIT_EQUATION_GAMMA = 7       # solver/wscsph.rs:26
+XSPH, PHYSICAL = "xsph", "physical"
 
 KERNEL_WENDLAND, KERNEL_POLY6, KERNEL_SPIKY = 0, 1, 2
 U = 2.0 ** -24
@@ -75,9 +81,12 @@ class Slots:
 
 
 class Restatement:
-    """The reference DFSPHSolver<XSPHViscosityModel> + FluidParticleWorld routines, one method per routine."""
+    """The reference DFSPHSolver / WCSPHSolver<XSPHViscosityModel | PhysicalViscosityModel> + FluidParticleWorld routines, one
+    method per routine.  model: ("xsph", epsilon) or ("physical", mu)."""
 
-    def __init__(self, smoothing_length, fluid_density, particle_density, gravity):
+    def __init__(self, smoothing_length, fluid_density, particle_density, gravity, model=(XSPH, XSPH_EPSILON)):
+        assert model[0] in (XSPH, PHYSICAL), model
+        self.model = (model[0], float(np.float32(model[1])))
         self.h = float(np.float32(smoothing_length))
         self.rho0 = float(np.float32(fluid_density))
         self.particle_density = float(np.float32(particle_density))
@@ -91,12 +100,23 @@ class Restatement:
         self.wendland_grad_norm = 140.0 / (np.pi * h ** 4)
         self.poly6_norm = 4.0 / (np.pi * h ** 8)
         self.spiky_norm = 10.0 / (np.pi * h ** 5)
+        self.spiky_grad_norm = 30.0 / (np.pi * h ** 5)           # spiky.rs:21
+        self.viscosity_laplacian_norm = 360.0 / (29.0 * np.pi * h ** 5)  # viscosity.rs:24
+        # solver/wscsph.rs:34,39,47-48: new() calls set_compressibility(eta = 0.01, expected max flow speed 1)
+        self.boundary_force_factor = 1.0
+        self.set_compressibility(0.01, 1.0)
+
+    def set_compressibility(self, target_density_variation, expected_max_flow_speed):
+        """wscsph.rs:45-49: c = v_max / sqrt(eta), B = rho0 c c / gamma."""
+        self.speed_of_sound = expected_max_flow_speed / np.sqrt(target_density_variation)
+        self.stiffness = self.rho0 * self.speed_of_sound * self.speed_of_sound / TAIT_EQUATION_GAMMA
 
     @classmethod
     def from_params(cls, params, particle_density):
-        """params: the library's parameter block (smoothing_length, fluid_density, gravity); particle_density: the value it was made
-        with (the block does not carry it)."""
-        return cls(params.smoothing_length, params.fluid_density, particle_density, tuple(params.gravity))
+        """params: the library's parameter block (smoothing_length, fluid_density, gravity, viscosity_model, fluid_viscosity,
+        xsph_epsilon); particle_density: the value it was made with (the block does not carry it)."""
+        model = (PHYSICAL, params.fluid_viscosity) if int(params.viscosity_model) == 1 else (XSPH, params.xsph_epsilon)
+        return cls(params.smoothing_length, params.fluid_density, particle_density, tuple(params.gravity), model)
 
     # ---- neighbour lists -------------------------------------------------------------------------------------------------------
     def slots(self, counts, lists, n_fluid, rows=None):
@@ -130,6 +150,26 @@ class Restatement:
         """spiky.rs:24-28: n max(h - r, 0)^3."""
         p, p_m = power_of_difference(np.maximum(self.h - r, 0.0), self.h + r, 3)
         return self.spiky_norm * p, self.spiky_norm * p_m
+
+    def spiky_gradient(self, ri_to_rj, r):
+        """spiky.rs:34-37 with kernel.rs:9: n_grad max(h - r, 0)^2 / (r + 1e-10) ri_to_rj."""
+        p, p_m = power_of_difference(np.maximum(self.h - r, 0.0), self.h + r, 2)
+        s = self.spiky_grad_norm / self.divided_distance(r)
+        return (s * p)[..., None] * ri_to_rj * self.spiky_gradient_sign(), s * p_m * r
+
+    def divided_distance(self, r):
+        """The divisor of the Spiky gradient (spiky.rs:36): r + DIVISION_EPSILON."""
+        return r + DIVISION_EPSILON
+
+    def spiky_gradient_sign(self):
+        """+1: the gradient points along ri_to_rj as spiky.rs:36 writes it (no minus sign; the solver's is in wscsph.rs:100)."""
+        return 1.0
+
+    def viscosity_laplacian(self, r):
+        """viscosity.rs:45-47: n_lap (h - r), with no test of r < h: slightly negative for a list member whose float64 distance
+        lies beyond h."""
+        d, d_m = power_of_difference(self.h - r, self.h + r, 1)
+        return self.viscosity_laplacian_norm * d, self.viscosity_laplacian_norm * d_m
 
     def evaluate(self, kind, r_sq, r):
         if kind == KERNEL_WENDLAND:
@@ -179,20 +219,51 @@ class Restatement:
         alpha = 1.0 / dc
         return alpha, denom_m / (dc * dc) + alpha
 
-    def nonpressure(self, X, V, rho, sl, dt_prev):
-        """dfsph.rs:436-469 with xsph.rs:21-23: a_i = g + sum_dyn eps m W_poly6(r_ij^2) / (rho_j dt_prev) (v_j - v_i); the viscosity
-        loop visits the dynamic neighbours only, and the model is called with the step length of the previous step."""
-        V, rho = f64(V), f64(rho)
-        w, w_m = self.pair_kernel(X, sl, KERNEL_POLY6)
-        w, w_m = w * sl.dyn, w_m * sl.dyn
-        rho_j = np.where(sl.dyn, rho[np.where(sl.dyn, sl.j, 0)], 1.0)
-        f = XSPH_EPSILON * self.mass * w / (rho_j * dt_prev)
-        f_m = XSPH_EPSILON * self.mass * w_m / (rho_j * dt_prev)
+    def viscous_factor(self, model, X, rho, sl, dt, mask):
+        """compute_viscous_accelleration without its velocity difference, per slot of `mask`, and its magnitude.
+        xsph.rs:21-23: epsilon m W_poly6(r^2) / (rho_j dt); physical.rs:21-23: mu m laplacian(r) / rho_j, no dt."""
+        kind, coef = model
+        _, r_sq, r = self.pair_vectors(X, sl)
+        rho_j = self.viscous_density(rho, sl, mask)
+        if kind == PHYSICAL:
+            w, w_m = self.viscosity_laplacian(r)
+            f, f_m = coef * self.mass * w / rho_j, abs(coef) * self.mass * w_m / rho_j
+            f, f_m = self.physical_time_scale(f, f_m, dt)
+        else:
+            w, w_m = self.poly6_evaluate(r_sq)
+            f, f_m = coef * self.mass * w / (rho_j * dt), abs(coef) * self.mass * w_m / (rho_j * dt)
+        return f * mask, f_m * mask
+
+    def viscous_density(self, rho, sl, mask):
+        """rhoj of compute_viscous_accelleration: the NEIGHBOUR's density (dfsph.rs:457-466, wscsph.rs:103-105)."""
+        return np.where(mask, f64(rho)[np.where(mask, sl.j, 0)], 1.0)
+
+    def physical_time_scale(self, f, f_m, dt):
+        """physical.rs:21: `_dt` is unused."""
+        return f, f_m
+
+    def viscous_mask(self, sl):
+        """The viscosity loops visit neighbors_dynamic only (dfsph.rs:449, wscsph.rs:89)."""
+        return sl.dyn
+
+    def viscous_sum(self, model, X, V, rho, sl, dt):
+        """sum over the visited neighbours of factor (v_j - v_i); a static neighbour (only a mutant visits one) has v_j = 0."""
+        V = f64(V)
+        mask = self.viscous_mask(sl)
+        if not np.array_equal(mask, sl.dyn):  # a mutant's static visit: boundary particles carry no density; rho0 stands in
+            rho = np.concatenate([f64(rho), np.full(len(X) - len(rho), self.rho0)])
+            V = np.concatenate([V, np.zeros((len(X) - len(V), 2))])
+        f, f_m = self.viscous_factor(model, X, rho, sl, dt, mask)
         vi = V[sl.rows]
-        vj = V[np.where(sl.dyn, sl.j, 0)]
-        acc = self.gravity + (f[..., None] * (vj - vi[:, None, :])).sum(1)
-        acc_m = norm(self.gravity) + (f_m * (norm(vj) + norm(vi)[:, None])).sum(1)
-        return acc, acc_m
+        vj = V[np.where(mask, sl.j, 0)]
+        return (f[..., None] * (vj - vi[:, None, :])).sum(1), (f_m * (norm(vj) + norm(vi)[:, None])).sum(1)
+
+    def nonpressure(self, X, V, rho, sl, dt_prev, model=None):
+        """dfsph.rs:436-469 with xsph.rs:21-23 or physical.rs:21-23: a_i = g + sum_dyn factor_ij (v_j - v_i); the viscosity loop
+        visits the dynamic neighbours only, and the model is called with the step length of the previous step.
+        model: ("xsph", epsilon) or ("physical", mu); None: the one the restatement was made with."""
+        a, a_m = self.viscous_sum(self.model if model is None else model, X, V, rho, sl, dt_prev)
+        return self.gravity + a, norm(self.gravity) + a_m
 
     def max_velocity_sq(self, V, acc, acc_m, dt_prev):
         """dfsph.rs:474-477: max |v + a dt_prev|^2 (the viscosity pass ran with dt_prev, so does this)."""
@@ -273,6 +344,79 @@ class Restatement:
     def advect(self, X, V, dt):
         """dfsph.rs:499-510: x += v* dt."""
         return f64(X) + f64(V) * dt, norm(f64(X)) + norm(f64(V)) * dt
+
+    # ---- WCSPHSolver -------------------------------------------------------------------------------------------------------------
+    def tait_exponent(self):
+        return TAIT_EQUATION_GAMMA
+
+    def pressure(self, rho):
+        """wscsph.rs:52-57: B (max(rho / rho0, 1)^7 - 1).  Magnitude: a^7 is seven factors that each carry a's relative error, and
+        the subtraction of 1 cancels at a = 1: B (7 a^7 + 1)."""
+        g = self.tait_exponent()
+        a = np.maximum(f64(rho) / self.rho0, 1.0) ** g
+        return self.stiffness * (a - 1.0), self.stiffness * (g * a + 1.0)
+
+    def pressure_pair(self, p_i, p_j, rho_i, rho_j):
+        """wscsph.rs:100: -m (p_i + p_j) / (2 rho_i rho_j) (linear in the pressures: the magnitudes go through the same form)."""
+        return -self.mass * (p_i + p_j) / (2.0 * rho_i * rho_j)
+
+    def boundary_force(self, d, r_sq, r):
+        """wscsph.rs:112-116: per static neighbour -f_b W_spiky(r) / r^2 ri_to_rj -> (vector, magnitude)."""
+        w, w_m = self.spiky_evaluate(r)
+        rs = np.where(r_sq > 0, r_sq, 1.0)
+        return -(self.boundary_force_factor * w / rs)[..., None] * d, self.boundary_force_factor * w_m / rs * r
+
+    def update_accellerations(self, X, V, rho, sl, dt, model=None):
+        """wscsph.rs:59-118: a_i = g + sum_dyn (-m (p_i + p_j) / (2 rho_i rho_j) grad W_spiky(ri_to_rj) + viscous term with this
+        step's dt) + sum_static (-f_b W_spiky(r) / r^2 ri_to_rj)."""
+        rho = f64(rho)
+        d, r_sq, r = self.pair_vectors(X, sl)
+        p, p_m = self.pressure(rho)
+        jd = np.where(sl.dyn, sl.j, 0)
+        rho_i = rho[sl.rows][:, None]
+        pu = self.pressure_pair(p[sl.rows][:, None], p[jd], rho_i, rho[jd]) * sl.dyn
+        pu_m = -self.pressure_pair(p_m[sl.rows][:, None], p_m[jd], rho_i, rho[jd]) * sl.dyn
+        g, g_m = self.spiky_gradient(d, r)
+        acc = (pu[..., None] * g).sum(1)
+        acc_m = (np.abs(pu_m) * g_m).sum(1)
+        a, a_m = self.viscous_sum(self.model if model is None else model, X, V, rho, sl, dt)
+        b, b_m = self.boundary_force(d, r_sq, r)
+        acc = self.gravity + acc + a + (b * sl.stat[..., None]).sum(1)
+        acc_m = norm(self.gravity) + acc_m + a_m + (b_m * sl.stat).sum(1)
+        return acc, acc_m
+
+    def leap_frog_1(self, X, V, A, dt):
+        """wscsph.rs:141-150: v += 0.5 dt a; x += v dt (a: the previous step's accelerations, slot by slot).
+        -> (x, M, v, M)"""
+        X, V, A = f64(X), f64(V), f64(A)
+        v, v_m = V + self.half_kick(dt) * A, norm(V) + self.half_kick(dt) * norm(A)
+        return X + v * dt, norm(X) + v_m * dt, v, v_m
+
+    def half_kick(self, dt):
+        return 0.5 * dt
+
+    def previous_accellerations(self, accel, n_held, n):
+        """wscsph.rs:122-124, :128: `accellerations` is slot-bound; clear_cached_data empties it, resize(n, zero) cuts it to n
+        slots or fills up with zeros.  accel: what an implementation holds; n_held: how many slots of it the solver held."""
+        out = np.zeros((n, 2))
+        k = min(n_held, n)
+        out[:k] = f64(accel).reshape(-1, 2)[:k]
+        return out
+
+    def wcsph_max_velocity_sq(self, V, acc, acc_m, dt):
+        """wscsph.rs:160-163: max |v + a dt|^2 with the step's own dt (before the timer changes it)."""
+        return self.max_velocity_sq(V, acc, acc_m, self.vmax_dt(dt))
+
+    def vmax_dt(self, dt):
+        return dt
+
+    def leap_frog_2(self, V, acc, acc_m, dt, dt_new):
+        """wscsph.rs:164-177: v += 0.5 dt a with the dt the timer just returned."""
+        k = self.half_kick_2(dt, dt_new)
+        return f64(V) + k * acc, norm(f64(V)) + k * acc_m
+
+    def half_kick_2(self, dt, dt_new):
+        return 0.5 * dt_new
 
     # ---- loop control ------------------------------------------------------------------------------------------------------------
     def average_density_error(self, e):

@@ -883,6 +883,14 @@ class SphxContext:
         self._chk(self.L.sphx_debug_download_accel(self.h, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def download_wcsph_half_step(self):
+        """sphx_debug_download_wcsph_half_step -> download()'s dictionary between wcsph_step_begin and wcsph_step_finish: the
+        leap-frogged positions, the velocities at the half step, the Poly6 densities and the ids (sorted order)."""
+        n = self.n
+        out = dict(pos=np.zeros((n, 2), np.float32), vel=np.zeros((n, 2), np.float32), density=np.zeros(n, np.float32), ids=np.zeros(n, np.uint32))
+        self._chk(self.L.sphx_debug_download_wcsph_half_step(self.h, _p(out["pos"]), _p(out["vel"]), _p(out["density"]), _p(out["ids"])))
+        return out
+
     def grid_info(self, which=0):
         """Cell table behind the grid: covered blocks, table entries, directory extent (sphx_grid_info)."""
         out = (C.c_uint32 * 4)()

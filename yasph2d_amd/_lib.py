@@ -340,6 +340,7 @@ SIGNATURES = {
     "sphx_debug_rigid_counts": (_i, [_vp, _vp]),
     "sphx_debug_rigid_predict_counts": (_i, [_vp, _vp]),
     "sphx_debug_download_accel": (_i, [_vp, _vp]),
+    "sphx_debug_download_wcsph_half_step": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "sphx_download_by_id": (_i, [_vp, _u32, _u32, _u32, C.POINTER(SphxTrackOut), C.POINTER(_u32)]),
     "sphx_download": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "sphx_download_boundary": (_i, [_vp, _vp, _vp]),

@@ -2293,9 +2293,7 @@ int sphx_view_fetch(sphx_ctx* c, int wait, const float** out_xys, uint32_t* out_
     return SPHX_OK;
 }
 
-int sphx_download(sphx_ctx* c, float* pos_xy, float* vel_xy, float* density, uint32_t* particle_id) {
-    if (!c) return SPHX_ERR_INVALID_ARGUMENT;
-    if (c->in_step) return c->fail(SPHX_ERR_NOT_READY, "sphx_download between step_begin and step_finish");
+static int download_particles(sphx_ctx* c, float* pos_xy, float* vel_xy, float* density, uint32_t* particle_id) {
     SPHX_HIP(c, hipSetDevice(c->device));
     flush_pending_advect(c);
     const size_t n = c->N;
@@ -2307,6 +2305,21 @@ int sphx_download(sphx_ctx* c, float* pos_xy, float* vel_xy, float* density, uin
     }
     SPHX_HIP(c, hipStreamSynchronize(c->stream));
     return SPHX_OK;
+}
+
+int sphx_download(sphx_ctx* c, float* pos_xy, float* vel_xy, float* density, uint32_t* particle_id) {
+    if (!c) return SPHX_ERR_INVALID_ARGUMENT;
+    if (c->in_step) return c->fail(SPHX_ERR_NOT_READY, "sphx_download between step_begin and step_finish");
+    return download_particles(c, pos_xy, vel_xy, density, particle_id);
+}
+
+// (between the two phases of a WCSPH step nothing is queued: sphx_wcsph_step_begin has waited for its last kernel, and
+// sphx_wcsph_step_finish changes the velocities alone)
+int sphx_debug_download_wcsph_half_step(sphx_ctx* c, float* pos_xy, float* vel_xy, float* density, uint32_t* particle_id) {
+    if (!c) return SPHX_ERR_INVALID_ARGUMENT;
+    if (!c->in_step || !c->in_wcsph)
+        return c->fail(SPHX_ERR_NOT_READY, "sphx_debug_download_wcsph_half_step outside sphx_wcsph_step_begin .. sphx_wcsph_step_finish");
+    return download_particles(c, pos_xy, vel_xy, density, particle_id);
 }
 
 int sphx_download_boundary(sphx_ctx* c, float* xy, uint32_t* boundary_id) {
