@@ -86,3 +86,49 @@ def scene(name, n=STEP_N, seed=0, velocity_scale=0.5, jitter=0.03, origin=ORIGIN
     cols = np.arange(-4, side + 4, dtype=np.float32)
     boundary = np.concatenate([np.stack([o[0] + cols * s, np.full_like(cols, o[1] - np.float32(1 + row) * s)], -1) for row in range(3)])
     return pos, vel, boundary.astype(np.float32).reshape(-1, 2)
+
+
+TILED_N = 6000                    # the tiled scene's block
+TILED_DRIFT = (1500.0, 900.0)     # spacings per second: the block crosses cell columns and rows within ten steps
+TILED_STEPS = 10
+TILED_HALO = 8
+
+
+def tiled_scene(name, n=TILED_N, drift=TILED_DRIFT, seed=0):
+    """scene(name, n) with a uniform drift velocity (in spacings per second) on top of the seeded one, so that particles change tile
+    within a ten-step run.  -> (positions, velocities, boundary), fp32."""
+    pos, vel, boundary = scene(name, n, seed=seed)
+    vel = (vel + (np.array(drift, np.float32) * spacing(name)).astype(np.float32)).astype(np.float32)
+    return pos, vel, boundary
+
+
+def cells(name, xy):
+    """Cell coordinates of positions under the set's own constants: sat_u16((p - grid_min) * fl(1 / h)) per axis, int64 [n, 2]."""
+    gm, inv = np.array(_set(name)[4], np.float32), np.float32(1.0) / properties(name)["smoothing_length"]
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = ((np.asarray(xy, np.float32) - gm).astype(np.float32) * inv).astype(np.float32)
+    return np.fmin(np.fmax(v, np.float32(0.0)), np.float32(65535.0)).astype(np.int64)
+
+
+def tile_cuts(name, pos):
+    """A 2 x 2 layout of the set's cell grid: the x-cut at the 40 % quantile of the particles' cell columns, every column cut again at
+    the median of its own cell rows.  -> (xcuts [3], ycuts [2][3])."""
+    c = cells(name, pos)
+    xcuts = [0, int(np.sort(c[:, 0])[int(0.4 * len(c))]), 65536]
+    ycuts = []
+    for ix in range(2):
+        col = c[(c[:, 0] >= xcuts[ix]) & (c[:, 0] < xcuts[ix + 1]), 1]
+        ycuts.append([0, int(np.sort(col)[len(col) // 2]), 65536])
+    return xcuts, ycuts
+
+
+def tile_rects(xcuts, ycuts):
+    """The rectangles (x0, x1, y0, y1) of tile_cuts' layout in rank order ix * 2 + iy, as MultiSolver.tile_rects() reports them."""
+    return np.array([(xcuts[ix], xcuts[ix + 1], ycuts[ix][iy], ycuts[ix][iy + 1]) for ix in range(2) for iy in range(2)], np.int64)
+
+
+def owner(rects, c):
+    """The tile whose rectangle holds each cell of c [n, 2]; exactly one does."""
+    inside = np.stack([(c[:, 0] >= r[0]) & (c[:, 0] < r[1]) & (c[:, 1] >= r[2]) & (c[:, 1] < r[3]) for r in np.asarray(rects).tolist()], 0)
+    assert (inside.sum(0) == 1).all(), "the rectangles do not partition the cell domain"
+    return inside.argmax(0).astype(np.int32)

@@ -6,6 +6,8 @@
 //   contour_merge_driver apron   -> "ok <cases>": windows of 2 strips in x, 3 strips in y and a 2 x 2 grid with its own y cuts per column,
 //                                   over fine, coarse and one-node-wide lattices: every apron node is found in exactly one border and
 //                                   carries that node's word; a window taken away or doubled is reported
+//   contour_merge_driver apron <gmin.x> <gmin.y> <h>   the same on another cell grid (fp32 bit patterns, hex): the lattices keep their place
+//                                   and spacing in cells (cell 5000 is where x = 0 lay), the cuts stay the cell indices they are
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -116,17 +118,30 @@ struct LatticeCase {
     uint32_t nx, ny;
 };
 
-static const float GMIN = -100.0f, H = 0.02f;
-static const float CELL_INV = 1.0f / H;
+static float GMIN[2] = {-100.0f, -100.0f}, H = 0.02f;
+static float CELL_INV = 1.0f / H;
+static bool g_other_grid = false;
+
+static float from_bits(const char* hex) {
+    const uint32_t u = (uint32_t)std::strtoul(hex, nullptr, 16);
+    float f;
+    std::memcpy(&f, &u, sizeof(f));
+    return f;
+}
+
+// a lattice written down for grid_min (-100, -100), h = 0.02, moved to the grid in use: the same cells, the same spacing in cells
+static float moved(float v, int axis) { return g_other_grid ? GMIN[axis] + (5000.0f + v / 0.02f) * H : v; }
+static float scaled(float d) { return g_other_grid ? d / 0.02f * H : d; }
 
 static uint32_t g_reported = 0;  // apron look-ups that named a node of a window taken away
 static uint32_t node_word(uint32_t ix, uint32_t iy) { return 0x40000000u + iy * 4099u + ix; }
 
-static int check_layout(const char* lname, const std::vector<CellRect>& rects, const LatticeCase& L, uint32_t& cases, uint32_t& empty_tiles, uint32_t& apron_nodes) {
+static int check_layout(const char* lname, const std::vector<CellRect>& rects, const LatticeCase& written, uint32_t& cases, uint32_t& empty_tiles, uint32_t& apron_nodes) {
+    const LatticeCase L = {written.name, moved(written.x0, 0), moved(written.y0, 1), scaled(written.dx), scaled(written.dy), written.nx, written.ny};
     const uint32_t n = (uint32_t)rects.size();
     std::vector<ch::Window> wins(n);
     for (uint32_t k = 0; k < n; ++k)
-        wins[k] = sh::lattice_window(L.x0, L.y0, L.dx, L.dy, L.nx, L.ny, GMIN, GMIN, CELL_INV, rects[k].x0, rects[k].x1, rects[k].y0, rects[k].y1);
+        wins[k] = sh::lattice_window(L.x0, L.y0, L.dx, L.dy, L.nx, L.ny, GMIN[0], GMIN[1], CELL_INV, rects[k].x0, rects[k].x1, rects[k].y0, rects[k].y1);
     REQUIRE(ch::windows_cover(wins.data(), n, L.nx, L.ny), "%s / %s: the windows do not cover the lattice", lname, L.name);
     const std::vector<size_t> off = ch::border_offsets(wins.data(), n);
     // the borders as the tiles would pack them, every node carrying its own word
@@ -241,7 +256,12 @@ static int run_apron() {
 int main(int argc, char** argv) {
     const std::string mode = argc > 1 ? argv[1] : "";
     if (mode == "merge") return run_merge();
+    if (mode == "apron" && argc >= 5) {
+        GMIN[0] = from_bits(argv[2]), GMIN[1] = from_bits(argv[3]), H = from_bits(argv[4]);
+        CELL_INV = 1.0f / H;
+        g_other_grid = true;
+    }
     if (mode == "apron") return run_apron();
-    std::fprintf(stderr, "usage: contour_merge_driver merge | apron\n");
+    std::fprintf(stderr, "usage: contour_merge_driver merge | apron [gmin.x gmin.y h as fp32 bit patterns]\n");
     return 2;
 }

@@ -1,8 +1,10 @@
 // multi_edit_driver.cpp — the host rules of an edit of a tiled run (yasph2d_amd/csrc/sphx_multi_edit.hpp) as a stand-alone program: routing
 // of new records to the tiles that own their cells, the id counter, the check of the positions.  Built by tests/test_multi_edit_host.py
 // with the address and undefined-behaviour sanitizers; prints "ok <checks>" or the first failed check.
-//   multi_edit_driver <routing|ids|positions|empty>
+//   multi_edit_driver <routing|ids|positions|empty> [<gmin.x> <gmin.y> <h>]    the grid of the hand cases as fp32 bit patterns (hex);
+//                                                                              default: grid_min (-100, -100), h = 0.02
 //   multi_edit_driver route <gmin> <h> <n_rects> {x0 x1 y0 y1}... {x y}...     -> the owners, one per record (for the numpy restatement)
+//   multi_edit_driver routebits <gmin.x> <gmin.y> <h> <n_rects> {x0 x1 y0 y1}... {x y}...   the same, every float as its fp32 bit pattern
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -25,12 +27,20 @@ static int checks = 0;
         }                                                                  \
     } while (0)
 
-static const float GMIN[2] = {-100.0f, -100.0f};
-static const float H = 0.02f;
-static const float INV = 1.0f / H;
+static float GMIN[2] = {-100.0f, -100.0f};
+static float H = 0.02f;
+static float INV = 1.0f / H;
 
-// the world coordinate of the low edge of cell c, nudged into the cell (fp32 of -100 + c * 0.02 may round to either side)
-static float in_cell(uint32_t c, float frac = 0.5f) { return GMIN[0] + ((float)c + frac) * H; }
+static float from_bits(const char* hex) {
+    const uint32_t u = (uint32_t)std::strtoul(hex, nullptr, 16);
+    float f;
+    std::memcpy(&f, &u, sizeof(f));
+    return f;
+}
+
+// the world coordinate of the low edge of cell c along `axis`, nudged into the cell (fp32 of -100 + c * 0.02 may round to either side)
+static float in_cell(uint32_t c, float frac = 0.5f, int axis = 0) { return GMIN[axis] + ((float)c + frac) * H; }
+static float in_cell_y(uint32_t c, float frac = 0.5f) { return in_cell(c, frac, 1); }
 
 static std::vector<int> owners(const std::vector<float>& xy, const std::vector<me::CellRect>& rects) {
     std::vector<int> o;
@@ -42,8 +52,8 @@ static int routing() {
     // three strips along x cut at cells 5000 and 5040
     const std::vector<me::CellRect> strips = {{0u, 5000u, 0u, 65536u}, {5000u, 5040u, 0u, 65536u}, {5040u, 65536u, 0u, 65536u}};
     {
-        const std::vector<float> xy = {in_cell(4999), in_cell(10), in_cell(5000, 0.01f), in_cell(77), in_cell(5039, 0.99f), in_cell(5040), in_cell(5040, 0.01f), in_cell(0),
-                                       in_cell(65535), in_cell(65535), -1.0e9f, 5.0f, 1.0e9f, -1.0e9f};
+        const std::vector<float> xy = {in_cell(4999), in_cell_y(10), in_cell(5000, 0.01f), in_cell_y(77), in_cell(5039, 0.99f), in_cell_y(5040), in_cell(5040, 0.01f), in_cell_y(0),
+                                       in_cell(65535), in_cell_y(65535), -1.0e9f, 5.0f, 1.0e9f, -1.0e9f};
         const std::vector<int> o = owners(xy, strips);
         CHECK(o.size() == 7);
         CHECK(o[0] == 0);  // the last cell of the first strip
@@ -55,12 +65,13 @@ static int routing() {
         CHECK(o[6] == 2);  // right of it: cell 65535 (x), cell 0 (y)
     }
     // the cell of a position is what the device computes: (v - gmin) * (1 / h) in fp32, truncated
-    for (uint32_t c : {0u, 1u, 4999u, 5000u, 5017u, 65534u, 65535u}) {
-        CHECK(me::cell_coord(in_cell(c), GMIN[0], INV) == c);
-        const float v = in_cell(c);
-        const float f = (v - GMIN[0]) * INV;
-        CHECK(me::cell_coord(v, GMIN[0], INV) == (f >= 65535.0f ? 65535u : (uint32_t)f));
-    }
+    for (int axis = 0; axis < 2; ++axis)
+        for (uint32_t c : {0u, 1u, 4999u, 5000u, 5017u, 65534u, 65535u}) {
+            CHECK(me::cell_coord(in_cell(c, 0.5f, axis), GMIN[axis], INV) == c);
+            const float v = in_cell(c, 0.5f, axis);
+            const float f = (v - GMIN[axis]) * INV;
+            CHECK(me::cell_coord(v, GMIN[axis], INV) == (f >= 65535.0f ? 65535u : (uint32_t)f));
+        }
     CHECK(me::cell_coord(std::numeric_limits<float>::quiet_NaN(), GMIN[0], INV) == 0u);
     CHECK(me::cell_coord(-std::numeric_limits<float>::infinity(), GMIN[0], INV) == 0u);
     CHECK(me::cell_coord(std::numeric_limits<float>::infinity(), GMIN[0], INV) == 65535u);
@@ -77,7 +88,7 @@ static int routing() {
         std::vector<float> xy;
         for (const Case& c : cases) {
             xy.push_back(in_cell(c.cx));
-            xy.push_back(in_cell(c.cy));
+            xy.push_back(in_cell_y(c.cy));
         }
         const std::vector<int> o = owners(xy, grid);
         for (size_t k = 0; k < sizeof(cases) / sizeof(cases[0]); ++k) {
@@ -96,7 +107,7 @@ static int routing() {
     const std::vector<me::CellRect> gap = {{0u, 10u, 0u, 65536u}, {20u, 65536u, 0u, 65536u}};
     CHECK(me::owner_of(15, 3, gap.data(), 2) == -1 && me::owner_of(9, 3, gap.data(), 2) == 0 && me::owner_of(20, 3, gap.data(), 2) == 1);
     {
-        const std::vector<float> xy = {in_cell(15), in_cell(3), in_cell(25), in_cell(3), in_cell(15), in_cell(3)};
+        const std::vector<float> xy = {in_cell(15), in_cell_y(3), in_cell(25), in_cell_y(3), in_cell(15), in_cell_y(3)};
         const std::vector<int> o = owners(xy, gap);
         CHECK(o[0] == -1 && o[1] == 1 && o[2] == -1);  // (the "try the last owner first" shortcut does not adopt a record nobody owns)
     }
@@ -108,7 +119,7 @@ static int routing() {
             s = s * 1664525u + 1013904223u;
             xy.push_back(in_cell(5000u + (s >> 8) % 40u));
             s = s * 1664525u + 1013904223u;
-            xy.push_back(in_cell(5040u + (s >> 8) % 40u));
+            xy.push_back(in_cell_y(5040u + (s >> 8) % 40u));
         }
         const std::vector<int> o = owners(xy, grid);
         for (int k = 0; k < 500; ++k) CHECK(o[k] == me::owner_of(me::cell_coord(xy[2 * k], GMIN[0], INV), me::cell_coord(xy[2 * k + 1], GMIN[1], INV), grid.data(), 4));
@@ -200,6 +211,27 @@ int main(int argc, char** argv) {
         me::route(xy.data(), (uint32_t)(xy.size() / 2), gmin, inv, rects.data(), (int)rects.size(), o);
         for (int v : o) std::printf("%d\n", v);
         return 0;
+    }
+    if (what == "routebits") {
+        if (argc < 6) return 2;
+        const float gmin[2] = {from_bits(argv[2]), from_bits(argv[3])};
+        const float inv = 1.0f / from_bits(argv[4]);
+        const int nr = std::atoi(argv[5]);
+        std::vector<me::CellRect> rects;
+        int at = 6;
+        for (int r = 0; r < nr && at + 3 < argc; ++r, at += 4)
+            rects.push_back(me::CellRect{(uint32_t)std::strtoul(argv[at], nullptr, 10), (uint32_t)std::strtoul(argv[at + 1], nullptr, 10),
+                                         (uint32_t)std::strtoul(argv[at + 2], nullptr, 10), (uint32_t)std::strtoul(argv[at + 3], nullptr, 10)});
+        std::vector<float> xy;
+        for (; at < argc; ++at) xy.push_back(from_bits(argv[at]));
+        std::vector<int> o;
+        me::route(xy.data(), (uint32_t)(xy.size() / 2), gmin, inv, rects.data(), (int)rects.size(), o);
+        for (int v : o) std::printf("%d\n", v);
+        return 0;
+    }
+    if (argc >= 5) {  // the grid of the hand cases
+        GMIN[0] = from_bits(argv[2]), GMIN[1] = from_bits(argv[3]), H = from_bits(argv[4]);
+        INV = 1.0f / H;
     }
     int rc = 2;
     if (what == "routing") rc = routing();

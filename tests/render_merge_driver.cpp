@@ -7,6 +7,8 @@
 //   render_merge_driver window   a window never leaves the image whatever the camera and the rectangle (+-1e30, NaN, +-inf, 1 x 1 and
 //                                odd images, rectangles touching 0 and 65536), and every pixel a particle of the rectangle's cells
 //                                covers lies inside it
+//   render_merge_driver window <gmin.x> <gmin.y> <h>   the coverage section on another cell grid (fp32 bit patterns, hex): the cameras
+//                                as they are, and once more with their lengths scaled by h / 0.02
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -170,6 +172,73 @@ uint32_t cell_coord(float v, float gmin, float cell_inv) {  // the grid's fp32 c
     return (uint32_t)c;
 }
 
+float from_bits(const char* hex) {
+    const uint32_t u = (uint32_t)std::strtoul(hex, nullptr, 16);
+    float f;
+    std::memcpy(&f, &u, sizeof(f));
+    return f;
+}
+
+struct Cam {
+    uint32_t w, h;
+    float cx, cy, ppu, r;
+};
+
+// nothing is lost: every pixel a particle covers (the contract's own fp32 test) lies in the window of every rectangle holding the
+// particle's cell; particles far outside the domain land in the saturated cells of an outer rectangle
+uint64_t check_coverage(const float gmin[2], float cell_inv, float particle_radius, const Cam* cams, size_t n_cams, uint32_t seed) {
+    using namespace sphx;
+    std::mt19937 g(seed);
+    std::uniform_real_distribution<float> u(0.0f, 1.0f);
+    uint64_t covered = 0;
+    for (size_t i = 0; i < n_cams; ++i) {
+        const Cam& c = cams[i];
+        sphx_render_view view;
+        std::memset(&view, 0, sizeof(view));
+        view.width = c.w, view.height = c.h, view.center[0] = c.cx, view.center[1] = c.cy, view.pixel_per_world_unit = c.ppu, view.radius = c.r;
+        CHECK(!render_view_error(&view, 10.0f * particle_radius), "a good view is refused");
+        const RenderCam v = render_make_cam(view, particle_radius);
+        const float spanx = (float)c.w / c.ppu, spany = (float)c.h / c.ppu;
+        for (int k = 0; k < 4000; ++k) {
+            float px = c.cx + (u(g) - 0.5f) * spanx * 1.3f, py = c.cy + (u(g) - 0.5f) * spany * 1.3f;
+            if (k % 50 == 0) px = -1e6f * u(g);  // far outside the domain: cell 0
+            if (k % 50 == 1) py = 1e6f * u(g);   // ... cell 65535
+            const uint32_t cx = cell_coord(px, gmin[0], cell_inv), cy = cell_coord(py, gmin[1], cell_inv);
+            // rectangles holding the cell: a thin one with the cell at either edge, strips cut right at the cell, the cell alone
+            const uint32_t rs[][4] = {{cx, cx + 1, cy, cy + 1}, {0, cx + 1, 0, 65536}, {cx, 65536, 0, 65536}, {0, 65536, 0, cy + 1}, {0, 65536, cy, 65536}};
+            const RenderRect pr = render_pixel_rect(v, px, py);
+            for (const auto& rc : rs) {
+                const RenderWindow w = render_tile_window(v, rc[0], rc[1], rc[2], rc[3], gmin[0], gmin[1], cell_inv);
+                for (uint32_t iy = pr.y0; iy < pr.y1; ++iy)
+                    for (uint32_t ix = pr.x0; ix < pr.x1; ++ix)
+                        if (render_covers(v, px, py, render_qx(v, ix), render_qy(v, iy))) {
+                            ++covered;
+                            CHECK(ix >= w.x0 && ix < w.x1 && iy >= w.y0 && iy < w.y1, "particle (%g, %g) of cell (%u, %u) covers pixel (%u, %u) outside the window [%u,%u)x[%u,%u)",
+                                  px, py, cx, cy, ix, iy, w.x0, w.x1, w.y0, w.y1);
+                        }
+            }
+        }
+    }
+    return covered;
+}
+
+const Cam CAMS[] = {{320, 240, 0.95f, 0.7f, 145.45454f, 0.015f}, {320, 240, 0.95f, 0.7f, 145.45454f, 0.005f}, {37, 23, 0.4f, 0.3f, 30.0f, 0.02f},
+                    {160, 120, 0.35f, 0.5f, 2000.0f, 0.02f},    {1, 1, 0.34f, 0.5f, 40.0f, 0.02f},          {64, 48, 0.95f, 0.7f, 20.0f, 0.0375f},
+                    {200, 100, -120.0f, 0.5f, 4.0f, 0.02f},     {101, 99, 1300.0f, 1250.0f, 0.5f, 0.02f}};
+constexpr size_t N_CAMS = sizeof(CAMS) / sizeof(CAMS[0]);
+
+// the coverage section on the cell grid (gmin, h) of the command line: the cameras as they are (cells of another size under the same
+// discs), then with every length scaled by h / 0.02 (the same picture in cells), the particle radius h / 4 as at smoothing factor 2
+void check_window_at(const float gmin[2], float h) {
+    const float cell_inv = 1.0f / h, s = h / 0.02f;
+    uint64_t covered = check_coverage(gmin, cell_inv, 0.005f, CAMS, N_CAMS, 777);
+    Cam scaled_cams[N_CAMS];
+    for (size_t i = 0; i < N_CAMS; ++i) scaled_cams[i] = Cam{CAMS[i].w, CAMS[i].h, CAMS[i].cx * s, CAMS[i].cy * s, CAMS[i].ppu / s, CAMS[i].r * s};
+    covered += check_coverage(gmin, cell_inv, 0.25f * h, scaled_cams, N_CAMS, 778);
+    CHECK(covered > 200000, "the scenes cover too few pixels (%llu)", (unsigned long long)covered);
+    std::printf("window: %llu covered pixels inside their windows at grid_min (%g, %g), h %.9g\n", (unsigned long long)covered, gmin[0], gmin[1], h);
+}
+
 void check_window() {
     using namespace sphx;
     const float inf = std::numeric_limits<float>::infinity(), nan = std::numeric_limits<float>::quiet_NaN();
@@ -203,45 +272,8 @@ void check_window() {
         }
     std::printf("window: %llu windows inside their images\n", (unsigned long long)n);
 
-    // nothing is lost: every pixel a particle covers (the contract's own fp32 test) lies in the window of every rectangle holding the
-    // particle's cell; particles far outside the domain land in the saturated cells of an outer rectangle
-    std::mt19937 g(777);
-    std::uniform_real_distribution<float> u(0.0f, 1.0f);
-    struct Cam {
-        uint32_t w, h;
-        float cx, cy, ppu, r;
-    };
-    const Cam cams[] = {{320, 240, 0.95f, 0.7f, 145.45454f, 0.015f}, {320, 240, 0.95f, 0.7f, 145.45454f, 0.005f}, {37, 23, 0.4f, 0.3f, 30.0f, 0.02f},
-                        {160, 120, 0.35f, 0.5f, 2000.0f, 0.02f},    {1, 1, 0.34f, 0.5f, 40.0f, 0.02f},          {64, 48, 0.95f, 0.7f, 20.0f, 0.0375f},
-                        {200, 100, -120.0f, 0.5f, 4.0f, 0.02f},     {101, 99, 1300.0f, 1250.0f, 0.5f, 0.02f}};
-    uint64_t covered = 0;
-    for (const Cam& c : cams) {
-        sphx_render_view view;
-        std::memset(&view, 0, sizeof(view));
-        view.width = c.w, view.height = c.h, view.center[0] = c.cx, view.center[1] = c.cy, view.pixel_per_world_unit = c.ppu, view.radius = c.r;
-        CHECK(!render_view_error(&view, 0.05f), "a good view is refused");
-        const RenderCam v = render_make_cam(view, 0.005f);
-        const float spanx = (float)c.w / c.ppu, spany = (float)c.h / c.ppu;
-        for (int k = 0; k < 4000; ++k) {
-            float px = c.cx + (u(g) - 0.5f) * spanx * 1.3f, py = c.cy + (u(g) - 0.5f) * spany * 1.3f;
-            if (k % 50 == 0) px = -1e6f * u(g);  // far outside the domain: cell 0
-            if (k % 50 == 1) py = 1e6f * u(g);   // ... cell 65535
-            const uint32_t cx = cell_coord(px, gmin, cell_inv), cy = cell_coord(py, gmin, cell_inv);
-            // rectangles holding the cell: a thin one with the cell at either edge, strips cut right at the cell, the cell alone
-            const uint32_t rs[][4] = {{cx, cx + 1, cy, cy + 1}, {0, cx + 1, 0, 65536}, {cx, 65536, 0, 65536}, {0, 65536, 0, cy + 1}, {0, 65536, cy, 65536}};
-            const RenderRect pr = render_pixel_rect(v, px, py);
-            for (const auto& rc : rs) {
-                const RenderWindow w = render_tile_window(v, rc[0], rc[1], rc[2], rc[3], gmin, gmin, cell_inv);
-                for (uint32_t iy = pr.y0; iy < pr.y1; ++iy)
-                    for (uint32_t ix = pr.x0; ix < pr.x1; ++ix)
-                        if (render_covers(v, px, py, render_qx(v, ix), render_qy(v, iy))) {
-                            ++covered;
-                            CHECK(ix >= w.x0 && ix < w.x1 && iy >= w.y0 && iy < w.y1, "particle (%g, %g) of cell (%u, %u) covers pixel (%u, %u) outside the window [%u,%u)x[%u,%u)",
-                                  px, py, cx, cy, ix, iy, w.x0, w.x1, w.y0, w.y1);
-                        }
-            }
-        }
-    }
+    const float gmin2[2] = {gmin, gmin};
+    const uint64_t covered = check_coverage(gmin2, cell_inv, 0.005f, CAMS, N_CAMS, 777);
     CHECK(covered > 100000, "the scenes cover too few pixels (%llu)", (unsigned long long)covered);
     std::printf("window: %llu covered pixels inside their windows\n", (unsigned long long)covered);
     // a window is not the whole image where it need not be: a strip's window ends near the cut
@@ -263,10 +295,13 @@ int main(int argc, char** argv) {
     const std::string what = argc > 1 ? argv[1] : "";
     if (what == "merge")
         check_merge();
-    else if (what == "window")
+    else if (what == "window" && argc >= 5) {
+        const float gmin[2] = {from_bits(argv[2]), from_bits(argv[3])};
+        check_window_at(gmin, from_bits(argv[4]));
+    } else if (what == "window")
         check_window();
     else {
-        std::printf("usage: render_merge_driver merge|window\n");
+        std::printf("usage: render_merge_driver merge|window [gmin.x gmin.y h as fp32 bit patterns]\n");
         return 2;
     }
     if (!failures) std::printf("ok %s\n", what.c_str());
