@@ -18,7 +18,7 @@
  * What is the contract and what is scaffolding (the header has grown beyond the boundary SURVEY.md 8(b) asks for):
  *   STABLE — the drop-in boundary a Rust shim binds:
  *       lifecycle (sphx_default_params, sphx_create, sphx_destroy, sphx_last_error, sphx_abi_version), the particle-array
- *       surface (sphx_set_boundary, sphx_upload, sphx_append, sphx_remove, sphx_download*, sphx_num_*, sphx_view_*, sphx_sample_*, sphx_render*, sphx_state_*, sphx_track_*, sphx_download_by_id, sphx_particle_fields, sphx_fluid_stats, sphx_stats_*, sphx_query_radius, sphx_select), the Solver trait (sphx_clear_cached,
+ *       surface (sphx_set_boundary, sphx_upload, sphx_append, sphx_remove, sphx_download*, sphx_num_*, sphx_view_*, sphx_sample_*, sphx_render*, sphx_state_*, sphx_track_*, sphx_download_by_id, sphx_particle_fields, sphx_fluid_stats, sphx_stats_*, sphx_query_radius, sphx_select, sphx_gauge_*, sphx_probe_*), the Solver trait (sphx_clear_cached,
  *       sphx_step_begin[_law], sphx_step_finish, sphx_wcsph_step_*), the same trait over a device list (sphx_multi_create[_rank],
  *       sphx_multi_destroy, sphx_multi_set_boundary, sphx_multi_upload, sphx_multi_clear_cached, sphx_multi_step_begin/finish,
  *       sphx_multi_simulation_step[s], sphx_multi_download, sphx_multi_sample_*, sphx_sample_merge, sphx_multi_query_radius, sphx_multi_select, sphx_query_merge, sphx_multi_num_owned, sphx_multi_last_error, sphx_comm_ops) and
@@ -81,7 +81,9 @@ extern "C" {
                             *    sphx_tile_contour_sample / _border_fetch / _cut / _fetch
                             * 5 (additive): sphx_query_radius, sphx_select, sphx_query_out, sphx_select_out, SPHX_QUERY_*, SPHX_SELECT_*
                             * 5 (additive): sphx_multi_query_radius, sphx_multi_select, sphx_query_merge, sphx_multi_query_out,
-                            *    sphx_multi_select_out, sphx_tile_query_radius / _query_fetch / _select / _select_fetch, sphx_tile_query_part */
+                            *    sphx_multi_select_out, sphx_tile_query_radius / _query_fetch / _select / _select_fetch, sphx_tile_query_part
+                            * 5 (additive): sphx_gauge_levels, sphx_gauge_reduce, sphx_probe_record / _get_status / _read, sphx_gauge, sphx_gauge_rec,
+                            *    sphx_probe_rec, sphx_probe_status, SPHX_GAUGE_* */
 
 /* ---- status codes ---- */
 enum {
@@ -699,6 +701,79 @@ int sphx_stats_record(sphx_ctx* ctx, const sphx_rect* rects /* host */, uint32_t
 int sphx_stats_get_status(const sphx_ctx* ctx, sphx_stats_status* out);
 int sphx_stats_read(sphx_ctx* ctx, uint32_t first_frame, uint32_t n_frames, sphx_stats_rec* out /* host, [n_frames][1 + n_rects] */,
                     sphx_stats_frame* info /* host, [n_frames], may be NULL */);
+
+/* ---- gauges and probes: water levels along rays, and a per-step recorder of levels and point probes --------------------------------
+ * What a dam-break study plots is a time series at fixed places: the water height at the gauges H1..H4, the position of the front along
+ * the bed, the velocity at a few probe points.  sphx_gauge_levels samples rays on the device and reduces each ray to one record (the
+ * highest sample inside the fluid and the crossing point behind it); sphx_probe_record stores such records, and sphx_sample_points'
+ * outputs at fixed points, behind every every-th finished step without synchronising anything.
+ * The gauge contract (all fp32, unfused, one rounding per operation):
+ *   Samples: sample k of a gauge is the point (x0 + (float)k*dx, y0 + (float)k*dy), 0 <= k < n.  f_k is exactly what sphx_sample_points
+ *     returns at that point for the chosen field (SPHX_GAUGE_FIELD_FRACTION: fraction, SPHX_GAUGE_FIELD_DENSITY: density), kernel_kind
+ *     and state — the same device function, the same bits; for dx == 0 that is column 0 of sphx_sample_grid(x0, y0, any dx, dy, 1, n).
+ *     `values`, when given, receives those bits, gauge after gauge.
+ *   Inside test and counts: b_k = (f_k >= iso); a NaN value is outside.  first = the lowest k with b_k, last = the highest, inside = the
+ *     number of k with b_k.  inside < last - first + 1 means a bubble or a detached splash on the ray.
+ *   Crossing:
+ *     0 <= last < n-1, with a = last and b = last+1:  t = (iso - f_a) / (f_b - f_a), (x, y) = (x_a + t*(x_b - x_a), y_a + t*(y_b - y_a)),
+ *       f_last = f_a, f_next = f_b.  (f_b - f_a is never zero here: equal values compare alike with iso.)
+ *     last == n-1 (the ray ends wet):  t = 0, (x, y) = sample n-1, f_last = f_(n-1), f_next = the word 0x7FC00000.
+ *     nothing inside:  first = last = SPHX_GAUGE_NONE, inside = 0, and t, x, y, f_last, f_next are the word 0x7FC00000.
+ *     The first row is sphx_surface_contour's crossing rule (a is the lower sample index): a vertical gauge at x0 returns, bit for bit,
+ *     the point where the contour cuts the left edge of cell (0, last) of the lattice (x0, y0, any dx > 0, dy, 2, n).  A gauge with
+ *     dy == 0 gives the position of the front along the bed.
+ *   sphx_gauge_reduce is this rule over given values, as plain host code without a context (gauges[k].n values per gauge, gauge after
+ *     gauge); the device agrees with it bit for bit.  It returns SPHX_ERR_INVALID_ARGUMENT for the argument errors below (and for
+ *     values NULL with samples to read).
+ *   Argument errors (SPHX_ERR_INVALID_ARGUMENT, the message names the argument): out NULL, gauges NULL with n_gauges > 0, n_gauges >
+ *     SPHX_GAUGE_MAX, a gauge with n == 0 or n > 2^20, the sum of n above 2^24, a non-finite x0, y0, dx, dy or iso, an unknown
+ *     kernel_kind, field or flag bit.  n_gauges == 0 succeeds.  Negative and zero steps are legal.  A ray that leaves the domain or the
+ *     covered region never faults: its samples are sampling's zeros.
+ *   When allowed, refusals, side effects: as sphx_sample_points (the same SPHX_ERR_NOT_READY rules and messages, a tile context is
+ *     refused, the call only reads).  Two calls on one state return the same bytes: no atomic is used anywhere.
+ *   SPHX_GAUGE_DEVICE_POINTERS: out and values are device pointers (out 4-byte aligned); the call is enqueued on the context's stream
+ *     and does not wait.  Without it: host pointers, through a device scratch grown on demand and freed in sphx_destroy.  `gauges` is
+ *     host memory either way (copied).
+ * The recorder: after sphx_probe_record(points, m_points, gauges, n_gauges, ..., max_frames, every) every every-th SUCCESSFULLY finished
+ *   step (either solver, counted from the call; so also each step inside sphx_solver_simulation_steps) enqueues one frame behind its own
+ *   kernels: m_points sphx_probe_rec (sphx_sample_points' four outputs at the fixed points, reserved zero), then n_gauges
+ *   sphx_gauge_rec.  Nothing comes back to the host and nothing is synchronised until the read.  The library keeps one
+ *   sphx_stats_frame per frame on the host: step = finished steps since the call (1-based), dt = the dt given to that step_finish, n =
+ *   the particle count at that moment.  A failed step takes no frame and does not count.  A finished step after which sampling is not
+ *   allowed (a WCSPH step over zero fluid particles runs no build) takes no frame and is counted in `dropped`, as are the frames
+ *   beyond max_frames.  max_frames == 0 stops and frees; every == 0, m_points + n_gauges == 0 with max_frames > 0, m_points >= 2^20 and
+ *   the gauge errors above are SPHX_ERR_INVALID_ARGUMENT; a buffer (max_frames * (m_points + n_gauges) * 32 bytes) above 64 MiB is
+ *   SPHX_ERR_CAPACITY; a new sphx_probe_record discards the old recording.  sphx_probe_read copies the frames [first_frame, first_frame +
+ *   n_frames) and waits for the stream; a range beyond `frames` is SPHX_ERR_INVALID_ARGUMENT.  Record, read: SPHX_ERR_NOT_READY inside an
+ *   open step, a tile context is refused.  Recording may be switched on before the first step: unlike the one-shot call it needs no
+ *   sampleable state at the time of the call.
+ *   Lifetime: points and gauges are copied at the call.  The recording belongs to the CONTEXT: sphx_upload, sphx_append, sphx_remove and
+ *   sphx_state_load leave it alone; sphx_state_save does not store it.
+ *   No side effects: a run with a recording (and gauge calls between its steps) is bit-identical to the same run without — every
+ *   sphx_state_digest word, every sphx_step_stats field, sphx_last_flags — and a queued run-ahead pass stays valid.
+ * Cost: a one-shot call is two launches behind ceil(n_gauges / 64) small ones that carry the gauges to the device; a recorded frame is
+ *   three launches whatever the number of gauges; DESIGN.md section 4t. */
+typedef struct sphx_gauge { float x0, y0, dx, dy; uint32_t n; uint32_t reserved[3]; } sphx_gauge;   /* 32 bytes: a ray of n samples */
+typedef struct sphx_gauge_rec {       /* 32 bytes */
+    uint32_t first, last, inside;     /* lowest / highest k with b_k, SPHX_GAUGE_NONE if none; number of k with b_k */
+    float t;                          /* crossing parameter between last and last+1 */
+    float x, y;                       /* crossing point */
+    float f_last, f_next;             /* field at last and at last+1 */
+} sphx_gauge_rec;
+typedef struct sphx_probe_rec { float density, fraction, velocity[2]; uint32_t count; uint32_t reserved[3]; } sphx_probe_rec; /* 32 bytes */
+typedef struct sphx_probe_status { uint32_t m_points, n_gauges, recording, max_frames, every, frames, dropped, reserved; } sphx_probe_status;
+#define SPHX_GAUGE_NONE 0xFFFFFFFFu
+#define SPHX_GAUGE_MAX 1024
+enum { SPHX_GAUGE_FIELD_FRACTION = 0, SPHX_GAUGE_FIELD_DENSITY = 1 };
+enum { SPHX_GAUGE_DEVICE_POINTERS = 1u };
+int sphx_gauge_levels(sphx_ctx* ctx, const sphx_gauge* gauges /* host */, uint32_t n_gauges, int kernel_kind, int field, float iso,
+                      uint32_t flags, sphx_gauge_rec* out /* [n_gauges] */, float* values /* [sum n], gauge after gauge, or NULL */);
+int sphx_gauge_reduce(const float* values, const sphx_gauge* gauges, uint32_t n_gauges, float iso, sphx_gauge_rec* out);
+int sphx_probe_record(sphx_ctx* ctx, const float* points_xy /* host */, uint32_t m_points, const sphx_gauge* gauges /* host */,
+                      uint32_t n_gauges, int kernel_kind, int field, float iso, uint32_t max_frames, uint32_t every);
+int sphx_probe_get_status(const sphx_ctx* ctx, sphx_probe_status* out);
+int sphx_probe_read(sphx_ctx* ctx, uint32_t first_frame, uint32_t n_frames, sphx_probe_rec* points_out /* [n_frames][m_points] or NULL */,
+                    sphx_gauge_rec* gauges_out /* [n_frames][n_gauges] or NULL */, sphx_stats_frame* info /* [n_frames] or NULL */);
 
 /* Test aid for the zero-correction skip: cumulative numbers of correction workgroups that skipped their walk
  * (out[0]), that a flag inside their window stopped (out[1]) and that a flag behind an out-of-window table line stopped (out[2]; a workgroup

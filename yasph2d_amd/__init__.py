@@ -16,7 +16,8 @@ from ._lib import (FLAG_DENSITY_ITER_CAP, FLAG_DIVERGENCE_ITER_CAP, FLAG_DENSE_C
 
 __all__ = ["SphxContext", "FluidParticleWorld", "TimeManager", "DFSPHSolver", "DFSPHMultiSolver", "default_params", "duration_from_secs_f32",
            "duration_as_secs_f32", "SphxError", "WCSPHSolver", "VISCOSITY_XSPH", "VISCOSITY_PHYSICAL", "SAMPLE_FIELDS", "gauge_elevation", "contour_chain", "contour_lines", "contour_merge",
-           "sample_merge", "query_merge", "render_fit", "render_merge", "track_merge", "track_merge_frames", "write_png", "SCENE_RECT", "TRACK_FIELDS", "MULTI_TRACK_FIELDS", "FIELD_NAMES", "STATS_DTYPE", "STATS_FRAME_DTYPE"]
+           "sample_merge", "query_merge", "render_fit", "render_merge", "track_merge", "track_merge_frames", "write_png", "SCENE_RECT", "TRACK_FIELDS", "MULTI_TRACK_FIELDS", "FIELD_NAMES", "STATS_DTYPE", "STATS_FRAME_DTYPE",
+           "GAUGE_DTYPE", "GAUGE_REC_DTYPE", "PROBE_REC_DTYPE", "gauge_reduce"]
 
 
 def _p(a):
@@ -228,6 +229,51 @@ STATS_DTYPE = np.dtype([("count", "<u8"), ("nonfinite", "<u8"), ("density_count"
                         ("sum_density", "<f8"), ("sum_density_sq", "<f8"), ("max_speed_sq", "<f8"), ("min_pos", "<f4", (2,)),
                         ("max_pos", "<f4", (2,)), ("min_density", "<f4"), ("max_density", "<f4")])
 STATS_FRAME_DTYPE = np.dtype([("step", "<u8"), ("dt", "<f4"), ("n", "<u4")])
+
+
+# a gauge (sphx_gauge: the ray x0 + k * dx, y0 + k * dy, 0 <= k < n), its record (sphx_gauge_rec) and a point probe of a recorded frame
+# (sphx_probe_rec); 32 bytes each
+GAUGE_DTYPE = np.dtype([("x0", "<f4"), ("y0", "<f4"), ("dx", "<f4"), ("dy", "<f4"), ("n", "<u4"), ("reserved", "<u4", (3,))])
+GAUGE_REC_DTYPE = np.dtype([("first", "<u4"), ("last", "<u4"), ("inside", "<u4"), ("t", "<f4"), ("x", "<f4"), ("y", "<f4"), ("f_last", "<f4"),
+                            ("f_next", "<f4")])
+PROBE_REC_DTYPE = np.dtype([("density", "<f4"), ("fraction", "<f4"), ("velocity", "<f4", (2,)), ("count", "<u4"), ("reserved", "<u4", (3,))])
+
+
+def _gauge_array(gauges):
+    """[g, 5] rows of x0, y0, dx, dy, n (or a GAUGE_DTYPE array, or None) -> contiguous GAUGE_DTYPE array [g]."""
+    if gauges is None:
+        return np.zeros(0, GAUGE_DTYPE)
+    if isinstance(gauges, np.ndarray) and gauges.dtype == GAUGE_DTYPE:
+        return np.ascontiguousarray(gauges).reshape(-1)
+    a = np.asarray(gauges, np.float64)
+    if a.size == 0:
+        return np.zeros(0, GAUGE_DTYPE)
+    if a.ndim == 1:
+        a = a[None, :]
+    if a.ndim != 2 or a.shape[1] != 5:
+        raise ValueError("gauges must be [g, 5] rows of x0, y0, dx, dy, n or a GAUGE_DTYPE array, not shape %s" % (a.shape,))
+    n = a[:, 4]
+    if not (np.isfinite(n).all() and (n == np.floor(n)).all() and (n >= 0).all() and (n < 2.0 ** 32).all()):
+        raise ValueError("the sample counts n of gauges must be whole numbers in [0, 2^32)")
+    g = np.zeros(len(a), GAUGE_DTYPE)
+    for k, name in enumerate(("x0", "y0", "dx", "dy")):
+        g[name] = a[:, k].astype(np.float32)
+    g["n"] = n.astype(np.uint32)
+    return g
+
+
+def gauge_reduce(values, gauges, iso=0.5):
+    """sphx_gauge_reduce: the gauge rule of include/sphx.h over given values (float32, gauges[k].n per gauge, gauge after gauge) ->
+    GAUGE_REC_DTYPE array [g].  Host code; no GPU.  The device (SphxContext.gauges) agrees with it bit for bit."""
+    g = _gauge_array(gauges)
+    v = np.ascontiguousarray(values, np.float32).reshape(-1)
+    if len(v) != int(g["n"].astype(np.int64).sum()):
+        raise ValueError("values must hold %d floats (the sum of the gauges' n), not %d" % (int(g["n"].astype(np.int64).sum()), len(v)))
+    rec = np.zeros(len(g), GAUGE_REC_DTYPE)
+    rc = _lib.lib().sphx_gauge_reduce(_p(v) if len(v) else None, _p(g) if len(g) else None, len(g), iso, _p(rec) if len(g) else rec.ctypes.data or 1)
+    if rc:
+        raise SphxError(rc, "sphx_gauge_reduce: invalid argument (see include/sphx.h, \"gauges and probes\")")
+    return rec
 
 
 SCENE_RECT = (-0.1, -0.1, 2.1, 1.6)  # the world rectangle the reference app's camera is fitted to (main.rs:137), at scale 1
@@ -735,6 +781,77 @@ class SphxContext:
         info = np.zeros(count, STATS_FRAME_DTYPE)
         self._chk(self.L.sphx_stats_read(self.h, first, count, _p(rec) if count else None, _p(info) if count else None))
         return rec, info
+
+    # ---- gauges and probes (the contract is in include/sphx.h, "gauges and probes") ----
+    def gauges(self, gauges, iso=0.5, field="fraction", kernel=KERNEL_WENDLAND_C2, values=False, out=None):
+        """sphx_gauge_levels: each gauge is a ray of n samples, (x0 + k * dx, y0 + k * dy); its record names the lowest and the highest
+        sample with field >= iso, their number, and the crossing point behind the highest one (a vertical gauge: the water level; a
+        gauge with dy == 0: the front along the bed).
+
+        gauges: [g, 5] rows of x0, y0, dx, dy, n, or a GAUGE_DTYPE array.  field: "fraction" or "density".
+        Returns a GAUGE_REC_DTYPE array [g]; with values=True the pair (records, float32 values [sum n], gauge after gauge).
+        Device path: out = a contiguous torch uint8 tensor of g * 32 bytes on the context's device, and values may be a float32 tensor
+        of sum n values there; the library writes into them on its own stream (torch's current stream is synchronised before the call
+        and the context's stream after it, as in stats()).  Returns out, or (out, values)."""
+        if field not in _lib.GAUGE_FIELDS:
+            raise ValueError("field must be one of %s, not %r" % (sorted(_lib.GAUGE_FIELDS), field))
+        g = _gauge_array(gauges)
+        total = int(g["n"].astype(np.int64).sum())
+        gp = _p(g) if len(g) else None
+        if out is not None:
+            import torch
+
+            if not _is_torch(out) or out.device.type != "cuda" or not out.is_contiguous() or out.dtype != torch.uint8 or \
+                    out.numel() != len(g) * GAUGE_REC_DTYPE.itemsize:
+                raise ValueError("out must be a contiguous uint8 cuda tensor of %d bytes" % (len(g) * GAUGE_REC_DTYPE.itemsize))
+            val = values if _is_torch(values) else None
+            if values is not False and values is not None and val is None:
+                raise ValueError("with a device out, values must be a float32 cuda tensor of %d values (or False)" % total)
+            if val is not None and (val.device.type != "cuda" or not val.is_contiguous() or val.dtype != torch.float32 or val.numel() != total):
+                raise ValueError("values must be a contiguous float32 cuda tensor of %d values" % total)
+            torch.cuda.current_stream(out.device).synchronize()
+            self._chk(self.L.sphx_gauge_levels(self.h, gp, len(g), kernel, _lib.GAUGE_FIELDS[field], iso, _lib.GAUGE_DEVICE_POINTERS,
+                                               out.data_ptr() or 1, (val.data_ptr() or 1) if val is not None else None))
+            self.synchronize()
+            return out if val is None else (out, val)
+        rec = np.zeros(len(g), GAUGE_REC_DTYPE)
+        val = np.zeros(total, np.float32) if values else None
+        self._chk(self.L.sphx_gauge_levels(self.h, gp, len(g), kernel, _lib.GAUGE_FIELDS[field], iso, 0, rec.ctypes.data or 1,
+                                           (val.ctypes.data or 1) if values else None))
+        return (rec, val) if values else rec
+
+    def probe_record(self, points=None, gauges=None, max_frames=0, every=1, iso=0.5, field="fraction", kernel=KERNEL_WENDLAND_C2):
+        """sphx_probe_record: from now on every `every`-th finished step stores one frame on the device — sample(points)' four fields
+        at the fixed points and the records of gauges(gauges, iso, field, kernel) — up to max_frames frames (later ones are counted in
+        probe_status()["dropped"]); max_frames=0 stops and frees.  Nothing is synchronised."""
+        if field not in _lib.GAUGE_FIELDS:
+            raise ValueError("field must be one of %s, not %r" % (sorted(_lib.GAUGE_FIELDS), field))
+        g = _gauge_array(gauges)
+        pts = np.zeros((0, 2), np.float32) if points is None else np.ascontiguousarray(points, np.float32)
+        if pts.ndim != 2 or pts.shape[1] != 2:
+            raise ValueError("points must be a float32 [m, 2] array, not shape %s" % (pts.shape,))
+        self._chk(self.L.sphx_probe_record(self.h, _p(pts) if len(pts) else None, len(pts), _p(g) if len(g) else None, len(g), kernel,
+                                           _lib.GAUGE_FIELDS[field], iso, max_frames, every))
+
+    def probe_status(self):
+        """sphx_probe_get_status -> dict(m_points, n_gauges, recording, max_frames, every, frames, dropped)."""
+        st = _lib.SphxProbeStatus()
+        self._chk(self.L.sphx_probe_get_status(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_ if k != "reserved"}
+
+    def probe_frames(self, first=0, count=None):
+        """sphx_probe_read -> dict(points [count, m_points] of PROBE_REC_DTYPE, gauges [count, n_gauges] of GAUGE_REC_DTYPE, info [count]
+        of STATS_FRAME_DTYPE: step, dt, n) for the recorded frames [first, first + count) (count=None: all from `first`).  Waits for
+        the context's stream."""
+        st = self.probe_status()
+        if count is None:
+            count = max(st["frames"] - first, 0)
+        pts = np.zeros((count, st["m_points"]), PROBE_REC_DTYPE)
+        gau = np.zeros((count, st["n_gauges"]), GAUGE_REC_DTYPE)
+        info = np.zeros(count, STATS_FRAME_DTYPE)
+        self._chk(self.L.sphx_probe_read(self.h, first, count, _p(pts) if pts.size else None, _p(gau) if gau.size else None,
+                                         _p(info) if count else None))
+        return dict(points=pts, gauges=gau, info=info)
 
     def tile_stats(self, rects=()):
         """sphx_tile_fluid_stats: stats() of a TILE context (MultiSolver.tile_context(k)) over the particles that tile owns — its ghosts

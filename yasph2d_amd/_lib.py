@@ -228,6 +228,30 @@ class SphxStatsStatus(C.Structure):
                 ("dropped", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+GAUGE_DEVICE_POINTERS = 1  # sphx_gauge_levels flags
+GAUGE_FIELDS = dict(fraction=0, density=1)  # SPHX_GAUGE_FIELD_*
+GAUGE_NONE = 0xFFFFFFFF
+GAUGE_MAX = 1024
+
+
+class SphxGauge(C.Structure):  # 32 bytes: a ray of n samples
+    _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("dx", C.c_float), ("dy", C.c_float), ("n", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class SphxGaugeRec(C.Structure):  # 32 bytes
+    _fields_ = [("first", C.c_uint32), ("last", C.c_uint32), ("inside", C.c_uint32), ("t", C.c_float), ("x", C.c_float), ("y", C.c_float),
+                ("f_last", C.c_float), ("f_next", C.c_float)]
+
+
+class SphxProbeRec(C.Structure):  # 32 bytes
+    _fields_ = [("density", C.c_float), ("fraction", C.c_float), ("velocity", C.c_float * 2), ("count", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class SphxProbeStatus(C.Structure):  # 32 bytes
+    _fields_ = [("m_points", C.c_uint32), ("n_gauges", C.c_uint32), ("recording", C.c_uint32), ("max_frames", C.c_uint32), ("every", C.c_uint32),
+                ("frames", C.c_uint32), ("dropped", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class SphxTimerState(C.Structure):
     _fields_ = [("fixed", C.c_uint32), ("cfl_factor", C.c_float), ("timestep_max_ns", C.c_uint64), ("timestep_min_ns", C.c_uint64),
                 ("simulation_step_ns", C.c_uint64), ("timestep_target_frame_ns", C.c_uint64), ("total_simulated_ns", C.c_uint64),
@@ -310,6 +334,11 @@ SIGNATURES = {
     "sphx_stats_record": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32, _u32]),
     "sphx_stats_get_status": (_i, [_vp, C.POINTER(SphxStatsStatus)]),
     "sphx_stats_read": (_i, [_vp, _u32, _u32, _vp, _vp]),
+    "sphx_gauge_levels": (_i, [_vp, _vp, _u32, _i, _i, _f, _u32, _vp, _vp]),
+    "sphx_gauge_reduce": (_i, [_vp, _vp, _u32, _f, _vp]),
+    "sphx_probe_record": (_i, [_vp, _vp, _u32, _vp, _u32, _i, _i, _f, _u32, _u32]),
+    "sphx_probe_get_status": (_i, [_vp, C.POINTER(SphxProbeStatus)]),
+    "sphx_probe_read": (_i, [_vp, _u32, _u32, _vp, _vp, _vp]),
     "sphx_tile_fluid_stats": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32, _vp]),
     "sphx_tile_stats_record": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32, _u32]),
     "sphx_tile_stats_frame": (_i, [_vp, _f, _u32]),

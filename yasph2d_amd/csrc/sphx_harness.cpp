@@ -2,7 +2,7 @@
 // draw (main.rs:85-129 set-up, :177-196 scene, :279 `sph_solver.simulation_step(&mut fluid_world, &mut time_manager)`).
 //
 //   sphx_harness [--solver dfsph|wcsph] [--viscosity xsph|physical[:mu]] [--scale S | --particles N] [--steps K] [--warmup W] [--no-law] [--sync]
-//                [--gauges x1,x2,... [--gauge-range lo:hi:dy]]
+//                [--gauges x1,x2,... [--gauge-range lo:hi:dy] [--gauge-out FILE [--gauge-every K]]]
 //                [--record DIR [--record-fps F] [--record-size WxH] [--record-min-pixel-radius P]]
 //                [--emit x,y,w,h[:every=K][:until=S][:vel=vx,vy]] [--drain x0,y0,x1,y1]... [--keep x0,y0,x1,y1]...
 //                [--load-state FILE] [--save-state FILE[:at=STEP]] [--track ID[,ID...] [--track-every E] --track-out FILE] [--fields-out FILE]
@@ -56,6 +56,12 @@
 // --gauges: after the run, the free-surface elevation at each x (sphx_sample_grid of the fluid fraction on a one-column lattice from lo
 // in steps of dy up to hi, the rule of yasph2d_amd.gauge_elevation): "gauge_elevations": [...] in the JSON line, null where a column
 // holds no fluid.  Default range lo = 0, hi = 2.5 * scale (the top of the scene), dy = particle_radius / 2.
+//
+// --gauge-out (needs --gauges): the same columns (x, from lo in steps of dy, floor((hi - lo) / dy) + 1 samples) are recorded on the device as
+// gauges behind every K-th step of the run (sphx_probe_record of the fluid fraction at 0.5, Wendland kernel; --gauge-every K, default 1;
+// warm-up and timed steps counted together) and written after the run as the CSV "step,dt,gauge,first,last,inside,x,y": one line per
+// frame and gauge, the members of sphx_gauge_rec (%.9g, which round-trips fp32; "nan" for a column without fluid, first / last then
+// 4294967295).  The JSON line gains "gauge_frames".  "gauge_elevations" is not affected.
 //
 // --record: the reference's recording mode (main.rs:310-331, :344-346, :380-397).  The timer gets TargetFrameLength(1 / F) (F = 60), the
 // camera is the app's (main.rs:137: Rect(-0.1, -0.1, 2.1, 1.6) x scale fitted to a W x H screen, 1920x1080), and every completed frame is
@@ -124,7 +130,7 @@ static bool gauge_elevation(sph::HipDfsphSolver& solver, double x, double lo, do
 // `count` comma-separated numbers; a rectangle bound may be infinite, never NaN
 static const char* const USAGE =
     "sphx_harness [--solver dfsph|wcsph] [--viscosity xsph|physical[:mu]] [--scale S | --particles N] [--steps K] [--warmup W] [--no-law] [--sync]\n"
-    "             [--gauges x1,x2,... [--gauge-range lo:hi:dy]]\n"
+    "             [--gauges x1,x2,... [--gauge-range lo:hi:dy] [--gauge-out FILE [--gauge-every K]]]\n"
     "             [--record DIR [--record-fps F] [--record-size WxH] [--record-min-pixel-radius P]]\n"
     "             [--emit x,y,w,h[:every=K][:until=S][:vel=vx,vy]] [--drain x0,y0,x1,y1]... [--keep x0,y0,x1,y1]...\n"
     "             [--load-state FILE] [--save-state FILE[:at=STEP]] [--track ID[,ID...] [--track-every E] --track-out FILE] [--fields-out FILE]\n"
@@ -137,6 +143,8 @@ static const char* const USAGE =
     "  --track ID[,ID...]           follow these particle ids on the device (sphx_track_set + sphx_track_record), a frame behind every step\n"
     "  --track-every E              ... behind every E-th step only (default 1)\n"
     "  --track-out FILE             write the frames after the run as CSV: frame,id,x,y,vx,vy\n"
+    "  --gauge-out FILE             record the --gauges columns as gauges (sphx_probe_record) behind every step, write the CSV step,dt,gauge,first,last,inside,x,y\n"
+    "  --gauge-every K              ... behind every K-th step\n"
     "  --stats-out FILE             record the whole fluid's statistics (sphx_stats_record) behind every step, write one JSON line per frame\n"
     "  --stats-every K              ... behind every K-th step only (default 1)\n"
     "  --fields-out FILE            write the final state's flow fields (sphx_particle_fields) as CSV: id,x,y,divergence,vorticity,cx,cy\n"
@@ -182,6 +190,8 @@ int main(int argc, char** argv) {
     long save_at = -1;  // (-1: after the last step)
     std::string track_arg, track_every_arg, track_out;
     bool want_track = false, want_track_every = false, want_track_out = false;
+    std::string gauge_out, gauge_every_arg;
+    bool want_gauge_out = false, want_gauge_every = false;
     std::string stats_out, stats_every_arg;
     bool want_stats = false, want_stats_every = false;
     std::string fields_out;
@@ -224,6 +234,8 @@ int main(int argc, char** argv) {
         else if (s == "--track") track_arg = a + 1 < argc ? argv[++a] : "", want_track = true;
         else if (s == "--track-every") track_every_arg = next(), want_track_every = true;
         else if (s == "--track-out") track_out = a + 1 < argc ? argv[++a] : "", want_track_out = true;
+        else if (s == "--gauge-out") gauge_out = a + 1 < argc ? argv[++a] : "", want_gauge_out = true;
+        else if (s == "--gauge-every") gauge_every_arg = next(), want_gauge_every = true;
         else if (s == "--stats-out") stats_out = a + 1 < argc ? argv[++a] : "", want_stats = true;
         else if (s == "--stats-every") stats_every_arg = next(), want_stats_every = true;
         else if (s == "--fields-out") fields_out = a + 1 < argc ? argv[++a] : "", want_fields = true;
@@ -368,6 +380,21 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    uint32_t gauge_every = 1;
+    std::vector<sphx_gauge> gauge_rays;  // the --gauges columns as gauges (--gauge-out)
+    if (want_gauge_out || want_gauge_every) {
+        double e = 1.0;
+        const double ny = std::floor((gauge_hi - gauge_lo) / gauge_dy) + 1.0;
+        const bool ok = want_gauge_out && want_gauges && !gauge_out.empty() && gauge_x.size() <= SPHX_GAUGE_MAX && ny >= 1.0 && ny <= 1048576.0 &&
+                        (!want_gauge_every || (parse_double(gauge_every_arg, &e) && e >= 1.0 && e == std::floor(e) && e <= 4294967295.0));
+        if (!ok) {
+            std::fprintf(stderr, "invalid --gauge options (--gauge-out FILE [--gauge-every K >= 1], with --gauges of at most %d columns of at most 2^20 samples)\n",
+                         SPHX_GAUGE_MAX);
+            return 2;
+        }
+        gauge_every = (uint32_t)e;
+        for (double x : gauge_x) gauge_rays.push_back(sphx_gauge{(float)x, (float)gauge_lo, 0.0f, (float)gauge_dy, (uint32_t)ny, {0u, 0u, 0u}});
+    }
     double record_fps = 60.0, record_mpr = 0.0;
     uint32_t record_w = 1920, record_h = 1080;
     if (want_record || want_fps || want_size || want_mpr) {
@@ -463,6 +490,18 @@ int main(int argc, char** argv) {
         const int rc = stats_max_frames > 0xFFFFFFFFull ? SPHX_ERR_CAPACITY : sphx_stats_record(solver->ctx(), nullptr, 0u, (uint32_t)stats_max_frames, stats_every);
         if (rc != SPHX_OK) {
             std::fprintf(stderr, "--stats-out failed: %s (status %d)\n", sphx_last_error(solver->ctx()), rc);
+            return 1;
+        }
+    }
+    // the gauge recorder, likewise
+    const uint64_t gauge_max_frames = want_gauge_out ? (uint64_t)std::max(warmup + steps, 0l) / gauge_every : 0;
+    if (gauge_max_frames) {
+        const int rc = gauge_max_frames > 0xFFFFFFFFull
+                           ? SPHX_ERR_CAPACITY
+                           : sphx_probe_record(solver->ctx(), nullptr, 0u, gauge_rays.data(), (uint32_t)gauge_rays.size(), SPHX_KERNEL_WENDLAND_C2,
+                                               SPHX_GAUGE_FIELD_FRACTION, 0.5f, (uint32_t)gauge_max_frames, gauge_every);
+        if (rc != SPHX_OK) {
+            std::fprintf(stderr, "--gauge-out failed: %s (status %d)\n", sphx_last_error(solver->ctx()), rc);
             return 1;
         }
     }
@@ -591,6 +630,37 @@ int main(int argc, char** argv) {
             gauge_json += (g ? ", " : "") + std::string(buf);
         }
         gauge_json += "]";
+    }
+    if (want_gauge_out) {
+        sphx_probe_status ps{};
+        std::vector<sphx_gauge_rec> rec;
+        std::vector<sphx_stats_frame> info;
+        int rc = sphx_probe_get_status(solver->ctx(), &ps);
+        if (rc == SPHX_OK && ps.frames) {
+            rec.resize((size_t)ps.frames * ps.n_gauges);
+            info.resize(ps.frames);
+            rc = sphx_probe_read(solver->ctx(), 0u, ps.frames, nullptr, rec.data(), info.data());
+        }
+        if (rc != SPHX_OK) {
+            std::fprintf(stderr, "--gauge-out: %s (status %d)\n", sphx_last_error(solver->ctx()), rc);
+            return 1;
+        }
+        FILE* f = std::fopen(gauge_out.c_str(), "w");
+        bool ok = f != nullptr && std::fputs("step,dt,gauge,first,last,inside,x,y\n", f) >= 0;
+        for (size_t k = 0; ok && k < rec.size(); ++k) {
+            const sphx_gauge_rec& r = rec[k];
+            const sphx_stats_frame& fr = info[k / ps.n_gauges];
+            ok = std::fprintf(f, "%llu,%.9g,%zu,%u,%u,%u,%.9g,%.9g\n", (unsigned long long)fr.step, (double)fr.dt, k % ps.n_gauges, r.first, r.last, r.inside,
+                              (double)r.x, (double)r.y) > 0;
+        }
+        if (f) ok = std::fclose(f) == 0 && ok;
+        if (!ok) {
+            std::fprintf(stderr, "cannot write %s\n", gauge_out.c_str());
+            return 1;
+        }
+        char buf[64];
+        std::snprintf(buf, sizeof(buf), ", \"gauge_frames\": %u", ps.frames);
+        gauge_json += buf;
     }
     if (want_record) {
         char buf[96];

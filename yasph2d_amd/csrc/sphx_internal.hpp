@@ -376,6 +376,18 @@ struct sphx_ctx {
         uint32_t n_rects = 0, recording = 0, max_frames = 0, every = 0, frames = 0, dropped = 0, steps = 0;  // steps: finished since sphx_stats_record
         std::vector<sphx_stats_frame> info;  // ... and one entry per stored frame (host)
     } stats;
+    // gauges and probes (sphx_gauge_levels, sphx_probe_*: sphx_gauge.inc).  Belongs to the context, not to the particle state.
+    struct Probe {
+        uint32_t* scratch = nullptr;  // device, one-shot call: gauge table | values (unless the caller's array takes them) | host path: records
+        size_t scratch_cap = 0;       // ... in 4-byte words
+        uint32_t* fixed = nullptr;    // recording, device: gauge table [8 n_gauges] | values [total] | points [2 m_points]
+        uint32_t* rec = nullptr;      // recording, device: [max_frames][m_points] sphx_probe_rec, then [max_frames][n_gauges] sphx_gauge_rec
+        uint32_t m_points = 0, n_gauges = 0, total = 0;  // total: samples of all gauges
+        int kind = 0, field = 0;
+        float iso = 0.0f;
+        uint32_t recording = 0, max_frames = 0, every = 0, frames = 0, dropped = 0, steps = 0;  // steps: finished since sphx_probe_record
+        std::vector<sphx_stats_frame> info;  // one entry per stored frame (host)
+    } probe;
     bool uploaded = false, boundary_changed = true, tails_dirty = true, in_step = false;
     bool lists_current = false;  // the neighbour lists were built from the positions the arrays hold (raised by a completed build, dropped with q_noclamp)
     unsigned long long* state_dig = nullptr;  // sphx_state_*: one digest per section (device), allocated on first use

@@ -2918,6 +2918,8 @@ __global__ __launch_bounds__(64) void k_publish(DevScalars* scal, Mailbox* mb, u
 #include "sphx_launch.inc"
 // field sampling at points and on lattices (kernels + C ABI)
 #include "sphx_sample.inc"
+// gauges along rays and the per-step recorder of gauges and point probes (kernels + C ABI)
+#include "sphx_gauge.inc"
 // the particles drawn as discs into an image (kernels + C ABI)
 #include "sphx_render.inc"
 // fluid appended to and removed from the device state between steps (kernels + C ABI)

@@ -727,6 +727,12 @@ void stats_take_frame(sphx_ctx* c, float dt);
 static inline void stats_after_step(sphx_ctx* c, float dt) {
     if (c->stats.recording) stats_take_frame(c, dt);
 }
+// The recorder of sphx_probe_record (sphx_gauge.inc), likewise: one flag test; with a recording on, a frame of point probes and gauge
+// records is queued behind the step's kernels (only where the finished step left a state that may be sampled).
+void probe_take_frame(sphx_ctx* c, float dt);
+static inline void probe_after_step(sphx_ctx* c, float dt) {
+    if (c->probe.recording) probe_take_frame(c, dt);
+}
 // Positions are about to change (or have changed) without the neighbour lists being rebuilt first: the walks go back to the forms
 // that are right for any distance (sqrt_dist in sphx_kernels.hip) until the next build.
 static inline void lists_went_stale(sphx_ctx* c) {
@@ -1801,7 +1807,7 @@ void sphx_destroy(sphx_ctx* c) {
     dev_free(&c->bpos); dev_free(&c->bpos2); dev_free(&c->bid); dev_free(&c->bid2); dev_free(&c->nb_list); dev_free(&c->nb_wave); dev_free(&c->nb_counts); dev_free(&c->nb_remote);
     dev_free(&c->scan_partials); dev_free(&c->scan_state); dev_free(&c->d_scal); dev_free(&c->tile_blk); dev_free(&c->sample_buf); dev_free(&c->render_buf); dev_free(&c->edit_buf); dev_free(&c->state_dig); dev_free(&c->mstate_buf);
     dev_free(&c->track.set_buf); dev_free(&c->track.rec); dev_free(&c->track.scratch); dev_free(&c->fields_buf);
-    dev_free(&c->stats.scratch); dev_free(&c->stats.rec); dev_free(&c->tsample.null_grid); dev_free(&c->contour_buf); dev_free(&c->query_buf); dev_free(&c->query_ent);
+    dev_free(&c->stats.scratch); dev_free(&c->stats.rec); dev_free(&c->probe.scratch); dev_free(&c->probe.fixed); dev_free(&c->probe.rec); dev_free(&c->tsample.null_grid); dev_free(&c->contour_buf); dev_free(&c->query_buf); dev_free(&c->query_ent);
     free_grid(c->gdyn);
     free_grid(c->gstat);
     if (c->mbox) hipHostFree((void*)c->mbox);
@@ -2148,6 +2154,7 @@ int sphx_step_finish(sphx_ctx* c, float dt, sphx_step_stats* out) {
     sample_after_step(c);  // re-grid, densities (fused into the build) and the divergence loop, which moves no particle
     track_after_step(c);
     stats_after_step(c, dt);
+    probe_after_step(c, dt);
     return SPHX_OK;
 }
 
@@ -2236,6 +2243,7 @@ int sphx_wcsph_step_finish(sphx_ctx* c, float dt, sphx_step_stats* out) {
     sample_after_step(c);  // phase A re-gridded the leap-frogged positions and took their Poly6 densities; leap frog 2 moves none
     track_after_step(c);
     stats_after_step(c, dt);
+    probe_after_step(c, dt);
     return SPHX_OK;
 }
 
