@@ -21,7 +21,7 @@
  *       surface (sphx_set_boundary, sphx_upload, sphx_append, sphx_remove, sphx_download*, sphx_num_*, sphx_view_*, sphx_sample_*, sphx_render*, sphx_state_*, sphx_track_*, sphx_download_by_id, sphx_particle_fields, sphx_fluid_stats, sphx_stats_*, sphx_query_radius, sphx_select, sphx_gauge_*, sphx_probe_*), the Solver trait (sphx_clear_cached,
  *       sphx_step_begin[_law], sphx_step_finish, sphx_wcsph_step_*), the same trait over a device list (sphx_multi_create[_rank],
  *       sphx_multi_destroy, sphx_multi_set_boundary, sphx_multi_upload, sphx_multi_clear_cached, sphx_multi_step_begin/finish,
- *       sphx_multi_simulation_step[s], sphx_multi_download, sphx_multi_sample_*, sphx_sample_merge, sphx_multi_query_radius, sphx_multi_select, sphx_query_merge, sphx_multi_num_owned, sphx_multi_last_error, sphx_comm_ops) and
+ *       sphx_multi_simulation_step[s], sphx_multi_download, sphx_multi_sample_*, sphx_sample_merge, sphx_multi_query_radius, sphx_multi_select, sphx_query_merge, sphx_multi_gauge_levels, sphx_gauge_merge, sphx_multi_probe_*, sphx_multi_num_owned, sphx_multi_last_error, sphx_comm_ops) and
  *       the status / flag codes.
  *   INSPECTION — parity tests and tools, not on the hot path, may change with the data layout:
  *       sphx_update_neighborhood, sphx_update_densities, sphx_compute_alpha (the pieces benches/ drives), sphx_download_solver_state,
@@ -83,7 +83,9 @@ extern "C" {
                             * 5 (additive): sphx_multi_query_radius, sphx_multi_select, sphx_query_merge, sphx_multi_query_out,
                             *    sphx_multi_select_out, sphx_tile_query_radius / _query_fetch / _select / _select_fetch, sphx_tile_query_part
                             * 5 (additive): sphx_gauge_levels, sphx_gauge_reduce, sphx_probe_record / _get_status / _read, sphx_gauge, sphx_gauge_rec,
-                            *    sphx_probe_rec, sphx_probe_status, SPHX_GAUGE_* */
+                            *    sphx_probe_rec, sphx_probe_status, SPHX_GAUGE_*
+                            * 5 (additive): sphx_multi_gauge_levels, sphx_gauge_merge, sphx_gauge_part, sphx_multi_probe_record / _get_status /
+                            *    _read, sphx_tile_gauge_levels / _gauge_fetch, sphx_tile_probe_record / _due / _frame / _read */
 
 /* ---- status codes ---- */
 enum {
@@ -1662,6 +1664,76 @@ int sphx_tile_query_radius(sphx_ctx* tile_ctx, const float* xy /* host, [2m] */,
 int sphx_tile_query_fetch(sphx_ctx* tile_ctx, uint64_t cap_entries, sphx_tile_query_part* part);
 int sphx_tile_select(sphx_ctx* tile_ctx, const sphx_rect* rects, uint32_t n_rects, uint32_t flags);
 int sphx_tile_select_fetch(sphx_ctx* tile_ctx, uint32_t cap, uint32_t* slot /* host, [cap] */, uint32_t* id, uint32_t* out_total);
+
+/* ---- gauges and probes of a tiled run (csrc/sphx_gauge.inc, csrc/sphx_gauge_window.hpp, csrc/sphx_gauge_merge.hpp) -----------------------
+ * sphx_gauge_levels and the sphx_probe_* recorder for a sphx_multi.  Every sample of a ray and every probe point is answered by the tile
+ * that owns its cell, over that tile's own arrays — the bits sphx_multi_sample_points returns at that point.  The values stay on the
+ * devices: each tile reduces the samples it owns on a gauge to one 32-byte sphx_gauge_part, and a pure host fold makes the record.
+ * Two facts carry this (stated and proved in sphx_gauge_window.hpp, held by tests/test_gauge_multi_host.py before any kernel runs):
+ *   1. the owned samples of one tile on one gauge are one contiguous index interval [lo, lo + count), found by four bisections on the
+ *      host, for steps of either sign, zero steps and coordinates that overflow;
+ *   2. the intervals of the tiles partition [0, n); if the tile that owns sample `last` does not own last + 1, then last + 1 is the
+ *      first owned sample of the tile that does.  So a part that carries the value at its own first sample is enough.
+ * sphx_gauge_part (one per tile and gauge): lo, count = the owned interval in global sample indices, count being the number of samples
+ *   the DEVICE's ownership test (the tile rectangle over cell_of) accepted; first, last, inside over the owned samples, as global
+ *   indices (SPHX_GAUGE_NONE / 0 if none); f_lo = the value at sample lo; f_last = the value at the part's own last; f_next = the value at
+ *   its own last + 1 if the part owns that sample.  A member without a meaning holds the word 0x7FC00000.
+ * The fold: the parts with count > 0, ordered by lo, must tile [0, n) exactly — a gap, an overlap or a count that disagrees with the
+ *   host's interval is an error (SPHX_ERR_HIP from the multi, SPHX_ERR_INVALID_ARGUMENT from sphx_gauge_merge) and no record is
+ *   returned.  Then first = the minimum, last = the maximum, inside = the sum, f_last from the part that holds last, f_next from that part
+ *   or from the f_lo of the part whose lo == last + 1, and the record is formed by the one function that forms it everywhere
+ *   (sphx_gauge_rule.hpp): bit for bit sphx_gauge_reduce over the concatenated values.  Consequences: the records equal the gauge rule
+ *   over sphx_multi_sample_points' values; in tiling-invariant mode they equal sphx_gauge_levels on a single context byte for byte.
+ * sphx_multi_gauge_levels: arguments, limits and messages of sphx_gauge_levels (flags must be 0: there is no device-pointer path across
+ *   several devices).  State rules and the ghost band: those of sphx_multi_sample_points — if the band is spent, the halo exchange the
+ *   next step owes happens now, and the run is unchanged; the call is collective in rank mode for that reason.  All local tiles
+ *   enqueue, then the parts (and the compact values, if asked for) are fetched and folded.  values: host, [sum n] — tile t's values of
+ *   gauge g arrive at offset(g) + lo; in rank mode the samples other ranks own are left as they were.  out_parts: host, [local
+ *   tiles][n_gauges], or NULL.  In rank mode out_parts is required, out may be NULL and is not written: the caller moves the parts and
+ *   folds them with sphx_gauge_merge(gauges, n_gauges, iso, parts, n_parts, out) — parts is [n_parts][n_gauges] — pure host code.
+ * The recorder: sphx_multi_probe_record(points, m_points, gauges, n_gauges, ..., max_frames, every) — arguments, limits, `dropped`,
+ *   max_frames == 0 and "a new record discards the old" as sphx_probe_record; the 64 MiB cap is per tile.  Every every-th finished
+ *   multi step (also each step inside sphx_multi_simulation_steps) takes a frame on every tile, behind the tile's own kernels: the
+ *   ghost band is made final the way a query does (the exchange the next step owes, if the band is spent — the next step then makes
+ *   none), then the tile enqueues its passes.  Nothing else is synchronised; the parts are folded at the read.  The cuts move: a tile's
+ *   interval table is rebuilt on the host and re-sent as kernel arguments whenever the tile's owned rectangle differs from the one
+ *   the table was built for, checked at every frame.  It may be called before the first upload.  The recording belongs to the
+ *   MULTI: it survives migration, re-partitioning, sphx_multi_append / _remove, uploads and state loads.
+ *   sphx_multi_probe_read(first, n, points_out, point_tile, gauges_out, info): points_out [n][m_points] sphx_probe_rec folded by the
+ *   tiles' "answered" mark, lowest tile first (reserved words zero; nobody answered: zeros), point_tile [n][m_points] the tile that
+ *   answered or -1, gauges_out [n][n_gauges] folded records.  Rank mode: points_out / point_tile are this rank's part (fold by
+ *   point_tile >= 0), gauges_out must be NULL — the rank's parts come from sphx_tile_probe_read on sphx_multi_tile_ctx.
+ * No side effects: a run with a recording and one-shot calls is bit-identical to the run without, exchanges and rebalances included.
+ * One tile (INTERNAL, accepted only on a tile context — sphx_gauge_levels and sphx_probe_* keep refusing one): sphx_tile_gauge_levels
+ *   enqueues the table, the sample pass over the owned samples and the reduce pass; sphx_tile_gauge_fetch copies the parts (and the
+ *   compact values: the owned samples gauge after gauge) and checks the device's counts against the host's intervals.
+ *   sphx_tile_probe_record / _due / _frame / _read are the seam of the recorder; a stored point slot carries the "answered" mark in
+ *   reserved[0]. */
+typedef struct sphx_gauge_part {      /* 32 bytes */
+    uint32_t lo, count;               /* the owned interval [lo, lo + count) */
+    uint32_t first, last, inside;     /* over the owned samples, global indices */
+    float f_lo, f_last, f_next;       /* values at lo, at last, at last + 1 (if owned) */
+} sphx_gauge_part;
+int sphx_multi_gauge_levels(sphx_multi* m, const sphx_gauge* gauges /* host */, uint32_t n_gauges, int kernel_kind, int field, float iso,
+                            uint32_t flags /* 0 */, sphx_gauge_rec* out /* [n_gauges] */, float* values /* host [sum n] or NULL */,
+                            sphx_gauge_part* out_parts /* [local tiles][n_gauges] or NULL */);
+int sphx_gauge_merge(const sphx_gauge* gauges, uint32_t n_gauges, float iso, const sphx_gauge_part* parts /* [n_parts][n_gauges] */,
+                     uint32_t n_parts, sphx_gauge_rec* out /* [n_gauges] */);   /* pure host code */
+int sphx_multi_probe_record(sphx_multi* m, const float* points_xy /* host */, uint32_t m_points, const sphx_gauge* gauges /* host */,
+                            uint32_t n_gauges, int kernel_kind, int field, float iso, uint32_t max_frames, uint32_t every);
+int sphx_multi_probe_get_status(const sphx_multi* m, sphx_probe_status* out);
+int sphx_multi_probe_read(sphx_multi* m, uint32_t first_frame, uint32_t n_frames, sphx_probe_rec* points_out /* [n_frames][m_points] or NULL */,
+                          int32_t* point_tile /* [n_frames][m_points] or NULL */, sphx_gauge_rec* gauges_out /* [n_frames][n_gauges] or NULL */,
+                          sphx_stats_frame* info /* [n_frames] or NULL */);
+int sphx_tile_gauge_levels(sphx_ctx* tile_ctx, const sphx_gauge* gauges /* host */, uint32_t n_gauges, int kernel_kind, int field, float iso);
+int sphx_tile_gauge_fetch(sphx_ctx* tile_ctx, sphx_gauge_part* parts /* host, [n_gauges] */, float* values /* host, compact, or NULL */,
+                          uint32_t* out_lo_count /* host, [2 n_gauges]: the host's intervals, or NULL */);
+int sphx_tile_probe_record(sphx_ctx* tile_ctx, const float* points_xy, uint32_t m_points, const sphx_gauge* gauges, uint32_t n_gauges,
+                           int kernel_kind, int field, float iso, uint32_t max_frames, uint32_t every);
+int sphx_tile_probe_due(const sphx_ctx* tile_ctx);  /* 1: the next sphx_tile_probe_frame stores a frame */
+int sphx_tile_probe_frame(sphx_ctx* tile_ctx, float dt, uint32_t n_global); /* one finished step: a frame if the recording is due */
+int sphx_tile_probe_read(sphx_ctx* tile_ctx, uint32_t first_frame, uint32_t n_frames, sphx_probe_rec* points_out /* marks kept */,
+                         sphx_gauge_part* parts_out /* [n_frames][n_gauges] */, sphx_stats_frame* info);
 
 /* ---- single-node scalar reductions through POSIX shared memory ---------------------------------------------------------------
  * The three per-step scalars of the tile driver (vmax, two residual sums) already sit in host memory (pinned mailbox) on every

@@ -2,6 +2,7 @@
 """Cost of the gauges (sphx_gauge_levels) and of the probe recorder (sphx_probe_record) on the dam break.
 
   tools/gauge_bench.py [--particles 1000000,16000000] [--warmup 40] [--calls 15] [--block 10] [--rounds 4] [--parent-lib PATH]
+  tools/gauge_bench.py --tiles K [the same options]      the tiled run: see tiled()
 
 Per particle count:
   (a) one-shot call.  The scene is stepped --warmup times; 8 columns x 512 samples across the free surface of the standing block are
@@ -189,6 +190,93 @@ def overhead(n, args):
     return out
 
 
+def tiled(n, args):
+    """--tiles K: the dam break in K tiles on one device (2 x 2 for K == 4, strips otherwise).
+    One-shot: 8 columns x 512 samples as ONE sphx_multi_gauge_levels call (wall time, median) next to the path without it —
+    multi.sample of the same points (fraction alone) plus gauge_reduce on the host — with the bytes that cross to the host in each.
+    Recorder: alternating blocks of --block steps without and with a recording of those columns and 8 probe points at every = 1, on one
+    multi; and the same blocks, all without a recording, on a library of the parent commit (--parent-lib) in a child process."""
+    y = load(args.lib)
+    from yasph2d_amd.multi import MultiSolver
+
+    scale = float(np.sqrt(n / 4050.0))
+    w = y.FluidParticleWorld()
+    w.reset_fluid(scale)
+    m = MultiSolver(y.default_params(), devices=[0] * args.tiles)
+    m.set_boundary(w.boundary_particles)
+    m.upload(w.positions)
+    t = y.TimeManager()
+    m.steps(t, args.warmup)
+    m.synchronize()
+    xs, y_lo, y_hi, dy = columns(scale)
+    gauges = [[x, y_lo, 0.0, dy, SAMPLES] for x in xs]
+    points = np.stack([xs, np.full(COLUMNS, 1.0 * scale)], -1).astype(np.float32)
+    has = hasattr(m, "gauges") and "sphx_multi_gauge_levels" in y._lib.SIGNATURES
+    out = dict(particles=n, tiles=args.tiles, columns=COLUMNS, samples=SAMPLES, library=args.lib or "this")
+
+    def block():
+        m.synchronize()
+        t0 = time.perf_counter()
+        m.steps(t, args.block)
+        m.synchronize()
+        return (time.perf_counter() - t0) * 1e6 / args.block
+
+    if has:
+        g = y._gauge_array(gauges)
+        k = np.arange(SAMPLES, dtype=np.float32)
+        pts = np.concatenate([np.stack([np.full(SAMPLES, np.float32(r["x0"]), np.float32), (np.float32(r["y0"]) + (k * np.float32(r["dy"])).astype(np.float32))], -1)
+                              for r in g]).astype(np.float32)
+        old = lambda: y.gauge_reduce(m.sample(pts, fields=("fraction",))["fraction"], g, 0.5)
+        for _ in range(3):  # warm both ways: code objects, the scratch
+            m.gauges(g)
+            old()
+        call_med, call_min, rec = wall_us(args.calls, lambda: m.gauges(g))
+        old_med, old_min, rec_old = wall_us(args.calls, old)
+        call_med2, call_min2, _ = wall_us(args.calls, lambda: m.gauges(g))  # (again, behind the other: the spread)
+        assert rec.tobytes() == rec_old.tobytes() and (rec["inside"] > 0).all()
+        out["one_shot"] = dict(gauge_levels_wall_us=dict(median=call_med, min=call_min, again_median=call_med2, again_min=call_min2),
+                               sample_plus_reduce_wall_us=dict(median=old_med, min=old_min), ratio_median=old_med / call_med,
+                               bytes_to_host=dict(gauge_levels=32 * COLUMNS * args.tiles, sample_plus_reduce=24 * COLUMNS * SAMPLES),
+                               bytes_to_device=dict(gauge_levels=0, sample_plus_reduce=8 * COLUMNS * SAMPLES * args.tiles),
+                               levels=[float(v) for v in rec["y"]])
+    off, on = [], []
+    block()  # (one block unmeasured)
+    for _ in range(args.rounds):
+        off.append(block())
+        if has and not args.no_record:
+            m.probe_record(points, gauges, max_frames=args.block, every=1)
+        ex0 = m.info()["exchanges"]
+        on.append(block())
+        ex1 = m.info()["exchanges"]
+        if has and not args.no_record:
+            assert m.probe_status()["frames"] == args.block
+            m.probe_record(max_frames=0)
+    out.update(recording=bool(has and not args.no_record), first_blocks_us=off, second_blocks_us=on, step_us_first=float(np.median(off)),
+               step_us_second=float(np.median(on)), exchanges_per_step_last_block=(ex1 - ex0) / args.block)
+    m.close()
+    return out
+
+
+def tiled_all(n, args):
+    """this library with the recording, and — with --parent-lib — the parent's library before and after it, in child processes"""
+    def run(lib, no_record):
+        cmd = [sys.executable, os.path.abspath(__file__), "--tiles", str(args.tiles), "--tiled-child", str(n), "--warmup", str(args.warmup), "--block",
+               str(args.block), "--rounds", str(args.rounds), "--calls", str(args.calls)]
+        cmd += (["--lib", lib] if lib else []) + (["--no-record"] if no_record else [])
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500)
+        if r.returncode != 0:
+            raise RuntimeError("child failed: %s\n%s" % (" ".join(cmd), r.stderr[-2000:]))
+        return json.loads(r.stdout.strip().splitlines()[-1])
+
+    runs = ([run(args.parent_lib, True)] if args.parent_lib else []) + [run(None, False)] + \
+        ([run(args.parent_lib, True), run(None, True)] if args.parent_lib else [])
+    return dict(runs=runs)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--particles", default="1000000,16000000")
@@ -201,7 +289,16 @@ def main():
     ap.add_argument("--child", type=int, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--lib", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--no-record", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--tiles", type=int, default=0, help="K > 0: the tiled run (sphx_multi_gauge_levels, sphx_multi_probe_record) in K tiles on device 0")
+    ap.add_argument("--tiled-child", type=int, default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.tiled_child is not None:
+        print(json.dumps(tiled(args.tiled_child, args)), flush=True)
+        return
+    if args.tiles:
+        for n in args.particles.split(","):
+            print(json.dumps(dict(particles=int(n), tiles=args.tiles, **tiled_all(int(n), args))), flush=True)
+        return
     if args.child is not None:
         child(args)
         return

@@ -17,7 +17,7 @@ from ._lib import (FLAG_DENSITY_ITER_CAP, FLAG_DIVERGENCE_ITER_CAP, FLAG_DENSE_C
 __all__ = ["SphxContext", "FluidParticleWorld", "TimeManager", "DFSPHSolver", "DFSPHMultiSolver", "default_params", "duration_from_secs_f32",
            "duration_as_secs_f32", "SphxError", "WCSPHSolver", "VISCOSITY_XSPH", "VISCOSITY_PHYSICAL", "SAMPLE_FIELDS", "gauge_elevation", "contour_chain", "contour_lines", "contour_merge",
            "sample_merge", "query_merge", "render_fit", "render_merge", "track_merge", "track_merge_frames", "write_png", "SCENE_RECT", "TRACK_FIELDS", "MULTI_TRACK_FIELDS", "FIELD_NAMES", "STATS_DTYPE", "STATS_FRAME_DTYPE",
-           "GAUGE_DTYPE", "GAUGE_REC_DTYPE", "PROBE_REC_DTYPE", "gauge_reduce"]
+           "GAUGE_DTYPE", "GAUGE_REC_DTYPE", "PROBE_REC_DTYPE", "gauge_reduce", "GAUGE_PART_DTYPE", "gauge_merge"]
 
 
 def _p(a):
@@ -237,6 +237,9 @@ GAUGE_DTYPE = np.dtype([("x0", "<f4"), ("y0", "<f4"), ("dx", "<f4"), ("dy", "<f4
 GAUGE_REC_DTYPE = np.dtype([("first", "<u4"), ("last", "<u4"), ("inside", "<u4"), ("t", "<f4"), ("x", "<f4"), ("y", "<f4"), ("f_last", "<f4"),
                             ("f_next", "<f4")])
 PROBE_REC_DTYPE = np.dtype([("density", "<f4"), ("fraction", "<f4"), ("velocity", "<f4", (2,)), ("count", "<u4"), ("reserved", "<u4", (3,))])
+# what one tile of a tiled run knows of a gauge (sphx_gauge_part): the interval it owns and the reduction over it; 32 bytes
+GAUGE_PART_DTYPE = np.dtype([("lo", "<u4"), ("count", "<u4"), ("first", "<u4"), ("last", "<u4"), ("inside", "<u4"), ("f_lo", "<f4"),
+                             ("f_last", "<f4"), ("f_next", "<f4")])
 
 
 def _gauge_array(gauges):
@@ -273,6 +276,21 @@ def gauge_reduce(values, gauges, iso=0.5):
     rc = _lib.lib().sphx_gauge_reduce(_p(v) if len(v) else None, _p(g) if len(g) else None, len(g), iso, _p(rec) if len(g) else rec.ctypes.data or 1)
     if rc:
         raise SphxError(rc, "sphx_gauge_reduce: invalid argument (see include/sphx.h, \"gauges and probes\")")
+    return rec
+
+
+def gauge_merge(parts, gauges, iso=0.5):
+    """sphx_gauge_merge: fold the tiles' (or ranks') parts of MultiSolver.gauges(..., tiles=True) — GAUGE_PART_DTYPE arrays [g], a list of
+    them or one array [p, g] — into the GAUGE_REC_DTYPE records [g] of `gauges` (the gauges and the iso of the calls that made the parts).
+    Host code; no GPU.  The parts with samples must tile every gauge exactly: a gap, an overlap or a wrong count raises SphxError."""
+    g = _gauge_array(gauges)
+    ps = [np.ascontiguousarray(p, GAUGE_PART_DTYPE).reshape(-1, len(g)) for p in ([parts] if isinstance(parts, np.ndarray) else parts)]
+    arr = np.ascontiguousarray(np.concatenate(ps, 0)) if ps else np.zeros((0, len(g)), GAUGE_PART_DTYPE)
+    rec = np.zeros(len(g), GAUGE_REC_DTYPE)
+    L = _lib.lib()
+    rc = L.sphx_gauge_merge(_p(g) if len(g) else None, len(g), iso, _p(arr) if arr.size else None, len(arr), rec.ctypes.data or 1)
+    if rc:
+        raise SphxError(rc, L.sphx_multi_last_error(None).decode())
     return rec
 
 
@@ -1751,6 +1769,19 @@ class DFSPHMultiSolver(DFSPHSolver):
 
     def sample_grid(self, origin, spacing, shape, kernel=KERNEL_WENDLAND_C2, fields=SAMPLE_FIELDS, tiles=False):
         return self.multi().sample_grid(origin, spacing, shape, kernel, fields, tiles)
+
+    # gauges and probes of the tiled run (MultiSolver.gauges and its recorder; the recorder fires behind every step of simulation_steps(k))
+    def gauges(self, gauges, iso=0.5, field="fraction", kernel=KERNEL_WENDLAND_C2, values=False, tiles=False):
+        return self.multi().gauges(gauges, iso, field, kernel, values, tiles)
+
+    def probe_record(self, points=None, gauges=None, max_frames=0, every=1, iso=0.5, field="fraction", kernel=KERNEL_WENDLAND_C2):
+        self.multi().probe_record(points, gauges, max_frames, every, iso, field, kernel)
+
+    def probe_status(self):
+        return self.multi().probe_status()
+
+    def probe_frames(self, first=0, count=None, tiles=False):
+        return self.multi().probe_frames(first, count, tiles)
 
     # the free surface of the tiled run (MultiSolver.contour: cut by the tiles, merged on the host in cell order)
     def contour(self, origin, spacing, shape, iso=0.5, field="fraction", kind=KERNEL_WENDLAND_C2, cap=None, tiles=False):

@@ -339,6 +339,17 @@ SIGNATURES = {
     "sphx_probe_record": (_i, [_vp, _vp, _u32, _vp, _u32, _i, _i, _f, _u32, _u32]),
     "sphx_probe_get_status": (_i, [_vp, C.POINTER(SphxProbeStatus)]),
     "sphx_probe_read": (_i, [_vp, _u32, _u32, _vp, _vp, _vp]),
+    "sphx_multi_gauge_levels": (_i, [_vp, _vp, _u32, _i, _i, _f, _u32, _vp, _vp, _vp]),
+    "sphx_gauge_merge": (_i, [_vp, _u32, _f, _vp, _u32, _vp]),
+    "sphx_multi_probe_record": (_i, [_vp, _vp, _u32, _vp, _u32, _i, _i, _f, _u32, _u32]),
+    "sphx_multi_probe_get_status": (_i, [_vp, C.POINTER(SphxProbeStatus)]),
+    "sphx_multi_probe_read": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "sphx_tile_gauge_levels": (_i, [_vp, _vp, _u32, _i, _i, _f]),
+    "sphx_tile_gauge_fetch": (_i, [_vp, _vp, _vp, _vp]),
+    "sphx_tile_probe_record": (_i, [_vp, _vp, _u32, _vp, _u32, _i, _i, _f, _u32, _u32]),
+    "sphx_tile_probe_due": (_i, [_vp]),
+    "sphx_tile_probe_frame": (_i, [_vp, _f, _u32]),
+    "sphx_tile_probe_read": (_i, [_vp, _u32, _u32, _vp, _vp, _vp]),
     "sphx_tile_fluid_stats": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32, _vp]),
     "sphx_tile_stats_record": (_i, [_vp, C.POINTER(SphxRect), _u32, _u32, _u32]),
     "sphx_tile_stats_frame": (_i, [_vp, _f, _u32]),

@@ -387,6 +387,17 @@ struct sphx_ctx {
         float iso = 0.0f;
         uint32_t recording = 0, max_frames = 0, every = 0, frames = 0, dropped = 0, steps = 0;  // steps: finished since sphx_probe_record
         std::vector<sphx_stats_frame> info;  // one entry per stored frame (host)
+        // a tile context (sphx_tile_gauge_* / sphx_tile_probe_*; sphx_gauge_levels and sphx_probe_* refuse a tile, so scratch, fixed and
+        // rec are its own here).  scratch: table | parts [8 n_gauges] | compact values; fixed: table | compact values [total] | points;
+        // rec: [max_frames][m_points] sphx_probe_rec with the "answered" mark, then [max_frames][n_gauges] sphx_gauge_part.
+        std::vector<sphx_gauge> gauges_host;    // recording: the caller's gauges (the interval table is rebuilt from them when the cuts move)
+        std::vector<uint32_t> table_lo_count;   // recording: the host's intervals {lo, count} per gauge the device table holds
+        uint32_t table_rect[4] = {0, 0, 0, 0};  // ... and the owned rectangle they were built for
+        bool table_valid = false;
+        uint32_t table_owned = 0;               // ... and their samples
+        std::vector<uint32_t> frame_lo_count;   // recording: the intervals of every stored frame [frames][2 n_gauges]
+        uint32_t shot_gauges = 0, shot_owned = 0;  // one-shot call in flight between sphx_tile_gauge_levels and _fetch
+        std::vector<uint32_t> shot_lo_count;
     } probe;
     bool uploaded = false, boundary_changed = true, tails_dirty = true, in_step = false;
     bool lists_current = false;  // the neighbour lists were built from the positions the arrays hold (raised by a completed build, dropped with q_noclamp)

@@ -41,6 +41,7 @@
 
 #include "../../include/sphx.h"
 #include "sphx_contour_merge.hpp"
+#include "sphx_gauge_merge.hpp"
 #include "sphx_multi_edit.hpp"
 #include "sphx_multi_state_format.hpp"
 #include "sphx_query_merge.hpp"
@@ -446,6 +447,19 @@ struct LocalComm : Comm {
     }
     void abort() override { sh->abort(); }
     const char* name() const override { return "in-process tiles (peer copies ordered by HIP events)"; }
+};
+
+// sphx_multi_probe_record: what the multi keeps of the recording (points and gauges are copied at the call; the tiles hold the frames).
+// A tile installs the recording of the current epoch in front of the first frame it is asked for, so a recording made before the first
+// upload — when the contexts are not tiles yet — works like any other.
+struct MultiProbe {
+    std::vector<float> points;
+    std::vector<sphx_gauge> gauges;
+    int kind = 0, field = 0;
+    float iso = 0.0f;
+    uint32_t max_frames = 0, every = 1;
+    bool on = false;
+    uint64_t epoch = 0;  // counts the sphx_multi_probe_record calls
 };
 
 // ---- one tile ---------------------------------------------------------------------------------------------------------------
@@ -1015,8 +1029,56 @@ struct TileDriver {
         TCHK(sphx_tile_stats_frame(ctx, dt, (uint32_t)n_owned_global));
         // sphx_multi_track_record: a frame of the tracked ids this tile owns, likewise
         TCHK(sphx_tile_track_frame(ctx));
+        // sphx_multi_probe_record: a frame of the gauges and probe points, likewise
+        if (probe && probe->on) {
+            rc = probe_frame(dt);
+            if (rc) return rc;
+        }
         if (st) *st = s;
         return SPHX_OK;
+    }
+
+    // sphx_multi_probe_*: the multi's recording and the epoch this tile has installed
+    const MultiProbe* probe = nullptr;
+    uint64_t probe_epoch = 0;
+    int probe_install() {
+        if (!probe || probe_epoch == probe->epoch) return SPHX_OK;
+        const MultiProbe& q = *probe;
+        const uint32_t mp = (uint32_t)(q.points.size() / 2), ng = (uint32_t)q.gauges.size();
+        const int rc = sphx_tile_probe_record(ctx, mp ? q.points.data() : nullptr, mp, ng ? q.gauges.data() : nullptr, ng, q.kind, q.field, q.iso,
+                                              q.on ? q.max_frames : 0u, q.every);
+        if (rc) {
+            err = std::string("sphx_tile_probe_record: ") + sphx_last_error(ctx);
+            return rc;
+        }
+        probe_epoch = q.epoch;
+        return SPHX_OK;
+    }
+    // One finished step.  A frame that is due reads ring-1 ghosts like a query: the band is made final first (sample_band(): with the
+    // band spent, the exchange the next step owes runs now — every tile takes the same decision — and that step then finds a full
+    // band), then the tile's passes go onto its stream.  Nothing is waited for.
+    int probe_frame(float dt) {
+        int rc = probe_install();
+        if (rc) return rc;
+        if (sphx_tile_probe_due(ctx) && (rc = sample_band())) return rc;
+        TCHK(sphx_tile_probe_frame(ctx, dt, (uint32_t)n_owned_global));
+        return SPHX_OK;
+    }
+    // sphx_multi_gauge_levels, first half: table, sample pass and reduce pass go onto the tile's stream; nothing is waited for
+    int gauge_enqueue(const sphx_gauge* gauges, uint32_t n_gauges, int kind, int field, float iso) {
+        const int rc = sphx_tile_gauge_levels(ctx, gauges, n_gauges, kind, field, iso);
+        if (rc) err = std::string("sphx_tile_gauge_levels: ") + sphx_last_error(ctx);  // (an argument or state error of one call: nobody is waiting in an all-reduce)
+        return rc;
+    }
+    // ... second half: the parts, the compact values and the host's intervals come back
+    std::vector<float> gauge_values;
+    std::vector<uint32_t> gauge_lo_count;
+    int gauge_fetch(sphx_gauge_part* parts, uint32_t n_gauges, uint64_t total, bool values) {
+        if (values && gauge_values.size() < total) gauge_values.resize(total);
+        gauge_lo_count.resize(2 * (size_t)n_gauges);
+        const int rc = sphx_tile_gauge_fetch(ctx, parts, values ? gauge_values.data() : nullptr, gauge_lo_count.data());
+        if (rc) err = std::string("sphx_tile_gauge_fetch: ") + sphx_last_error(ctx);
+        return rc;
     }
 
     // sphx_multi_fluid_stats, first half: this tile's records go onto its stream, into stats_dev; nothing is waited for
@@ -1297,6 +1359,7 @@ struct sphx_multi {
     bool state_broken = false;  // a sphx_multi_state_load found a digest mismatch after the copy: the multi asks for an upload or a load
     sphx::TrackSet track;  // sphx_multi_track_set: the host tables of the set every local tile has installed (the map to the caller's order lives here only)
     std::vector<uint32_t> sample_records;  // sphx_multi_sample_points: the tiles' packed records on the host (grown on demand, kept between calls)
+    MultiProbe probe;  // sphx_multi_probe_record: the recording (every tile points at it)
     uint64_t next_id = 0;  // sphx_multi_append: the id the next appended record gets (sphx_multi_edit::counter_after; the same on every rank)
 
     // run f(tile, index) on every tile, each on its own host thread (the tiles meet in barriers); returns the first error
@@ -1366,6 +1429,7 @@ int sphx_multi_create(const sphx_params* params, const int* devices, int n_devic
             g_multi_error = "tile " + std::to_string(r) + ": " + t->err;
             return rc;
         }
+        t->probe = &m->probe;
         m->tiles.push_back(std::move(t));
     }
     *out = m.release();
@@ -1404,6 +1468,7 @@ int sphx_multi_create_rank(const sphx_params* params, int device, const sphx_com
         g_multi_error = t->err;
         return rc;
     }
+    t->probe = &m->probe;
     m->tiles.push_back(std::move(t));
     *out = m.release();
     return SPHX_OK;
@@ -3132,6 +3197,187 @@ int sphx_multi_select(sphx_multi* m, const sphx_rect* rects, uint32_t n_rects, u
         at += totals[k];
     }
     out->count[0] = at;
+    return SPHX_OK;
+}
+
+}  // extern "C"
+
+// ---- gauges and probes of a tiled run (include/sphx.h, "gauges and probes of a tiled run"; the device passes are csrc/sphx_gauge.inc, the
+// intervals csrc/sphx_gauge_window.hpp, the fold csrc/sphx_gauge_merge.hpp) ---------------------------------------------------------------
+namespace {
+
+namespace gh = sphx_gauge_host;
+
+// the argument rules of sphx_gauge_levels that need no context, in its order; nullptr: they pass
+const char* gauge_args_error(const sphx_gauge* gauges, uint32_t n_gauges, int kind, int field, float iso, uint64_t* total) {
+    if (const char* bad = gh::check(gauges, n_gauges, iso, total)) return bad;
+    if (kind != SPHX_KERNEL_WENDLAND_C2 && kind != SPHX_KERNEL_POLY6 && kind != SPHX_KERNEL_SPIKY) return "unknown kernel_kind";
+    if (field != SPHX_GAUGE_FIELD_FRACTION && field != SPHX_GAUGE_FIELD_DENSITY) return "unknown field";
+    return nullptr;
+}
+
+bool probe_installed(const sphx_multi* m) { return m->probe.epoch != 0 && m->tiles[0]->probe_epoch == m->probe.epoch; }
+
+}  // namespace
+
+extern "C" {
+
+int sphx_gauge_merge(const sphx_gauge* gauges, uint32_t n_gauges, float iso, const sphx_gauge_part* parts, uint32_t n_parts, sphx_gauge_rec* out) {
+    auto bad = [](const char* what) {
+        g_multi_error = std::string("sphx_gauge_merge: ") + what;  // (no object to hang the message on: sphx_multi_last_error(NULL))
+        return SPHX_ERR_INVALID_ARGUMENT;
+    };
+    if (!out) return bad("out is NULL");
+    uint64_t total;
+    if (const char* b = gh::check(gauges, n_gauges, iso, &total)) return bad(b);
+    if (n_gauges && n_parts && !parts) return bad("parts is NULL with n_parts > 0");
+    if (const char* b = gh::merge(gauges, n_gauges, iso, parts, n_parts, out)) return bad(b);
+    return SPHX_OK;
+}
+
+int sphx_multi_gauge_levels(sphx_multi* m, const sphx_gauge* gauges, uint32_t n_gauges, int kernel_kind, int field, float iso, uint32_t flags,
+                            sphx_gauge_rec* out, float* values, sphx_gauge_part* out_parts) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    const char* const fn = "sphx_multi_gauge_levels";
+    if (!out && !m->rank_mode) return sample_bad(m, fn, "out is NULL");
+    uint64_t total = 0;
+    if (const char* b = gauge_args_error(gauges, n_gauges, kernel_kind, field, iso, &total)) return sample_bad(m, fn, b);
+    if (flags) return sample_bad(m, fn, "unknown flags bits (there is no device-pointer path across several devices)");
+    if (m->world > 64) return sample_bad(m, fn, "more than 64 tiles");
+    if (m->rank_mode && !out_parts) return sample_bad(m, fn, "out_parts is NULL in rank mode (the ranks' parts are folded with sphx_gauge_merge)");
+    if (n_gauges == 0) return SPHX_OK;
+    int rc;
+    if ((rc = multi_state_ready(m, fn, true))) return rc;
+    if ((rc = sample_band(m))) return rc;
+    // every local tile enqueues on its own stream and device first, then the parts are collected: the tiles' passes overlap
+    const size_t nt = m->tiles.size();
+    for (size_t k = 0; k < nt; ++k)
+        if ((rc = m->tiles[k]->gauge_enqueue(gauges, n_gauges, kernel_kind, field, iso))) return sample_tile_failed(m, k, rc);
+    std::vector<sphx_gauge_part> parts(nt * n_gauges);
+    for (size_t k = 0; k < nt; ++k) {
+        TileDriver& t = *m->tiles[k];
+        if ((rc = t.gauge_fetch(parts.data() + k * n_gauges, n_gauges, total, values != nullptr))) return sample_tile_failed(m, k, rc);
+        if (values) {  // the tile's compact values to offset(g) + lo
+            size_t at = 0, from = 0;
+            for (uint32_t g = 0; g < n_gauges; ++g) {
+                const uint32_t lo = t.gauge_lo_count[2 * (size_t)g], cnt = t.gauge_lo_count[2 * (size_t)g + 1];
+                if (cnt) std::memcpy(values + at + lo, t.gauge_values.data() + from, (size_t)cnt * 4);
+                from += cnt;
+                at += gauges[g].n;
+            }
+        }
+    }
+    if (!m->rank_mode) {
+        std::vector<gh::Words> rec(n_gauges);
+        for (uint32_t g = 0; g < n_gauges; ++g)
+            if (const char* b = gh::fold(gauges[g], iso, parts.data() + g, (uint32_t)nt, n_gauges, &rec[g])) {
+                m->err = std::string(fn) + ": gauge " + std::to_string(g) + ": " + b;
+                return SPHX_ERR_HIP;
+            }
+        std::memcpy(out, rec.data(), (size_t)n_gauges * sizeof(gh::Words));
+    }
+    if (out_parts) std::memcpy(out_parts, parts.data(), parts.size() * sizeof(sphx_gauge_part));
+    return SPHX_OK;
+}
+
+int sphx_multi_probe_record(sphx_multi* m, const float* points_xy, uint32_t m_points, const sphx_gauge* gauges, uint32_t n_gauges, int kernel_kind,
+                            int field, float iso, uint32_t max_frames, uint32_t every) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    const char* const fn = "sphx_multi_probe_record";
+    int rc;
+    if ((rc = multi_state_ready(m, fn, false))) return rc;
+    if (max_frames) {  // (checked before any tile is touched: all tiles keep the old recording or all get the new one)
+        if (every == 0) return sample_bad(m, fn, "every must be >= 1");
+        if (m_points >= (1u << 20)) return sample_bad(m, fn, "m_points must be < 2^20");
+        if (m_points && !points_xy) return sample_bad(m, fn, "points_xy is NULL with m_points > 0");
+        uint64_t total;
+        if (const char* b = gauge_args_error(gauges, n_gauges, kernel_kind, field, iso, &total)) return sample_bad(m, fn, b);
+        if (m_points + n_gauges == 0) return sample_bad(m, fn, "m_points + n_gauges is 0: nothing to record");
+        if ((uint64_t)max_frames * (m_points + n_gauges) * 32ull > (64ull << 20)) {
+            m->err = std::string(fn) + ": max_frames * (m_points + n_gauges) records exceed 64 MiB per tile";
+            return SPHX_ERR_CAPACITY;
+        }
+    }
+    MultiProbe& q = m->probe;
+    q.on = max_frames != 0;
+    q.points.assign(q.on && m_points ? points_xy : nullptr, q.on && m_points ? points_xy + 2 * (size_t)m_points : nullptr);
+    q.gauges.assign(q.on && n_gauges ? gauges : nullptr, q.on && n_gauges ? gauges + n_gauges : nullptr);
+    q.kind = kernel_kind, q.field = field, q.iso = iso;
+    q.max_frames = max_frames;
+    q.every = every ? every : 1u;
+    q.epoch += 1;
+    if (!m->uploaded) return SPHX_OK;  // (the contexts become tiles with the first upload: they install in front of their first frame)
+    for (size_t k = 0; k < m->tiles.size(); ++k)
+        if ((rc = m->tiles[k]->probe_install())) {
+            m->err = "tile " + std::to_string(k) + ": " + m->tiles[k]->err;
+            q.on = false;  // no half-made recording
+            q.epoch += 1;
+            for (auto& t : m->tiles) t->probe_install();
+            return rc;
+        }
+    return SPHX_OK;
+}
+
+// (every tile counts the same steps and stores the same number of frames: the first local tile speaks for all)
+int sphx_multi_probe_get_status(const sphx_multi* m, sphx_probe_status* out) {
+    if (!m || !out) return SPHX_ERR_INVALID_ARGUMENT;
+    if (probe_installed(m)) return sphx_probe_get_status(m->tiles[0]->ctx, out);
+    std::memset(out, 0, sizeof(*out));
+    const MultiProbe& q = m->probe;
+    if (!q.on) return SPHX_OK;
+    out->m_points = (uint32_t)(q.points.size() / 2);
+    out->n_gauges = (uint32_t)q.gauges.size();
+    out->recording = 1u;
+    out->max_frames = q.max_frames;
+    out->every = q.every;
+    return SPHX_OK;
+}
+
+int sphx_multi_probe_read(sphx_multi* m, uint32_t first_frame, uint32_t n_frames, sphx_probe_rec* points_out, int32_t* point_tile,
+                          sphx_gauge_rec* gauges_out, sphx_stats_frame* info) {
+    if (!m) return SPHX_ERR_INVALID_ARGUMENT;
+    const char* const fn = "sphx_multi_probe_read";
+    int rc;
+    if ((rc = multi_state_ready(m, fn, false))) return rc;
+    sphx_probe_status st;
+    sphx_multi_probe_get_status(m, &st);
+    if ((uint64_t)first_frame + n_frames > st.frames)
+        return sample_bad(m, fn, "first_frame + n_frames is beyond the frames recorded (sphx_multi_probe_get_status)");
+    if (n_frames == 0) return SPHX_OK;
+    if (m->world > 64) return sample_bad(m, fn, "more than 64 tiles");
+    if (m->rank_mode && gauges_out && st.n_gauges)
+        return sample_bad(m, fn, "gauges_out in rank mode (a rank holds parts: sphx_tile_probe_read, folded with sphx_gauge_merge)");
+    const size_t nt = m->tiles.size(), np = (size_t)n_frames * st.m_points, ng = (size_t)n_frames * st.n_gauges;
+    const bool want_points = (points_out || point_tile) && st.m_points, want_gauges = gauges_out && st.n_gauges;
+    std::vector<sphx_probe_rec> pts(want_points ? nt * np : 0);
+    std::vector<sphx_gauge_part> parts(want_gauges ? nt * ng : 0);
+    for (size_t k = 0; k < nt; ++k)
+        if ((rc = sphx_tile_probe_read(m->tiles[k]->ctx, first_frame, n_frames, want_points ? pts.data() + k * np : nullptr,
+                                       want_gauges ? parts.data() + k * ng : nullptr, k == 0 ? info : nullptr))) {
+            m->err = "tile " + std::to_string(k) + ": " + sphx_last_error(m->tiles[k]->ctx);
+            return rc;
+        }
+    if (want_points) {
+        std::vector<const sphx_probe_rec*> src(nt);
+        std::vector<int32_t> tile_of(nt);
+        for (size_t k = 0; k < nt; ++k) tile_of[k] = (int32_t)track_tile_rank(m, k);
+        for (uint32_t f = 0; f < n_frames; ++f) {
+            for (size_t k = 0; k < nt; ++k) src[k] = pts.data() + k * np + (size_t)f * st.m_points;
+            gh::fold_points(st.m_points, src.data(), tile_of.data(), (uint32_t)nt, points_out ? points_out + (size_t)f * st.m_points : nullptr,
+                            point_tile ? point_tile + (size_t)f * st.m_points : nullptr);
+        }
+    }
+    if (want_gauges) {
+        const MultiProbe& q = m->probe;
+        std::vector<gh::Words> rec(ng);
+        for (uint32_t f = 0; f < n_frames; ++f)
+            for (uint32_t g = 0; g < st.n_gauges; ++g)
+                if (const char* b = gh::fold(q.gauges[g], q.iso, parts.data() + (size_t)f * st.n_gauges + g, (uint32_t)nt, ng, &rec[(size_t)f * st.n_gauges + g])) {
+                    m->err = std::string(fn) + ": frame " + std::to_string(first_frame + f) + ", gauge " + std::to_string(g) + ": " + b;
+                    return SPHX_ERR_HIP;
+                }
+        std::memcpy(gauges_out, rec.data(), ng * sizeof(gh::Words));
+    }
     return SPHX_OK;
 }
 

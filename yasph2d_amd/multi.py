@@ -376,6 +376,81 @@ class MultiSolver:
         self._chk(self.L.sphx_multi_sample_grid(self.h, origin[0], origin[1], dx, dy, nx, ny, kernel, 0, C.byref(o)))
         return outs
 
+    # ---- gauges and probes of the tiled run (the contract is in include/sphx.h, "gauges and probes of a tiled run") ----
+    def gauges(self, gauges, iso=0.5, field="fraction", kernel=_lib.KERNEL_WENDLAND_C2, values=False, tiles=False):
+        """sphx_multi_gauge_levels: SphxContext.gauges for the tiled run — every sample is answered by the tile that owns its cell, each
+        tile reduces the samples it owns on its device, and the 32-byte parts are folded on the host: no sample value crosses unless
+        values=True asks for them.  Returns the GAUGE_REC_DTYPE array [g]; with values=True and / or tiles=True a tuple that adds the
+        float32 values [sum n] and / or the tiles' parts (GAUGE_PART_DTYPE [local tiles, g]), in that order.  If the ghost band is spent,
+        the halo exchange the next step owes happens now (collective in rank mode).  Rank mode: the records are None and the parts are
+        always returned; fold the ranks' parts with yasph2d_amd.gauge_merge."""
+        from . import GAUGE_PART_DTYPE, GAUGE_REC_DTYPE, _gauge_array
+
+        if field not in _lib.GAUGE_FIELDS:
+            raise ValueError("field must be one of %s, not %r" % (sorted(_lib.GAUGE_FIELDS), field))
+        g = _gauge_array(gauges)
+        total = int(g["n"].astype(np.int64).sum())
+        rank_mode = self._in_rank_mode()
+        rec = np.zeros(len(g), GAUGE_REC_DTYPE)
+        val = np.zeros(total, np.float32) if values else None
+        parts = np.zeros((self.info()["local_tiles"], len(g)), GAUGE_PART_DTYPE) if tiles or rank_mode else None
+        self._chk(self.L.sphx_multi_gauge_levels(self.h, _p(g) if len(g) else None, len(g), kernel, _lib.GAUGE_FIELDS[field], iso, 0,
+                                                 rec.ctypes.data or 1, (val.ctypes.data or 1) if values else None,
+                                                 (parts.ctypes.data or 1) if parts is not None else None))
+        res = (None if rank_mode else rec,) + ((val,) if values else ()) + ((parts,) if parts is not None else ())
+        return res[0] if len(res) == 1 else res
+
+    def probe_record(self, points=None, gauges=None, max_frames=0, every=1, iso=0.5, field="fraction", kernel=_lib.KERNEL_WENDLAND_C2):
+        """sphx_multi_probe_record: from now on every `every`-th finished multi step stores one frame on every tile's device —
+        sample(points)' four fields at the fixed points and the parts of gauges(gauges, iso, field, kernel) — up to max_frames frames
+        (later ones are counted in probe_status()["dropped"]); max_frames=0 stops and frees.  Works inside steps(timer, k) and may be
+        called before the first upload; nothing is synchronised beyond the halo exchange a frame may pull forward."""
+        from . import _gauge_array
+
+        if field not in _lib.GAUGE_FIELDS:
+            raise ValueError("field must be one of %s, not %r" % (sorted(_lib.GAUGE_FIELDS), field))
+        g = _gauge_array(gauges)
+        pts = np.zeros((0, 2), np.float32) if points is None else np.ascontiguousarray(points, np.float32)
+        if pts.ndim != 2 or pts.shape[1] != 2:
+            raise ValueError("points must be a float32 [m, 2] array, not shape %s" % (pts.shape,))
+        self._chk(self.L.sphx_multi_probe_record(self.h, _p(pts) if len(pts) else None, len(pts), _p(g) if len(g) else None, len(g), kernel,
+                                                 _lib.GAUGE_FIELDS[field], iso, max_frames, every))
+
+    def probe_status(self):
+        """sphx_multi_probe_get_status -> dict(m_points, n_gauges, recording, max_frames, every, frames, dropped)."""
+        st = _lib.SphxProbeStatus()
+        self._chk(self.L.sphx_multi_probe_get_status(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_ if k != "reserved"}
+
+    def probe_frames(self, first=0, count=None, tiles=False):
+        """sphx_multi_probe_read -> dict(points [count, m_points] of PROBE_REC_DTYPE, gauges [count, n_gauges] of GAUGE_REC_DTYPE, info
+        [count] of STATS_FRAME_DTYPE) for the recorded frames [first, first + count) (count=None: all from `first`), folded over the
+        tiles; tiles=True adds "point_tile": int32 [count, m_points], the tile that answered each point (-1: none).  Waits for the
+        tiles' streams.  Rank mode: "points" and "point_tile" are this rank's part, "gauges" is None and "parts" holds the rank's
+        GAUGE_PART_DTYPE [count, n_gauges] (fold each frame with yasph2d_amd.gauge_merge)."""
+        from . import GAUGE_PART_DTYPE, GAUGE_REC_DTYPE, PROBE_REC_DTYPE, STATS_FRAME_DTYPE
+
+        st = self.probe_status()
+        if count is None:
+            count = max(st["frames"] - first, 0)
+        rank_mode = self._in_rank_mode()
+        pts = np.zeros((count, st["m_points"]), PROBE_REC_DTYPE)
+        til = np.full((count, st["m_points"]), -1, np.int32) if tiles or rank_mode else None
+        gau = None if rank_mode else np.zeros((count, st["n_gauges"]), GAUGE_REC_DTYPE)
+        info = np.zeros(count, STATS_FRAME_DTYPE)
+        self._chk(self.L.sphx_multi_probe_read(self.h, first, count, _p(pts) if pts.size else None, _p(til) if til is not None and til.size else None,
+                                               _p(gau) if gau is not None and gau.size else None, _p(info) if count else None))
+        res = dict(points=pts, gauges=gau, info=info)
+        if til is not None:
+            res["point_tile"] = til
+        if rank_mode:
+            parts = np.zeros((count, st["n_gauges"]), GAUGE_PART_DTYPE)
+            if parts.size:
+                ctx = self.tile_context(0)
+                ctx._chk(self.L.sphx_tile_probe_read(ctx.h, first, count, None, _p(parts), None))
+            res["parts"] = parts
+        return res
+
     # ---- the free surface of the tiled run (the contract is in include/sphx.h, "free surface of a tiled run") ----
     def contour(self, origin, spacing, shape, iso=0.5, field="fraction", kind=_lib.KERNEL_WENDLAND_C2, cap=None, tiles=False):
         """sphx_multi_surface_contour: the contour `field == iso` of the lattice sample_grid(origin, spacing, shape) returns, cut by the
